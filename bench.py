@@ -12,16 +12,27 @@ batch on its shard, the per-shard (score, row) keys are exchanged with one RCCL 
 GATHER_EVERY batches and merged on the GPU.  Total work is fixed as N grows => "scaling": "strong".
 
 Rank 0 prints ONE JSON line.  `value`, `dtype` and `roofline` describe the scan over the fp16 ROWS (N * 1536 B per
-batch) at every N -- `--scan fp16` is the default and the operand is named in config.workload / config.scan.  Extra objects:
-  "roofline"      scan kernel: algorithmic bytes / HIP-event duration measured here, over the timed region
-  "cpu_baseline"  N = 1: oracle port, fp32 OpenBLAS brute force on this box's host cores, bounded sample
+batch) at every N -- `--scan fp16` is the default and the operand is named in config.workload / config.scan.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs DIR) and the line.
+Its `roofline` comes from the HIP events of the timed region (N = 1; none at N > 1, where the events are off).
+`--full` adds everything else, outside the timed region:
+  "roofline.isolated"  24 launches of the plain scan kernel on one stream (at N > 1 the roofline itself)
+  "timed_path_vs_exact_fp64_scan"  N = 1: the timed slots against the library's exact fp64 scan
+  "cpu_baseline"  N = 1: oracle port, fp32 OpenBLAS brute force on this box's host cores, bounded sample; with the oracle check of
+                  the timed slots (ids_exact, recall_at_10, max_abs_score_err)
   "int8_scan"     N = 1: the same loop with the library's int8 image of the shard as the scan operand (768 B per row read, +768 B
                   per row of HBM; every returned row is still re-scored in fp64 from the fp16 rows and certified): its own value,
                   roofline, traffic and oracle check
   "k100"          N = 1: the same loop at k = 100 (SURVEY 8(d) quotes configs[1] at k = 10 and k = 100), both operands
   "structured"    N = 1: both operands on document-structured and clustered 1M-row corpora (the int8 scan's data dependence)
   "host_api"      N = 1: the blocking host-buffer calls (rq_search, DenseIndex.search_vectors) beside `value`
+  "ids_match_exact_fp64_scan"  N > 1: the merged top-k against every rank's exact fp64 scan
+(--no-cpu-baseline / --no-extra-legs leave parts of that out.)
 `--scan int8` / `--scan auto` make the int8 image / the library's own rule the main figure instead (dtype then says "i8").
+`--dump-outputs DIR` writes what the timed path returned in its LAST step -- the merged top-k of that batch of 64 queries -- as
+DIR/scores.npy (float32 [64, k]) and DIR/rows.npy (global corpus rows as float64 [64, k]).  Corpus and queries are seeded, so two
+runs with the same arguments search the same inputs.
 """
 from __future__ import annotations
 
@@ -55,8 +66,11 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--rows", type=int, default=N_ROWS)
     ap.add_argument("--k", type=int, default=TOPK)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the int8_scan / structured / host_api legs that follow the timed region at N = 1")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, also run the calibration, exactness checks, CPU baseline and "
+                                                         "the other legs (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the scores and rows the timed path returned in its last step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg and the oracle check at N = 1")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the int8_scan / k100 / structured / host_api legs at N = 1")
     ap.add_argument("--streams", type=int, default=0, help="caller streams the batches alternate over (0 = 1 at one GPU, 2 at several)")
     ap.add_argument("--event-stride", type=int, default=4, help="HIP events around every n-th scan launch of the timed region")
     ap.add_argument("--scan", choices=("auto", "fp16", "int8"), default="fp16",
@@ -69,7 +83,11 @@ def main() -> None:
                     help="headline = BASELINE.json configs[1] (the metric); config2/3/4 = the other GPU configs at their shapes on ONE GPU "
                          "(tests/config_workloads.py, synthetic stand-ins), one JSON line each")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.workload != "headline":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the outputs of the headline workload")
         if int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.gpus != 1:
             raise SystemExit("--workload config2/3/4 are single-GPU legs")
         sys.path.insert(0, os.path.join(ROOT, "tests"))          # the harness lives with the tests (it uses the oracle as its checker)
@@ -162,6 +180,8 @@ def main() -> None:
             self.status_host = torch.zeros((N_QUERY_BATCHES, B), dtype=torch.int32).pin_memory()
             self.status_np = self.status_host.numpy()          # (view made once, outside the timed region)
             self.pending = {"n": 0, "ring": 0, "ev": [None, None]}
+            self.last = (0, 0)          # (result slot, position in the gathered ring) of the latest step
+            self.redone = False         # N > 1: fixup_all re-did the slots and wrote the merged results into them
             self.trains = None
             if use_comm:
                 self.ring = [torch.zeros((GATHER_EVERY, B, k), device=dev, dtype=torch.int64) for _ in range(2)]
@@ -209,6 +229,7 @@ def main() -> None:
             if use_hint:   # the batch this stream searches next: its queries are prepared by extra workgroups of this launch
                 idx.search_hint_next_device(self.qs[(i + len(streams)) % N_QUERY_BATCHES], B, s.cuda_stream)
             idx.search_device(self.qs[j], B, k, nat.METRIC_COSINE, o["scores"], o["rows"], keys, o["status"], s.cuda_stream)
+            self.last = (j, pending["n"])
             if use_comm:
                 pending["n"] += 1
                 if pending["n"] == GATHER_EVERY:
@@ -220,6 +241,7 @@ def main() -> None:
             while i < n:
                 if self.trains is not None and self.pending["n"] == 0 and i % N_QUERY_BATCHES == 0 and n - i >= GATHER_EVERY:
                     self.idx.search_train_device(self.trains[self.pending["ring"]], B, k, nat.METRIC_COSINE)
+                    self.last = ((i + GATHER_EVERY - 1) % N_QUERY_BATCHES, GATHER_EVERY - 1)
                     self.pending["n"] = GATHER_EVERY
                     self.flush()
                     i += GATHER_EVERY
@@ -243,6 +265,7 @@ def main() -> None:
             """certificate check of every slot (inside the timed region): repairs uncertified queries exactly"""
             k = self.k
             idx, fixed = self.idx, 0
+            self.redone = False
             nslots = min(N_QUERY_BATCHES, nsteps)
             bad = self.status_np[:nslots].any(axis=1)                          # (finish() has copied and synchronised)
             for j in np.nonzero(bad)[0].tolist():
@@ -252,6 +275,7 @@ def main() -> None:
                 if int(all_reduce_scalar(fixed)) > 0:
                     # rare: some shard repaired a query after its keys were gathered -> redo those batches synchronously
                     one = torch.zeros((world, B, k), device=dev, dtype=torch.int64)
+                    self.redone = True
                     for j in range(nslots):
                         o = self.slots[j]
                         idx.search_device(self.qs[j], B, k, nat.METRIC_COSINE, o["scores"], o["rows"], o["keys"], o["status"], 0)
@@ -330,6 +354,14 @@ def main() -> None:
             r["rows"] = [self.slots[j]["rows"].cpu().numpy().copy() for j in range(ns)]
             r["scores"] = [self.slots[j]["scores"].cpu().numpy().copy() for j in range(ns)]
             r["status"] = self.status_all[:ns].cpu().numpy().copy()
+            # what a caller of the timed path received for its last batch: the slot itself at one rank (and after a re-do at N > 1),
+            # else that batch's rows of the merged top-k of the last all-gather
+            j, pos = self.last
+            if use_comm and not self.redone:
+                r["last_scores"] = self.m_scores[pos * B:(pos + 1) * B].cpu().numpy().copy()
+                r["last_rows"] = self.m_rows[pos * B:(pos + 1) * B].cpu().numpy().copy()
+            else:
+                r["last_scores"], r["last_rows"] = r["scores"][j], r["rows"][j]
             return r
 
         def calibrate(self) -> dict:
@@ -379,11 +411,13 @@ def main() -> None:
 
     def roofline_of(r: dict, iso: dict, n_rows: int, live: bool) -> dict:
         """bytes the scan kernel must read per launch -- one pass over the fp16 shard (N * 768 * 2), or over its int8 image
-        (N * 768) when the int8 scan is in use; the library reports which (rq_timing.scan_bytes) -- over the average HIP-event duration"""
+        (N * 768) when the int8 scan is in use; the library reports which (rq_timing.scan_bytes) -- over the average HIP-event duration.
+        `iso` (the calibration launches) is None in a plain run: no `isolated` figure then, and no roofline without live events."""
         int8 = r["int8"]
         timing = r["timing"] if live else iso      # no per-launch events in the timed region: report the calibration launches
+        if timing is None:
+            return None
         scan_us = timing["scan_ms"] * 1e3 / max(timing["scan_launches"], 1)
-        iso_us = iso["scan_ms"] * 1e3 / max(iso["scan_launches"], 1)
         algo = timing["scan_bytes"] // max(timing["scan_launches"], 1) if timing["scan_launches"] else n_rows * DIM * (1 if int8 else 2)
         achieved = algo / (scan_us * 1e-6) / 1e9 if scan_us > 0 else 0.0
         # HBM traffic per launch is a PMC figure (rocprofv3 --pmc passes, tools/run_profiles.sh): it cannot be collected
@@ -398,18 +432,21 @@ def main() -> None:
                     break
                 except Exception:
                     traffic = None
-        return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+        roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "traffic": traffic, "traffic_source": traffic_source, "kernel": "rq_scan_tail_kernel" if args.pipeline == 2 else "rq_scan_kernel",
                 "avg_launch_us": scan_us, "launches": timing["scan_launches"], "algorithmic_bytes_per_launch": algo,
                 "scanned": "int8 image, 768 B per row" if int8 else "fp16 rows, 1536 B per row",
                 "measured": f"HIP events attached to every {max(1, args.event_stride)}-th scan dispatch of the timed region, on the stream it is launched on" if live else
-                            "HIP events around 24 single-stream launches right after the timed region (N > 1: no events inside it)",
-                "isolated": {"avg_launch_us": iso_us, "achieved": algo / (iso_us * 1e-6) / 1e9 if iso_us > 0 else 0.0,
-                             "frac": (algo / (iso_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if iso_us > 0 else 0.0,
-                             "note": "rq_scan_kernel alone (pipeline 0), 24 launches on one stream right after the timed region.  With one "
-                                     "caller stream (the N = 1 default) the live figure is the same scan with the previous batch's "
-                                     "tail workgroups riding along; with two caller streams a live interval would start when the launch "
-                                     "is dequeued and include the wait for the other stream's scan to release its workgroup slots"}}
+                            "HIP events around 24 single-stream launches right after the timed region (N > 1: no events inside it)"}
+        if iso is not None:
+            iso_us = iso["scan_ms"] * 1e3 / max(iso["scan_launches"], 1)
+            roof["isolated"] = {"avg_launch_us": iso_us, "achieved": algo / (iso_us * 1e-6) / 1e9 if iso_us > 0 else 0.0,
+                                "frac": (algo / (iso_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if iso_us > 0 else 0.0,
+                                "note": "rq_scan_kernel alone (pipeline 0), 24 launches on one stream right after the timed region.  With one "
+                                        "caller stream (the N = 1 default) the live figure is the same scan with the previous batch's "
+                                        "tail workgroups riding along; with two caller streams a live interval would start when the launch "
+                                        "is dequeued and include the wait for the other stream's scan to release its workgroup slots"}
+        return roof
 
     # ---- corpus shard: synthetic Gaussian rows, unit norm, fp16, generated in HBM ---------------
     idx = nat.NativeIndex(DIM, local_rank)
@@ -432,7 +469,11 @@ def main() -> None:
     loop = Loop(idx, queries)
     live_events = not use_comm or os.environ.get("RQ_BENCH_LIVE_EVENTS") == "1"
     main_r = loop.timed(args.scan, args.steps, args.warmup, live_events)
-    iso = loop.calibrate()
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), np.asarray(main_r["last_scores"], dtype=np.float32))
+        np.save(os.path.join(args.dump_outputs, "rows.npy"), np.asarray(main_r["last_rows"], dtype=np.float64))
+    iso = loop.calibrate() if args.full else None
     int8_scan = main_r["int8"]
     elapsed = main_r["elapsed"]
     out = {
@@ -460,11 +501,11 @@ def main() -> None:
         "exact_scans": main_r["timing"]["exact_scans"],
     }
 
-    # ---- outside the timed region (N = 1 only): exactness of the timed path, the other operand, structured corpora, host calls ----
-    if world == 1:
+    # ---- --full, outside the timed region (N = 1 only): exactness of the timed path, the other operand, structured corpora, host calls ----
+    if world == 1 and args.full:
         out["timed_path_vs_exact_fp64_scan"] = loop.exact_fp64_check(main_r, N_QUERY_BATCHES)
     int8_r = None
-    if world == 1 and not args.no_extra_legs:
+    if world == 1 and args.full and not args.no_extra_legs:
         # (a) the same loop over the other operand.  At --scan fp16 (default) this is the int8 image: half the bytes per pass, +768 B of
         #     HBM per row, and a data-dependent candidate count (see "structured" below)
         other = "fp16" if int8_scan else "int8"
@@ -524,7 +565,7 @@ def main() -> None:
         out["host_api"] = host_api
         idx.set_option("pipeline", args.pipeline)
 
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import dense_oracle as orc
         x16 = idx.get_rows_f16(0, n_local)
         # (c) the oracle: ALL queries of the first two slots of the TIMED (fused) path -- and of the int8 leg
@@ -577,7 +618,7 @@ def main() -> None:
                                          + ", ".join(f"{n_}: {t_ * 1e3:.0f} ms" for n_, t_ in trial.items()) + ")"}
         del cpu
 
-    if use_comm:
+    if use_comm and args.full:
         # N > 1 correctness evidence (outside the timed region): the benchmarked path = approximate scan + certified
         # re-score per shard -> RCCL all-gather of keys -> device merge, against the library's own EXACT path (every row
         # of the shard re-scored in fp64, no approximation, no certificate: option slack_bins >= number of bins) ->
@@ -609,7 +650,7 @@ def main() -> None:
     del loop, idx
 
     # ---- N = 1: both operands on structured corpora (after the main index is gone: one 1M-row corpus in HBM at a time) ----------
-    if world == 1 and not args.no_extra_legs and n_total >= 200_000:
+    if world == 1 and args.full and not args.no_extra_legs and n_total >= 200_000:
         try:
             out["structured"] = structured_leg(nat, torch, np, dev, n_total, k, Loop, sync_all)
         except Exception as e:

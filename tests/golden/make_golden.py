@@ -15,6 +15,11 @@ What is captured (inputs + the reference's outputs, nothing of its source):
                           consumer of the hot path that BASELINE.json configs[4] feeds
   g4_oracle_dense.json    the oracle's own answers on seeded inputs (regression pin of oracle/dense_oracle.py;
                           NOT a reference output: the reference's dense arithmetic lives in ChromaDB, absent here)
+  g7_dropin.json          tests/test_reference_dropin.py's scenarios: what this package's HybridRetriever returns, fed to the
+                          reference's RetrievalRouter.hybrid_rerank (seeded as for g2) and RAGEvaluator._recall_at_k; and the
+                          reference's HybridRetriever.hybrid_search over this package's BM25Index (+ the test's stand-in dense index)
+
+`python tests/golden/make_golden.py g7_dropin.json` rewrites only the named files.
 """
 import json
 import os
@@ -166,20 +171,59 @@ def run_oracle_pin():
     return out
 
 
-def main():
-    dumps = {
-        "g1_hybrid_fusion.json": run_fusion(),
-        "g2_router.json": run_router(),
-        "g3_retrieval_metrics.json": run_metrics(),
-        "g5_hash_embedding.json": run_hash_embedding(),
-        "g6_records.json": run_records(),
-        "g4_oracle_dense.json": run_oracle_pin(),
+def run_dropin():
+    import torch
+    from rag_uq.router import RetrievalRouter, RouterConfig
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_reference_dropin import CORPUS, QUERIES, QUESTIONS, FakeDense, positive
+    from rag_uq_amd import streaming_index as si
+    tmp = tempfile.mkdtemp()
+    r = si.HybridRetriever(bm25_persist_path=os.path.join(tmp, "b.pkl"), chroma_persist_path=os.path.join(tmp, "c"), dense_index=FakeDense())
+    r.add_documents([si.Document(id=i, text=t) for i, t in CORPUS])
+    torch.manual_seed(0)
+    model = RetrievalRouter(RouterConfig()).eval()
+    evaluator = RAGEvaluator(output_dir=os.path.join(tmp, "res"))
+    questions = []
+    for question, answer_doc in QUESTIONS:
+        bm25, dense, ids, texts = r.get_scores_for_router(question, num_passages=10)        # run_evaluation.py:165-173
+        with torch.no_grad():
+            top_s, top_i = model.hybrid_rerank(torch.tensor([bm25]), torch.tensor([dense]), top_k=5)
+        order = [int(i) for i in top_i.reshape(-1)[:5]]
+        retrieved = [ids[i] for i in order if ids[i]]
+        questions.append(dict(question=question, answer_doc=answer_doc, bm25=[float(x) for x in bm25], dense=[float(x) for x in dense],
+                              ids=list(ids), texts=list(texts), rerank_scores=top_s[0].tolist(), rerank_indices=order, retrieved=retrieved,
+                              recall_at_5=float(evaluator._recall_at_k(retrieved, [answer_doc], 5))))
+    router = dict(num_passages=10, top_k=5, questions=questions, recall_at_5=float(np.mean([q["recall_at_5"] for q in questions])))
+    theirs = ref.HybridRetriever(bm25_persist_path=os.path.join(tmp, "x.pkl"), chroma_persist_path=os.path.join(tmp, "c3"))
+    theirs.bm25_index = si.BM25Index()
+    theirs.dense_index = FakeDense()
+    docs = [ref.Document(id=i, text=t) for i, t in CORPUS]
+    theirs.bm25_index.add_documents(docs)            # (their add_documents skips empty indexes: `if self.bm25_index:` defect)
+    theirs.dense_index.add_documents(docs)
+    theirs.documents = {d.id: d for d in docs}
+    hybrid = dict(top_k=5, pool=50, queries=[dict(query=q, bm25_search=[[d, float(s)] for d, s in theirs.bm25_search(q, 50)],
+                                                  positive=positive(theirs.hybrid_search(q, top_k=5, retrieval_pool_size=50))) for q in QUERIES])
+    return dict(router=router, hybrid=hybrid)
+
+
+def main(names=None):
+    builders = {
+        "g1_hybrid_fusion.json": run_fusion,
+        "g2_router.json": run_router,
+        "g3_retrieval_metrics.json": run_metrics,
+        "g5_hash_embedding.json": run_hash_embedding,
+        "g6_records.json": run_records,
+        "g4_oracle_dense.json": run_oracle_pin,
+        "g7_dropin.json": run_dropin,
     }
-    for name, obj in dumps.items():
+    for name, build in builders.items():
+        if names and name not in names:
+            continue
+        obj = build()
         with open(os.path.join(HERE, name), "w") as f:
             json.dump(obj, f, indent=1, sort_keys=True)
         print("wrote", name)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

@@ -705,7 +705,7 @@ def test_wide_batches_at_headline_size_match_oracle():
     idx.close()
 
 
-def test_nomic_bert_embedder_end_to_end_random_init():
+def test_nomic_bert_embedder_end_to_end_random_init(tmp_path):
     """BASELINE.json configs[3] shape: raw text -> PyTorch-ROCm NomicBert forward -> HIP search.  No weights are
     available offline, so the architecture runs with random weights (2 layers to keep the test quick) and a
     byte-level stand-in tokenizer: this checks plumbing and exactness of the search over the produced embeddings,
@@ -719,7 +719,7 @@ def test_nomic_bert_embedder_end_to_end_random_init():
     texts = [f"passage {i}: the quick brown fox number {i * 7919 % 1000} jumps over topic {i % 13}" for i in range(600)]
     vec = emb.embed(texts)
     assert vec.shape == (600, 768) and np.isfinite(vec).all()
-    idx = si.DenseIndex(persist_directory="/tmp/rq_test_nomic", embedder=emb, load_persisted=False)
+    idx = si.DenseIndex(persist_directory=str(tmp_path / "nomic"), embedder=emb, load_persisted=False)
     assert idx.add_documents([si.Document(id=f"p{i}", text=t) for i, t in enumerate(texts)], batch_size=256) == 600
     queries = [texts[5], texts[123], "an unrelated question about rivers"] + [f"query text {i}" for i in range(253)]   # 256 raw text queries
     res = idx.search_batch(queries, top_k=10)
@@ -991,7 +991,7 @@ def test_sharded_searcher_over_rccl_world_of_one():
         dist.destroy_process_group()
 
 
-def test_multi_device_index_in_one_process():
+def test_multi_device_index_in_one_process(tmp_path):
     """rows block-distributed over several 'devices' of one process (here the same GPU twice / three times):
     stripe mapping, host merge, incremental appends, duplicates across shards"""
     from rag_uq_amd import distributed as d
@@ -1012,8 +1012,8 @@ def test_multi_device_index_in_one_process():
     # through the reference-shaped class
     from rag_uq_amd.embedders import HashEmbedder
     docs = [si.Document(id=f"p{i}", text=f"passage {i} item {i * 37 % 211}") for i in range(400)]
-    one = si.DenseIndex(persist_directory="/tmp/rq_md_1", embedder=HashEmbedder(), load_persisted=False)
-    many = si.DenseIndex(persist_directory="/tmp/rq_md_2", embedder=HashEmbedder(), devices=[0, 0], load_persisted=False,
+    one = si.DenseIndex(persist_directory=str(tmp_path / "md_1"), embedder=HashEmbedder(), load_persisted=False)
+    many = si.DenseIndex(persist_directory=str(tmp_path / "md_2"), embedder=HashEmbedder(), devices=[0, 0], load_persisted=False,
                          backend_options={"stripe_rows": 64})
     one.add_documents(docs); many.add_documents(docs[:150]); many.add_documents(docs[150:])
     for text in ["passage 7 item 48", "item 100", docs[333].text]:

@@ -473,7 +473,7 @@ def test_batched_fusion_in_row_space_equals_the_per_query_path(tmp_path, metric)
 
 
 def test_committed_bench_line_has_the_contract_shape():
-    """profiles/r03_bench20.json is a `python bench.py --steps 20 --warmup 5` line from the GPU box (tools/run_profiles.sh): the keys the
+    """profiles/r03_bench20.json is a `python bench.py --full --steps 20 --warmup 5` line from an MI355X (tools/run_profiles.sh): the keys the
     driver and the review read, on BASELINE's basis -- fp16 rows as `value`, 1536 B per row in the roofline, the int8 image and the
     structured corpora as sibling objects -- and the internal consistency of the numbers (kernel <= step, achieved = bytes / time)."""
     import os

@@ -2,9 +2,10 @@
 
     python tools/make_profiles.py r01
 
-expects  gpurun_out/prof_bench/*/*kernel_stats.csv      rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline
-         gpurun_out/pmc_fetch/*/*counter_collection.csv  rocprofv3 --pmc FETCH_SIZE -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
-         gpurun_out/pmc_write/*/*counter_collection.csv  rocprofv3 --pmc WRITE_SIZE -- (same)
+expects, in the output directory of tools/run_profiles.sh:
+         prof_bench/*/*kernel_stats.csv      rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-extra-legs
+         pmc_fetch/*/*counter_collection.csv  rocprofv3 --pmc FETCH_SIZE -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra-legs
+         pmc_write/*/*counter_collection.csv  rocprofv3 --pmc WRITE_SIZE -- (same)
 """
 import csv, glob, json, os, sys
 
