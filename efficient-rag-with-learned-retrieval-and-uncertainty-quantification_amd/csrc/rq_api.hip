@@ -320,6 +320,7 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     else if (s == "bin_bound") idx->bin_bound = (int)v != 0;     // A/B: 0 = every bin is tested with the shard's worst row error (round 2)
     else if (s == "tail_local") idx->tail_local = (int)v != 0;   // A/B: 0 = every re-scored row's key goes to the query's global list
     else if (s == "use_hint") idx->use_hint = (int)v != 0;   // 0: rq_search_hint_next_device is ignored (A/B of the folded query preparation)
+    else if (s == "scan_ahead") idx->scan_ahead = (int)v != 0;   // 0: a hinted batch is never scanned together with the call before it (A/B)
     else if (s == "poison_cand") idx->poison_cand = (int)v;   // test hook: candidate lists are filled with 0xff..ff keys before every tail
     else return set_err(RQ_EINVAL, "unknown option '%s'", name);
     return RQ_OK;
@@ -349,6 +350,7 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
     if (s == "eps") return idx->eps < 0 ? RQ_EPS_DEFAULT : idx->eps;   // the base bound; "eps_cosine" / "eps_ip": with the shard's flush term
     if (s == "profile") return idx->profile;
     if (s == "fast_tail") return idx->fast_tail;
+    if (s == "scan_ahead") return idx->scan_ahead;
     if (s == "pipeline") return idx->pipeline;
     if (s == "profile_stride") return idx->profile_stride;
     if (s == "cu_count") return idx->cu_count;
@@ -601,6 +603,15 @@ static int poison_cand(const rq_index* idx, const RqTailArgs& t, int B, hipStrea
     return RQ_OK;
 }
 
+// "scan_ahead": the half of a pair that was scanned ahead is not claimed (another call came, or a flush).  The first batch's
+// tail becomes an ordinary pending tail -- it rides with the next fused launch of the stream or runs at the flush -- and the
+// second half's records are never read.
+static void drop_pair(StreamCtx& c) {
+    if (!c.pair_pending) return;
+    c.pair_pending = false;
+    c.fused_tail = c.pair_tail; c.fused_B = c.pair_B; c.fused_pending = true;
+}
+
 // Make `s` wait for every tail still running on the internal tail stream of `s` (pipeline = 1) and launch the
 // tail that was waiting for the next scan (pipeline = 2).
 static int flush_tails(rq_index* idx, hipStream_t s) {
@@ -608,6 +619,7 @@ static int flush_tails(rq_index* idx, hipStream_t s) {
     if (it == idx->ctx.end()) return RQ_OK;
     StreamCtx& c = it->second;
     c.hint_q = nullptr;   // a flush ends the loop the hint belonged to (queries already prepared stay usable)
+    drop_pair(c);
     if (c.fused_pending) {
         c.fused_pending = false;
         if (int r = poison_cand(idx, c.fused_tail, c.fused_B, s)) return r;
@@ -626,7 +638,7 @@ static int flush_tails(rq_index* idx, hipStream_t s) {
 // is drained first -- every scan those tails depend on has then finished -- and the tails run on the index's own stream.
 static int flush_all(rq_index* idx) {
     bool any = false;
-    for (auto& kv : idx->ctx) any = any || kv.second.fused_pending || kv.second.tail_pending[0] || kv.second.tail_pending[1];
+    for (auto& kv : idx->ctx) any = any || kv.second.fused_pending || kv.second.pair_pending || kv.second.tail_pending[0] || kv.second.tail_pending[1];
     if (!any) return RQ_OK;
     RQ_ON_DEVICE(idx);
     HIPCHK(hipDeviceSynchronize());
@@ -634,6 +646,7 @@ static int flush_all(rq_index* idx) {
         StreamCtx& c = kv.second;
         c.hint_q = nullptr;
         c.tail_pending[0] = c.tail_pending[1] = false;   // (their events have fired: the device is idle)
+        drop_pair(c);
         if (!c.fused_pending) continue;
         c.fused_pending = false;
         if (int r = poison_cand(idx, c.fused_tail, c.fused_B, idx->own_stream)) return r;
@@ -662,6 +675,38 @@ extern "C" int rq_stream_release(rq_index* idx, void* stream) {
     RQ_ON_DEVICE(idx);
     if (idx->ctx.find((hipStream_t)stream) == idx->ctx.end()) return RQ_OK;
     return release_contexts(idx, (hipStream_t)stream, false);
+}
+
+// Preparation of B queries at q into ring slot `slot` of a stream (64 workgroups: slots >= B are written as zero).
+static RqPrepArgs ring_prep(const rq_index* idx, const StreamCtx& c, const float* q, int B, int slot) {
+    RqPrepArgs pa{};
+    pa.q = q; pa.dim = idx->dim; pa.B = B; pa.nslots = 64;
+    pa.qh = c.ring_qh[slot]; pa.q32pad = c.ring_q32[slot]; pa.qnorm64 = c.ring_qn[slot];
+    pa.q8 = c.ring_q8[slot]; pa.qscale8 = c.ring_qscale8[slot]; pa.qeps8 = c.ring_qeps8[slot];
+    pa.q8lo = c.ring_q8lo[slot]; pa.qeps8s = c.ring_qeps8s[slot];
+    return pa;
+}
+
+// Second call of a scanned-ahead pair (option "scan_ahead", see run_pipeline): the previous call's 128-query pass has written
+// this batch's records, so no scan is enqueued.  ONE launch runs the tails of both batches -- the previous call's outputs and
+// this call's, each with its own k -- and prepares the batch this call announces into the next ring slot.
+static int pair_second(rq_index* idx, StreamCtx& cx, int B, int k, float* d_scores, int64_t* d_rows, uint64_t* d_keys, int* d_status, hipStream_t s) {
+    const int slot = (int)(cx.calls++ % 3);   // the slot the pass read this batch from
+    cx.pair_pending = false;
+    cx.prepped_q = nullptr;
+    idx->hints_used++;
+    idx->last_use8 = false; idx->last_wide1 = false;
+    RqTailArgs t1 = cx.pair_next;
+    t1.k = k; t1.m = (int)std::min<int64_t>(k, idx->n);
+    t1.out_scores = d_scores; t1.out_rows = d_rows; t1.out_keys = d_keys; t1.out_status = d_status;
+    RqPrepArgs pa{};
+    if (cx.hint_q) pa = ring_prep(idx, cx, cx.hint_q, cx.hint_B, (slot + 1) % 3);
+    if (int r = poison_cand(idx, cx.pair_tail, cx.pair_B, s)) return r;
+    if (int r = poison_cand(idx, t1, B, s)) return r;
+    HIPCHK(rq_pair_tail_launch(cx.pair_tail, cx.pair_B, t1, B, pa, s));
+    if (pa.nslots) { cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = (slot + 1) % 3; }
+    cx.hint_q = nullptr;
+    return RQ_OK;
 }
 
 // One pass of the pipeline for B queries.  nb < 0: exact scan (every bin re-scored, no corpus scan).
@@ -741,6 +786,17 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
     const bool piped = fast && may_defer && idx->pipeline == 1;
     // fused mode: one scan launch per call (<= 64 queries), which carries the tail of the previous call
     const bool fused = fast && may_defer && idx->pipeline == 2 && bpad == 64;
+    if (cx.pair_pending) {   // the previous call scanned this stream's announced batch ahead (below)
+        if (fused && !use8 && d_q == cx.pair_q && B == cx.pair_qB && metric == cx.pair_metric)
+            return pair_second(idx, cx, B, k, d_scores, d_rows, d_keys, d_status, s);
+        drop_pair(cx);
+    }
+    // Option "scan_ahead": a fused call over the fp16 rows whose stream has announced its next batch (rq_search_hint_next_device)
+    // scans BOTH in one 128-query pass (rq_scan_wide.hip variant 0: 266-268 us at 1M rows against 237 us for 64 queries); the
+    // next call, if it brings the announced batch, only runs the two tails (pair_second).  Only on shards the Infinity Cache
+    // cannot hold (the rule of the non-temporal loads below): smaller shards are not bound by HBM bytes.
+    const bool pair = fused && !use8 && idx->scan_ahead && cx.hint_q && cx.hint_B <= 64 &&
+                      idx->n * (int64_t)(RQ_DPAD * 2) > ((int64_t)208 << 20);
     int par = 0, slot = -1;
     if (fused) {
         slot = (int)(cx.calls % 3);
@@ -773,7 +829,8 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
     }
     if (!fused) cx.hint_q = nullptr;   // a hint is for the next FUSED call of the stream only
     Workspace& w = cx.w[par];
-    if (int r = ensure_ws(w, bpad, exact ? 64 : stride, exact ? 1 : m, (size_t)B * (size_t)ncand)) return r;
+    // (a pair: the announced batch's records, candidates and counters take query slots 64..127 of the same workspace)
+    if (int r = ensure_ws(w, pair ? 128 : bpad, exact ? 64 : stride, exact ? 1 : m, (size_t)(pair ? 128 : B) * (size_t)ncand)) return r;
     const float* scale = idx->inv_norm;
     if (metric == RQ_METRIC_IP) { if (int r = ensure_ones(idx, s)) return r; scale = idx->ones; }
 
@@ -807,12 +864,20 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
     }
     // the queries announced for the NEXT call are prepared by extra workgroups of this call's fused launch
     RqPrepArgs pa{};
-    if (fused && cx.hint_q) {
-        const int nslot = (slot + 1) % 3;
-        pa.q = cx.hint_q; pa.dim = idx->dim; pa.B = cx.hint_B; pa.nslots = 64;
-        pa.qh = cx.ring_qh[nslot]; pa.q32pad = cx.ring_q32[nslot]; pa.qnorm64 = cx.ring_qn[nslot];
-        pa.q8 = cx.ring_q8[nslot]; pa.qscale8 = cx.ring_qscale8[nslot]; pa.qeps8 = cx.ring_qeps8[nslot];
-        pa.q8lo = cx.ring_q8lo[nslot]; pa.qeps8s = cx.ring_qeps8s[nslot];
+    if (fused && cx.hint_q) pa = ring_prep(idx, cx, cx.hint_q, cx.hint_B, (slot + 1) % 3);
+    if (pair) {
+        // the pass reads the announced batch from the next ring slot: it is prepared first, by a launch of its own; and a tail
+        // still waiting for a scan (the call before this one was not paired) runs on its own, as the wide pass carries none
+        HIPCHK(rq_prep_queries_launch(pa, s));
+        cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = (slot + 1) % 3;
+        cx.pair_q = cx.hint_q; cx.pair_qB = cx.hint_B; cx.pair_metric = metric;
+        cx.hint_q = nullptr;
+        pa.nslots = 0;
+        if (cx.fused_pending) {
+            cx.fused_pending = false;
+            if (int r = poison_cand(idx, cx.fused_tail, cx.fused_B, s)) return r;
+            HIPCHK(rq_tail_launch(cx.fused_tail, cx.fused_B, s));
+        }
     }
     // Scan grids.  Every fp16 pass of more than 64 queries, and the int8 256-query pass, runs ONE 512-thread workgroup per CU ("wide");
     // the 64-query passes and the int8 128-query pass run wg_per_cu 256-thread workgroups per CU.  A call's passes are cut widest first,
@@ -834,6 +899,7 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
     const int grid_wide = (int)std::min<int64_t>(std::min<int64_t>(nquads, RQ_WGMAX_STRIDE), (int64_t)idx->cu_count);
     int nwg_split = bpad;                                          // first query of the first narrow pass
     for (int blk = npass - 1, q0 = bpad; blk >= 0 && !pass_wide(pass_q[blk]); --blk) nwg_split = (q0 -= pass_q[blk]);
+    if (pair) nwg_split = 64;                                      // both batches of a pair: the wide grid
     if (!exact) {
         // non-temporal loads only for shards that cannot stay in the 256 MiB Infinity Cache between two scans
         // (measured: 192 MB shard 36 us with default policy vs 39 us nt; 1.5 GB shard 250 us nt vs 285 us default)
@@ -846,11 +912,12 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
             a.x = idx->x;
             a.row_scale = scale;
             a.qh = qh + (size_t)q0 * RQ_DPAD;
+            a.qh_hi = pair ? cx.ring_qh[(slot + 1) % 3] : nullptr;
             a.bins = w.bins + (size_t)q0 * w.bins_stride;
             a.bins_stride = w.bins_stride;
             a.n_rows = idx->n;
             a.nquads = nquads;
-            a.nq_valid = idx->scan_nostore == 1 ? 0 : std::min(qb, B - q0);
+            a.nq_valid = idx->scan_nostore == 1 ? 0 : pair ? 64 + cx.pair_qB : std::min(qb, B - q0);
             a.wgmax = w.wgmax + (size_t)q0 * RQ_WGMAX_STRIDE;
             a.wgmax_stride = RQ_WGMAX_STRIDE;
             if (use8) {
@@ -869,7 +936,8 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
                 e0 = idx->events[idx->ev_used].first; e1 = idx->events[idx->ev_used].second;
                 if (idx->profile_legacy) { HIPCHK(hipEventRecord(e0, s)); e0 = e1 = nullptr; }   // A/B: hipEventRecord around the launch
             }
-            if (fused && cx.fused_pending) {
+            if (pair) HIPCHK(rq_scan_wide_launch(a, 0, 128, nt, grid, s, e0, e1));   // compiler-scheduled LDS reads only (never 8: DESIGN 4.4)
+            else if (fused && cx.fused_pending) {
                 cx.fused_pending = false;
                 if (int r = poison_cand(idx, cx.fused_tail, cx.fused_B, s)) return r;
                 if (idx->tail_stop == 9) {   // development: fused kernel without its tail workgroups, tail launched after it
@@ -929,6 +997,14 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
                 // the tail runs with the NEXT scan launch (or at the flush): it reads the workspace's own copy of the
                 // queries, so the caller's buffer is free as soon as this call's work has run
                 ta.q = q32; ta.dim = RQ_DPAD;
+                if (pair) {   // the announced batch: slots 64..127 of the pass and of the workspace, its own queries' copy
+                    RqTailArgs t1 = ta;
+                    t1.q = cx.ring_q32[(slot + 1) % 3];
+                    t1.bins = w.bins + 64 * w.bins_stride; t1.wgmax = w.wgmax + 64 * RQ_WGMAX_STRIDE;
+                    t1.cand = w.cand + (size_t)64 * RQ_CAND_CAP; t1.rowcount = w.rowcount + 64; t1.done = w.done + 64; t1.ovf = w.ovf + 64;
+                    cx.pair_tail = ta; cx.pair_B = B; cx.pair_next = t1; cx.pair_pending = true;
+                    return RQ_OK;
+                }
                 cx.fused_tail = ta; cx.fused_B = B; cx.fused_pending = true;
                 return RQ_OK;
             }

@@ -92,6 +92,15 @@ struct StreamCtx {
     int hint_B = 0;
     const float* prepped_q = nullptr;   // queries a launch has already prepared ...
     int prepped_B = 0, prepped_slot = -1;   // ... and the slot they are in
+    // option "scan_ahead": ONE 128-query pass has scanned this stream's last call (ring slot i) together with the batch it
+    // announced (slot i + 1), into the two halves of that call's workspace.  The first batch's tail waits in pair_tail; the
+    // second half's tail (pair_next, without k / m / outputs) belongs to the next call if it brings pair_q, pair_qB and
+    // pair_metric; anything else (another call, a flush) runs pair_tail alone and discards the second half.
+    bool pair_pending = false;
+    RqTailArgs pair_tail, pair_next;
+    int pair_B = 0;
+    const float* pair_q = nullptr;
+    int pair_qB = 0, pair_metric = -1;
 };
 
 // Default scan variant: half-row stages (kstage 2), ring of 3, one LDS fragment ahead (prefetch 1, <= 168 VGPRs),
@@ -133,10 +142,10 @@ struct rq_index {
     bool wide1_ok[2] = {false, false}, wide1_off[2] = {false, false}, last_wide1 = false;
     int64_t wide1_checked[2] = {0, 0}, wide1_repaired[2] = {0, 0};
     int64_t repaired_total = 0;    // queries that came back uncertified and were repaired (any rung of the repair ladder)
-    int64_t hints_used = 0;        // rq_search_hint_next_device: searches that skipped their preparation launch
+    int64_t hints_used = 0;        // rq_search_hint_next_device: searches whose queries a launch before them prepared or scanned ahead
     uint64_t scan_seq = 0;         // scan launches seen while profile = 1 (every profile_stride-th one is timed)
     // options
-    int ring = 3, prefetch = 1, kstage = 2, wide_batch = 1, wg_per_cu = 2, nt = -1, slack_bins = -1, profile = 0, profile_stride = 1, scan_nostore = 0, fast_tail = 1, pipeline = 0, tail_stop = 0, poison_cand = 0, wide128 = 0, wide256 = 2, epi = 1, use_hint = 1, profile_legacy = 0, scan8 = 1, tail_local = 1, scan8_split = -1, wide8 = 1, wide256_8 = 31, bin_bound = 1, exact_mfma = 1, fused_nv = 0;
+    int ring = 3, prefetch = 1, kstage = 2, wide_batch = 1, wg_per_cu = 2, nt = -1, slack_bins = -1, profile = 0, profile_stride = 1, scan_nostore = 0, fast_tail = 1, pipeline = 0, tail_stop = 0, poison_cand = 0, wide128 = 0, wide256 = 2, epi = 1, use_hint = 1, scan_ahead = 1, profile_legacy = 0, scan8 = 1, tail_local = 1, scan8_split = -1, wide8 = 1, wide256_8 = 31, bin_bound = 1, exact_mfma = 1, fused_nv = 0;
     double thr_mult8 = 1.25;       // int8 scan: threshold = P - thr_mult8 * bound (rq_tail_body.h)
     double eps = -1.0;
     std::map<hipStream_t, StreamCtx> ctx;

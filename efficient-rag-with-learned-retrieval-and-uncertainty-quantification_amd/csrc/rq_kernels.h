@@ -21,6 +21,9 @@ struct RqScanArgs {
     int i8;
     const float* qscale;
     const void* qlo;
+    // fp16 128-query passes of rq_scan_wide.hip only: queries 64..127 of the block come from here instead of qh + 64 rows
+    // (the two 64-slot query buffers of a scanned-ahead pair, rq_api.hip "scan_ahead"); null = qh holds the whole block
+    const _Float16* qh_hi;
 };
 #define RQ_WGMAX_STRIDE 1024   // scan grids never exceed this many workgroups
 
@@ -143,6 +146,10 @@ struct RqTailArgs {
 hipError_t rq_scan_tail_launch(const RqScanArgs& sa, const RqTailArgs& ta, int tail_B, const RqPrepArgs& pa, bool nt, int scan_grid, int epi, hipStream_t stream,
                                hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 hipError_t rq_tail_launch(const RqTailArgs& a, int B, hipStream_t stream);
+// Tails of the two batches of a scanned-ahead pair (one 128-query pass, rq_api.hip "scan_ahead") in ONE launch, plus pa.nslots
+// workgroups that prepare the queries of the batch announced after them: grid = chunks x (B0 + B1) tail workgroups, then pa.
+// t0 / t1 must not share cand / rowcount / done / ovf.
+hipError_t rq_pair_tail_launch(const RqTailArgs& t0, int B0, const RqTailArgs& t1, int B1, const RqPrepArgs& pa, hipStream_t stream);
 // chunk size rule shared by both launchers: 512-bin chunks while that keeps the grid around a thousand workgroups
 // (enough to spread the hits, few enough to be one dispatch round), else 2048-bin chunks
 static inline bool rq_tail_small_chunks(int64_t nbins, int B) { return ((nbins + 511) / 512) * B <= 1536; }

@@ -133,7 +133,9 @@ __device__ __forceinline__ void rq_scanw_body(const RqScanArgs& a, const int b, 
     float qsc[QG];      // int8: s_q / |q| of this lane's query (rq_prep_body), applied once per quad
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
-        const rq_half8* qsrc = (const rq_half8*)((const char*)a.qh + (size_t)(16 * (QG * wave + g) + r16) * ROWB + 16 * kg);
+        const int qi = 16 * (QG * wave + g) + r16;
+        const char* qrow = (!I8 && a.qh_hi && qi >= 64) ? (const char*)a.qh_hi + (size_t)(qi - 64) * ROWB : (const char*)a.qh + (size_t)qi * ROWB;
+        const rq_half8* qsrc = (const rq_half8*)(qrow + 16 * kg);
 #pragma unroll
         for (int s = 0; s < KS; ++s) qf[g][s] = qsrc[4 * s];
 #pragma unroll

@@ -39,3 +39,36 @@ hipError_t rq_tail_launch(const RqTailArgs& a, int B, hipStream_t stream) {
     if (a.m < 1 || a.m > RQ_FAST_MAX_M || a.k < 1 || a.k > RQ_FAST_MAX_K) return hipErrorInvalidValue;
     return rq_tail_small_chunks(a.nbins, B) ? rq_tail_launch_nv<1>(a, B, stream) : rq_tail_launch_nv<4>(a, B, stream);
 }
+
+// Tails of a scanned-ahead pair (both batches' records come from one 128-query pass) + the preparation of the next batch.
+// Block ids: [0, chunks * B0) tail t0 | [.., + chunks * B1) tail t1 | pa.nslots workgroups of rq_prep_body.
+union RqPairLds {
+    RqTailLds tail;
+    double prep[16];
+};
+template <int NV>
+__global__ __launch_bounds__(256) void rq_pair_tail_kernel(RqTailArgs t0, int B0, RqTailArgs t1, int B1, RqPrepArgs pa, int chunks) {
+    __shared__ RqPairLds lds;
+    const int bid = (int)blockIdx.x;
+    const int n0 = chunks * B0, n1 = chunks * B1;
+    if (bid < n0) rq_tail_body<NV>(t0, bid % chunks, bid / chunks, chunks, lds.tail);
+    else if (bid < n0 + n1) rq_tail_body<NV>(t1, (bid - n0) % chunks, (bid - n0) / chunks, chunks, lds.tail);
+    else rq_prep_body(pa, bid - n0 - n1, lds.prep);
+}
+
+template <int NV>
+static hipError_t rq_pair_tail_launch_nv(const RqTailArgs& t0, int B0, const RqTailArgs& t1, int B1, const RqPrepArgs& pa, hipStream_t stream) {
+    const int64_t chunks = (t0.nbins + 512 * NV - 1) / (512 * NV);
+    const int64_t grid = chunks * (B0 + B1) + pa.nslots;
+    if (chunks < 1 || grid > INT32_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((rq_pair_tail_kernel<NV>), dim3((unsigned)grid), dim3(256), 0, stream, t0, B0, t1, B1, pa, (int)chunks);
+    return hipGetLastError();
+}
+
+hipError_t rq_pair_tail_launch(const RqTailArgs& t0, int B0, const RqTailArgs& t1, int B1, const RqPrepArgs& pa, hipStream_t stream) {
+    for (const RqTailArgs* t : {&t0, &t1})
+        if (t->m < 1 || t->m > RQ_FAST_MAX_M || t->k < 1 || t->k > RQ_FAST_MAX_K) return hipErrorInvalidValue;
+    if (B0 < 1 || B1 < 1 || t0.nbins != t1.nbins || pa.nslots < 0 || pa.nslots > 64) return hipErrorInvalidValue;
+    return rq_tail_small_chunks(t0.nbins, B0 + B1) ? rq_pair_tail_launch_nv<1>(t0, B0, t1, B1, pa, stream)
+                                                   : rq_pair_tail_launch_nv<4>(t0, B0, t1, B1, pa, stream);
+}

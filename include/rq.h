@@ -103,7 +103,11 @@ int rq_search_flush_device(rq_index* idx, void* stream);
  * own (measured: one 5 us kernel + a launch boundary per batch).  d_next_queries must hold its final contents when the
  * current call is made and stay unchanged until the call that searches it.  Advisory: a hint that cannot be used (more than
  * 64 queries, another pipeline mode, a different pointer / B at the next call, a flush in between) is dropped and the
- * next call prepares its queries itself; results never depend on it.  B = 0 or NULL withdraws a pending hint. */
+ * next call prepares its queries itself; results never depend on it.  B = 0 or NULL withdraws a pending hint.
+ * Option "scan_ahead" (default 1): on shards the Infinity Cache cannot hold (rows x 1536 B > 208 MiB), a call over the fp16
+ * rows that has an announced successor scans BOTH batches in one 128-query pass; the next call, when it brings exactly
+ * d_next_queries, B and the same metric (any k), enqueues no scan of its own and runs the two batches' tails.  Anything else
+ * (another call, a flush, rq_stream_release) completes the first batch as usual and discards the half scanned ahead. */
 int rq_search_hint_next_device(rq_index* idx, const float* d_next_queries, int B, void* stream);
 /* A TRAIN of searches enqueued by one call (serving loops, the multi-GPU bench: a 125 k-row shard answers a 64-query batch in
  * ~25 us, which a host loop that crosses the language boundary twice per batch cannot feed): batch i = B queries at
@@ -138,7 +142,8 @@ int rq_merge_keys_device(const uint64_t* d_keys_in, int n_per_query, int B, int 
  * "pipeline" (see rq_search_flush_device), "wide_batch" (calls of more than 64 queries: 0 = passes of 64 only, 1 = passes of
  * 256 / 128 / 64, 3 = 128 / 64, 2 = round 1's 8-wave 128-query pass), "wide128" / "wide256" (variant of csrc/rq_scan_wide.hip),
  * "epi" (selection form of the 64-query scan: 1 = row positions inside the scores, 0 = compare / select),
- * "use_hint" (0: rq_search_hint_next_device is ignored),
+ * "use_hint" (0: rq_search_hint_next_device is ignored), "scan_ahead" (1 = default: an announced batch is scanned together with
+ *   the call before it on shards beyond 208 MiB of fp16 rows, see rq_search_hint_next_device; 0 = never),
  * "scan8" (searches may scan an int8 image of the shard instead of its fp16 rows -- half the bytes per pass;
  *   candidates are still re-scored from the fp16 rows in fp64, so results do not change: 0 = never, 1 = for k <= 128 on shards of
  *   200 000 rows and more (default), 2 = always.  The image (+768 B per row) is built by the first search that wants it (no room for it: the fp16 rows stay the operand); a shard whose
@@ -163,7 +168,7 @@ int rq_merge_keys_device(const uint64_t* d_keys_in, int n_per_query, int B, int 
  * not built), "scan8_level" (ladder position: class k <= 32 + 10 * class of larger k; 0 one image, 1 two images, 2 fp16 scan),
  * "scan8_wide_one_image" (same encoding: 1 = calls of more than 64 queries of that class scan ONE int8 image per query -- also in a class whose 64-query calls
  *   run on two images, when the image-build measurement found one image eligible; given up for the wide calls alone after too many repairs),
- * "scan8_suspended" (bit 0 / 1: that class is back at the fp16 scan), "hints_used" (searches that found their queries prepared, see rq_search_hint_next_device), "max_row_norm", "max_sub_rel" / "max_sub_abs" (largest share of a stored row that sits in fp16-subnormal elements,
+ * "scan8_suspended" (bit 0 / 1: that class is back at the fp16 scan), "hints_used" (searches whose announced queries a launch before them prepared or scanned, see rq_search_hint_next_device), "max_row_norm", "max_sub_rel" / "max_sub_abs" (largest share of a stored row that sits in fp16-subnormal elements,
  * which the matrix cores flush), "eps_cosine" / "eps_ip" (the certificate's bound including that term). */
 int rq_set_option(rq_index* idx, const char* name, double value);
 double rq_get_option(const rq_index* idx, const char* name);
