@@ -73,6 +73,7 @@ _SIGNATURES = {
     "rq_merge_keys_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "rq_debug_pooled": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "rq_debug_bin_records": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "rq_debug_bin_err": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64]),
     "rq_debug_read_bandwidth": (C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rq_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
@@ -262,6 +263,13 @@ class NativeIndex:
         out = np.empty((int(max_bins),), dtype=np.float32)
         n = _check(self._lib.rq_debug_pooled(self._h, C.c_void_p(stream), int(query), _ptr(out), int(max_bins)), "rq_debug_pooled")
         return out[:n]
+
+    def debug_bin_records(self, q0: int, nq: int, stream: int = 0) -> np.ndarray:
+        """Raw bin records (x, y) of query slots q0 .. q0 + nq of the last search on `stream`: uint32 [nq][bins][2] (include/rq.h)."""
+        nbins = (len(self) + 63) // 64
+        out = np.empty((int(nq), nbins, 2), dtype=np.uint32)
+        n = _check(self._lib.rq_debug_bin_records(self._h, C.c_void_p(stream), int(q0), int(nq), _ptr(out), nbins), "rq_debug_bin_records")
+        return out.reshape(-1)[: int(nq) * n * 2].reshape(int(nq), n, 2)   # (rows per slot packed: n bins each)
 
     def debug_bin_err(self, max_bins: int) -> np.ndarray:
         out = np.empty((int(max_bins),), dtype=np.float32)

@@ -293,8 +293,9 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     const std::string s(name);
     if (s == "ring") { if (v < 2 || v > 6) return set_err(RQ_EINVAL, "ring must be 2..6"); idx->ring = (int)v; }
     else if (s == "wide_batch") { if (v < 0 || v > 3) return set_err(RQ_EINVAL, "wide_batch must be 0..3"); idx->wide_batch = (int)v; }
-    else if (s == "wide128") { if (v < 0 || v > 99) return set_err(RQ_EINVAL, "wide128: a 128-query variant of csrc/rq_scan_wide.hip"); idx->wide128 = (int)v; }
-    else if (s == "wide256") { if (v < 0 || v > 92) return set_err(RQ_EINVAL, "wide256: a 256-query variant of csrc/rq_scan_wide.hip"); idx->wide256 = (int)v; }
+    // (8 and 11, the fp16 forms with asm fragment reads and counted LDS waits, are withdrawn: csrc/rq_scan_wide.hip)
+    else if (s == "wide128") { if (v < 0 || v > 99 || v == 8) return set_err(RQ_EINVAL, "wide128: a 128-query variant of csrc/rq_scan_wide.hip (8 is withdrawn)"); idx->wide128 = (int)v; }
+    else if (s == "wide256") { if (v < 0 || v > 92 || v == 11) return set_err(RQ_EINVAL, "wide256: a 256-query variant of csrc/rq_scan_wide.hip (11 is withdrawn)"); idx->wide256 = (int)v; }
     else if (s == "kstage") { if (v != 1 && v != 2) return set_err(RQ_EINVAL, "kstage must be 1 or 2"); idx->kstage = (int)v; }
     else if (s == "prefetch") { if (v != 1 && v != 4 && v != 6 && v != 12) return set_err(RQ_EINVAL, "prefetch must be 1, 4, 6 or 12"); idx->prefetch = (int)v; }
     else if (s == "wg_per_cu") { if (v < 0 || v > 8) return set_err(RQ_EINVAL, "wg_per_cu must be 1..8 (0: back to the library's rule)"); idx->wg_auto = v == 0; idx->wg_per_cu = v == 0 ? 2 : (int)v; }
@@ -322,6 +323,7 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     else if (s == "use_hint") idx->use_hint = (int)v != 0;   // 0: rq_search_hint_next_device is ignored (A/B of the folded query preparation)
     else if (s == "scan_ahead") idx->scan_ahead = (int)v != 0;   // 0: a hinted batch is never scanned together with the call before it (A/B)
     else if (s == "poison_cand") idx->poison_cand = (int)v;   // test hook: candidate lists are filled with 0xff..ff keys before every tail
+    else if (s == "poison_bins") idx->poison_bins = (int)v;   // test hook: the query slots a call's passes cover are filled with 0xff bytes before its scan
     else return set_err(RQ_EINVAL, "unknown option '%s'", name);
     return RQ_OK;
 }
@@ -603,6 +605,19 @@ static int poison_cand(const rq_index* idx, const RqTailArgs& t, int B, hipStrea
     return RQ_OK;
 }
 
+// Where a call's bin records are (test hooks rq_debug_bin_records / rq_debug_pooled); bins == nullptr: it scanned nothing.
+static void set_records(StreamCtx& c, const uint2* bins, int64_t stride, int B, int slots) {
+    c.rec_bins = bins; c.rec_stride = stride; c.rec_B = B; c.rec_slots = slots;
+}
+
+// Test hook ("poison_bins"): before a call's scan, the records of every query slot its passes cover are filled with 0xff bytes.
+// A record no workgroup wrote then decodes to a NaN maximum, and a pass that writes slots beyond its valid queries shows.
+static int poison_bins(const rq_index* idx, uint2* bins, int64_t stride, int slots, hipStream_t s) {
+    if (!idx->poison_bins || slots <= 0) return RQ_OK;
+    HIPCHK(hipMemsetAsync(bins, 0xff, (size_t)slots * (size_t)stride * sizeof(uint2), s));
+    return RQ_OK;
+}
+
 // "scan_ahead": the half of a pair that was scanned ahead is not claimed (another call came, or a flush).  The first batch's
 // tail becomes an ordinary pending tail -- it rides with the next fused launch of the stream or runs at the flush -- and the
 // second half's records are never read.
@@ -697,6 +712,7 @@ static int pair_second(rq_index* idx, StreamCtx& cx, int B, int k, float* d_scor
     idx->hints_used++;
     idx->last_use8 = false; idx->last_wide1 = false;
     RqTailArgs t1 = cx.pair_next;
+    set_records(cx, t1.bins, t1.bins_stride, B, 64);   // this call's records: the upper half of the previous call's pass
     t1.k = k; t1.m = (int)std::min<int64_t>(k, idx->n);
     t1.out_scores = d_scores; t1.out_rows = d_rows; t1.out_keys = d_keys; t1.out_status = d_status;
     RqPrepArgs pa{};
@@ -713,7 +729,10 @@ static int pair_second(rq_index* idx, StreamCtx& cx, int B, int k, float* d_scor
 // may_defer: the caller accepts results that are complete only after rq_search_flush_device ("pipeline" option).
 static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, float* d_scores, int64_t* d_rows,
                         uint64_t* d_keys, int* d_status, hipStream_t s, bool may_defer, bool force_generic, bool allow8) {
-    if (idx->n == 0) return fill_empty(B, k, d_scores, d_rows, d_keys, d_status, s);
+    if (idx->n == 0) {
+        if (auto it = idx->ctx.find(s); it != idx->ctx.end()) set_records(it->second, nullptr, 0, 0, 0);
+        return fill_empty(B, k, d_scores, d_rows, d_keys, d_status, s);
+    }
     const int binrows = RQ_BIN_ROWS;
     const int nquads = (int)((idx->n + 63) / 64);
     const int64_t nbins = nquads;   // bin = quad
@@ -900,7 +919,11 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
     int nwg_split = bpad;                                          // first query of the first narrow pass
     for (int blk = npass - 1, q0 = bpad; blk >= 0 && !pass_wide(pass_q[blk]); --blk) nwg_split = (q0 -= pass_q[blk]);
     if (pair) nwg_split = 64;                                      // both batches of a pair: the wide grid
+    if (exact) set_records(cx, nullptr, 0, 0, 0);
     if (!exact) {
+        const int slots = pair ? 128 : bpad;                       // (a pair: both halves; the upper one is the next call's, pair_second)
+        set_records(cx, w.bins, w.bins_stride, pair ? 64 + cx.pair_qB : B, slots);
+        if (int r = poison_bins(idx, w.bins, w.bins_stride, slots, s)) return r;
         // non-temporal loads only for shards that cannot stay in the 256 MiB Infinity Cache between two scans
         // (measured: 192 MB shard 36 us with default policy vs 39 us nt; 1.5 GB shard 250 us nt vs 285 us default)
         const bool nt = idx->nt < 0 ? (idx->n * (int64_t)(use8 ? RQ_DPAD : RQ_DPAD * 2) > ((int64_t)208 << 20)) : idx->nt != 0;
@@ -1352,15 +1375,31 @@ extern "C" int64_t rq_debug_pooled(rq_index* idx, void* stream, int query, float
     if (!idx || !out || query < 0 || !idx->shards.empty()) return set_err(RQ_EINVAL, "bad arguments");
     RQ_ON_DEVICE(idx);
     auto it = idx->ctx.find((hipStream_t)stream);
-    if (it == idx->ctx.end() || !it->second.w[0].bins || query >= it->second.w[0].bcap) return set_err(RQ_EINVAL, "no search has run on this stream");
-    const Workspace& w = it->second.w[0];
-    const int64_t nbins = (idx->n + 63) / 64;
-    const int64_t n = std::min(nbins, max_bins);
+    if (it == idx->ctx.end() || !it->second.rec_bins) return set_err(RQ_EINVAL, "the last search on this stream ran no approximate scan");
+    const StreamCtx& c = it->second;
+    if (query >= c.rec_slots) return set_err(RQ_EINVAL, "query %d beyond the %d slots the last search's passes covered", query, c.rec_slots);
+    const int64_t n = std::min({(idx->n + 63) / 64, max_bins, c.rec_stride});   // (rows appended since: their bins have no record)
     HIPCHK(hipDeviceSynchronize());
     // field x of every 8-byte record: the bin's largest approximate score (26 bits, rounded up) | its row
     std::vector<uint32_t> raw((size_t)n);
-    HIPCHK(hipMemcpy2D(raw.data(), sizeof(uint32_t), w.bins + (size_t)query * w.bins_stride, sizeof(uint2), sizeof(uint32_t), (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(raw.data(), sizeof(uint32_t), c.rec_bins + (size_t)query * c.rec_stride, sizeof(uint2), sizeof(uint32_t), (size_t)n, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < n; ++i) out[i] = rq_rec_m1(raw[(size_t)i]);
+    return n;
+}
+
+// ---- test hook: the raw bin records (rq_device.h) of query slots q0 .. q0 + nq of the last search on `stream` ----------
+extern "C" int64_t rq_debug_bin_records(rq_index* idx, void* stream, int q0, int nq, uint32_t* out, int64_t max_bins) {
+    if (!idx || !out || q0 < 0 || nq < 1 || max_bins < 0 || !idx->shards.empty()) return set_err(RQ_EINVAL, "bad arguments");
+    RQ_ON_DEVICE(idx);
+    auto it = idx->ctx.find((hipStream_t)stream);
+    if (it == idx->ctx.end() || !it->second.rec_bins) return set_err(RQ_EINVAL, "the last search on this stream ran no approximate scan");
+    const StreamCtx& c = it->second;
+    if ((int64_t)q0 + nq > c.rec_slots) return set_err(RQ_EINVAL, "slots %d..%d beyond the %d the last search's passes covered", q0, q0 + nq - 1, c.rec_slots);
+    const int64_t n = std::min({(idx->n + 63) / 64, max_bins, c.rec_stride});
+    HIPCHK(hipDeviceSynchronize());
+    if (n > 0)
+        HIPCHK(hipMemcpy2D(out, (size_t)n * sizeof(uint2), c.rec_bins + (size_t)q0 * c.rec_stride, (size_t)c.rec_stride * sizeof(uint2), (size_t)n * sizeof(uint2),
+                           (size_t)nq, hipMemcpyDeviceToHost));
     return n;
 }
 

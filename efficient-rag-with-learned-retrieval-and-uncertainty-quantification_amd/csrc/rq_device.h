@@ -92,6 +92,10 @@ __device__ __forceinline__ float rq_pos_score(float acc_times_scale, uint32_t po
 // scale, NaN only from the pad rows' NaN scale): a NaN needs no special care -- v_max_f32 returns the other operand and v_med3_f32 with a
 // NaN operand returns the MINIMUM of the other two, so rq_insert3 leaves a sorted triple m1 >= m2 >= m3 exactly as it was (the position
 // bits keep a quiet NaN a quiet NaN).  One VALU less per score where instruction issue is the bound (rq_scan_wide.hip I8).
+// Triples filled this way START at RQ_TRIPLE_EMPTY8 (-FLT_MAX), not -inf: a lane whose rows of the quad are all pad rows keeps its start
+// values, and the lane's row-group bits OR-ed into -inf (0xff800000) would make a SIGNALLING NaN, which v_max_f32 / v_med3_f32 return
+// quieted instead of dropping it -- the bin's record then read m1 = NaN and the tail never re-scored the ragged last bin.
+#define RQ_TRIPLE_EMPTY8 (-3.4028234664e38f)
 __device__ __forceinline__ float rq_pos_score_finite(float acc_times_scale, uint32_t pos) {
     return __uint_as_float((__float_as_uint(acc_times_scale) & 0xffffffc0u) | pos);
 }

@@ -101,6 +101,12 @@ struct StreamCtx {
     int pair_B = 0;
     const float* pair_q = nullptr;
     int pair_qB = 0, pair_metric = -1;
+    // where the stream's last call left its bin records (test hooks rq_debug_bin_records / rq_debug_pooled): query slot j of
+    // that call is rec_bins + j * rec_stride; its passes covered rec_slots slots (rec_B of them valid, the rest pad).
+    // rec_bins == nullptr: the last call ran no approximate scan (exact route, empty shard).
+    const uint2* rec_bins = nullptr;
+    int64_t rec_stride = 0;
+    int rec_B = 0, rec_slots = 0;
 };
 
 // Default scan variant: half-row stages (kstage 2), ring of 3, one LDS fragment ahead (prefetch 1, <= 168 VGPRs),
@@ -145,7 +151,7 @@ struct rq_index {
     int64_t hints_used = 0;        // rq_search_hint_next_device: searches whose queries a launch before them prepared or scanned ahead
     uint64_t scan_seq = 0;         // scan launches seen while profile = 1 (every profile_stride-th one is timed)
     // options
-    int ring = 3, prefetch = 1, kstage = 2, wide_batch = 1, wg_per_cu = 2, nt = -1, slack_bins = -1, profile = 0, profile_stride = 1, scan_nostore = 0, fast_tail = 1, pipeline = 0, tail_stop = 0, poison_cand = 0, wide128 = 0, wide256 = 2, epi = 1, use_hint = 1, scan_ahead = 1, profile_legacy = 0, scan8 = 1, tail_local = 1, scan8_split = -1, wide8 = 1, wide256_8 = 31, bin_bound = 1, exact_mfma = 1, fused_nv = 0;
+    int ring = 3, prefetch = 1, kstage = 2, wide_batch = 1, wg_per_cu = 2, nt = -1, slack_bins = -1, profile = 0, profile_stride = 1, scan_nostore = 0, fast_tail = 1, pipeline = 0, tail_stop = 0, poison_cand = 0, poison_bins = 0, wide128 = 0, wide256 = 2, epi = 1, use_hint = 1, scan_ahead = 1, profile_legacy = 0, scan8 = 1, tail_local = 1, scan8_split = -1, wide8 = 1, wide256_8 = 31, bin_bound = 1, exact_mfma = 1, fused_nv = 0;
     double thr_mult8 = 1.25;       // int8 scan: threshold = P - thr_mult8 * bound (rq_tail_body.h)
     double eps = -1.0;
     std::map<hipStream_t, StreamCtx> ctx;

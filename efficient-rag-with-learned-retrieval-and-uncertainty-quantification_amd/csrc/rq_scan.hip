@@ -182,8 +182,9 @@ __device__ __forceinline__ void rq_scan_body(const RqScanArgs& a, const int b, c
     };
     for (int lq = 0; lq < nloc; ++lq) {
         const int quad = q_lo + lq;
-        float m1 = NEG_INF, m2 = NEG_INF, m3 = NEG_INF;   // the three largest approximate scores of the lane's 16 rows
-        float n1 = NEG_INF, n2 = NEG_INF, n3 = NEG_INF;   // I8 = 3: the same for the second query group
+        constexpr float EMPTY = I8 ? RQ_TRIPLE_EMPTY8 : -__builtin_huge_valf();   // (int8: finite, see rq_device.h)
+        float m1 = EMPTY, m2 = EMPTY, m3 = EMPTY;         // the three largest approximate scores of the lane's 16 rows
+        float n1 = EMPTY, n2 = EMPTY, n3 = EMPTY;         // I8 = 3: the same for the second query group
         uint32_t ap = 0;                                  // rows (0..63) of the largest [7:0] and second largest [15:8]
         const char* nrow = norm_lds + ((lq & 1) << 8) + kg * 16;
 

@@ -123,6 +123,7 @@ __device__ __forceinline__ void rq_scanw_body(const RqScanArgs& a, const int b, 
     if (nst > 1) issue(1);
 
     const float NEG_INF = -__builtin_huge_valf();
+    constexpr float EMPTY = I8 ? RQ_TRIPLE_EMPTY8 : -__builtin_huge_valf();   // start of a selection triple (int8: finite, see rq_device.h)
     float wmax[QG];
 #pragma unroll
     for (int g = 0; g < QG; ++g) wmax[g] = NEG_INF;
@@ -143,11 +144,7 @@ __device__ __forceinline__ void rq_scanw_body(const RqScanArgs& a, const int b, 
         qsc[g] = I8 ? a.qscale[16 * (QG * wave + g) + r16] : 1.f;
     }
 
-    // PRIO == 3: the fragment reads are asm (ds_read_b128 with immediate offsets from 8 per-lane base addresses) and every
-    // MFMA group waits with a COUNTED s_waitcnt lgkmcnt(D): exactly D younger fragment reads may still be in flight.  The
-    // compiler's own schedule drains the whole LDS queue (lgkmcnt(0)) every few fragments, which exposes the latency of the
-    // read it has just issued.  LDS operations return in order, so other LDS instructions (the compiler's: row scales,
-    // record staging, shuffles) between the asm reads can only make a counted wait stricter, never too lax.
+    // per-lane LDS base addresses of the fragment reads (the int8 form's; see set_bases)
     unsigned abase[2][4];   // [ring half: slots 0-1 / 2-3][s & 3]
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -167,13 +164,7 @@ __device__ __forceinline__ void rq_scanw_body(const RqScanArgs& a, const int b, 
         if (I8) {
             rq_half8 v;
             const unsigned base = next_quad ? bn[s & 3] : bc[s & 3];
-            if (PRIO == 3) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(base), "n"((t >> 1) * STAGE_BYTES + (t & 1) * TILE_BYTES + ((s & ~3) << 6)));
-            else v = *(const rq_half8*)((const char*)(__attribute__((address_space(3))) const char*)(size_t)base + (t >> 1) * STAGE_BYTES + (t & 1) * TILE_BYTES + ((s & ~3) << 6));
-            return v;
-        }
-        if (PRIO == 3) {
-            rq_half8 v;
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(abase[t >> 1][s & 3]), "n"((t & 1) * STAGE_BYTES + ((s & ~3) << 6)));
+            v = *(const rq_half8*)((const char*)(__attribute__((address_space(3))) const char*)(size_t)base + (t >> 1) * STAGE_BYTES + (t & 1) * TILE_BYTES + ((s & ~3) << 6));
             return v;
         }
         return *(const rq_half8*)(rq_smem_w + t * STAGE_BYTES + (rbase0 ^ (unsigned)((s & 3) << 6)) + ((s & ~3) << 6));
@@ -195,11 +186,9 @@ __device__ __forceinline__ void rq_scanw_body(const RqScanArgs& a, const int b, 
     if (PRIO == 1 && QW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
     rq_half8 av[D];   // fragment ring: fragment f of the quad lives in av[f % D]
     if (I8) set_bases(0);
-    // The counted lgkmcnt waits below are sound only while LDS operations are the ONLY users of that counter: LDS returns in
-    // order, scalar (kernel-argument) loads do not, and one s_load still in flight when the first fragment reads are issued can
-    // satisfy "at most D outstanding" in place of the oldest ds_read (round 3: the compiler had sunk the load of a.nq_valid to just
-    // before the loop of the int8 form; queries of some waves then multiplied a stale register in their first tile).  Every
-    // argument the loop and the epilogue use is therefore pinned in registers here, and the queue is drained once.
+    // Every argument the loop and the epilogue use is pinned in registers here, and the LDS / scalar-load queue drained once
+    // (introduced for the counted lgkmcnt waits of the withdrawn asm forms, variants 8 / 11: an s_load still in flight could
+    // satisfy such a wait in place of the oldest ds_read; kept, the code of the remaining forms is unchanged by it).
     int nq_valid = a.nq_valid, wgmax_stride = a.wgmax_stride;
     int64_t bins_stride = a.bins_stride;
     uint2* bins_p = a.bins;
@@ -218,7 +207,7 @@ __device__ __forceinline__ void rq_scanw_body(const RqScanArgs& a, const int b, 
         float m1[QG], m2[QG], m3[QG];   // the three largest approximate scores of the lane's 16 rows, per query group
         uint32_t ap[QG];                // rows (0..63) of the largest [7:0] and second largest [15:8]
 #pragma unroll
-        for (int g = 0; g < QG; ++g) { m1[g] = NEG_INF; m2[g] = NEG_INF; m3[g] = NEG_INF; ap[g] = 0; }
+        for (int g = 0; g < QG; ++g) { m1[g] = EMPTY; m2[g] = EMPTY; m3[g] = EMPTY; ap[g] = 0; }
         const char* nrow = norm_lds + ((lq & (NPAR - 1)) << 8) + kg * 16;
         // accumulators alternate between two register sets by tile parity: with PRIO == 2 the waves 4..7 of an 8-wave
         // workgroup run the selection of tile t after the first 12 MFMAs of tile t + 1 (tiles 0..2; tile 3's at the end of the
@@ -256,7 +245,6 @@ __device__ __forceinline__ void rq_scanw_body(const RqScanArgs& a, const int b, 
                 }
             }
             rq_half8 curw = cur;
-            if (PRIO == 3) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(curw) : "n"(D));   // fragment f has landed; f+1 .. f+D may be in flight
             rq_float4 (&acc)[QG] = acc2[t & 1];
             rq_int4 (&iacc)[QG] = iacc2[t & 1];
             if (s == 0) {
@@ -465,7 +453,6 @@ __device__ __forceinline__ void rq_scanw32_body(const RqScanArgs& a, const int b
         return *(const rq_int4*)((const char*)(__attribute__((address_space(3))) const char*)(size_t)(lbase[s & 7] + par_off) + t * STAGE_BYTES + ((s & ~7) << 5));
     };
     float wmax = -__builtin_huge_valf();
-    const float NEG_INF = -__builtin_huge_valf();
     int nq_valid = a.nq_valid, wgmax_stride = a.wgmax_stride;
     int64_t bins_stride = a.bins_stride;
     uint2* bins_p = a.bins;
@@ -488,7 +475,7 @@ __device__ __forceinline__ void rq_scanw32_body(const RqScanArgs& a, const int b
     for (int lq = 0; lq < nloc; ++lq) {
         const bool more = lq + 1 < nloc;
         const unsigned pc = (unsigned)((lq & 1) * 2 * STAGE_BYTES), pn = (unsigned)(((lq + 1) & 1) * 2 * STAGE_BYTES);
-        float m1 = NEG_INF, m2 = NEG_INF, m3 = NEG_INF;
+        float m1 = RQ_TRIPLE_EMPTY8, m2 = RQ_TRIPLE_EMPTY8, m3 = RQ_TRIPLE_EMPTY8;   // (finite: see rq_device.h)
         const char* nrow = norm_lds + ((lq & (NPAR - 1)) << 8) + h * 16;
         rq_int16 acc2[2];
 #pragma clang loop unroll(full)
@@ -577,10 +564,10 @@ static hipError_t rq_scanw_launch_t(const RqScanArgs& a, int grid, hipStream_t s
 // Variants (option "wide128" / "wide256"; queries per pass = 16 * waves * groups):
 //   0  128 queries: 8 waves x 1 group, reads 12 fragments ahead, compiler-scheduled LDS waits          <- default for 128
 //   1  128 queries: as 0, reads 4 ahead
-//   8  128 queries: as 0 with asm fragment reads + counted lgkmcnt waits (within 1 % of 0)
-//  11  256 queries: 8 waves x 2 groups, reads 2 ahead, asm fragment reads + counted lgkmcnt waits: 256 VGPRs, nothing
-//      spilled (385-398 us per pass); A/B only since round 3 (see the int8 note below)
-//   2  256 queries: as 11 with compiler-scheduled reads (7 values spilled outside the streaming loop; 400-415 us)   <- default for 256
+//   2  256 queries: 8 waves x 2 groups, reads 2 ahead, compiler-scheduled LDS waits (7 values spilled outside the streaming
+//      loop; 400-415 us)   <- default for 256
+//   (8 and 11 -- 0 and 2 with asm fragment reads + counted lgkmcnt waits; 8 within 1 % of 0, 11 385-398 us per pass -- are
+//    withdrawn: the int8 twin of that construct scored rows from stale registers (note below); "wide128" = 8 / "wide256" = 11 are rejected)
 //   4  128 queries: as 1 with rq_scan.hip's compare/select epilogue (A/B of the selection forms)
 //   5  128 queries: 4 waves x 2 groups, one wave per SIMD (A/B: a lone wave cannot overlap its own VALU with its MFMAs)
 //   6  128 queries: as 0 with the selection of waves 4..7 staggered by half a tile;  7: as 0 with s_setprio 1 for waves 4..7
@@ -619,12 +606,12 @@ hipError_t rq_scan_wide_launch(const RqScanArgs& a, int variant, int queries, bo
     RQW_CASE(0, 12, 2, 8, 1, 1) RQW_CASE(1, 4, 2, 8, 1, 1) RQW_CASE(2, 2, 2, 8, 2, 1)
     RQW_CASE(4, 4, 2, 8, 1, 0) RQW_CASE(5, 4, 1, 4, 2, 1)
     RQW_CASE(6, 12, 2, 8, 1, 1, 0, 2) RQW_CASE(7, 12, 2, 8, 1, 1, 0, 1)
-    RQW_CASE(8, 12, 2, 8, 1, 1, 0, 3) RQW_CASE(11, 2, 2, 8, 2, 1, 0, 3)
     // int8 image (a.i8 = 4): 22  256 queries, 8 waves x 2 groups, reads 12 ahead, compiler-scheduled LDS waits   <- default ("wide256_8")
-    //     25  as 22, reads 6 ahead.  (Round 3 also built this form with asm fragment reads + counted lgkmcnt waits, as variants 8 / 11 do
+    //     25  as 22, reads 6 ahead.  (Round 3 also built this form with asm fragment reads + counted lgkmcnt waits, as variants 8 / 11 did
     //     for fp16: same speed -- 227 us per pass at 1M rows -- but NOT exact: one row in ~10^5 bins was scored from a stale register,
     //     differently from run to run.  An asm ds_read is invisible to the compiler's own hazard tracking: it may copy or re-use the
-    //     destination register before the data has landed.  Removed; and the fp16 256-query default went back from 11 to 2 for the same reason.)
+    //     destination register before the data has landed.  Removed; the fp16 256-query default went back from 11 to 2 for the same reason,
+    //     and the fp16 asm forms 8 / 11 are withdrawn as well.)
     RQW_CASE(22, 12, 2, 8, 2, 1, 0, 0, 1) RQW_CASE(25, 6, 2, 8, 2, 1, 0, 0, 1)
     // (a 128-query int8 form here -- 8 waves x 1 group, one workgroup per CU -- measured 154-160 us per pass against 150-157 of rq_scan.hip's
     //  I8 = 3 form, 4 waves x 2 groups at two per CU: not kept)

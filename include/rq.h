@@ -161,7 +161,8 @@ int rq_merge_keys_device(const uint64_t* d_keys_in, int n_per_query, int B, int 
  *   csrc/rq_scan_wide.hip; 0 = passes of 128 as in round 2), "bin_bound" (A/B hook, default 1: the tail tests every bin with its own rows'
  *   worst quantisation error instead of the shard's), "stripe_rows" (multi-device index, before the first append: rows per stripe),
  * "tail_local" (A/B hook, default 1: a tail workgroup with more than k re-scored rows publishes only its own k best keys),
- * "poison_cand" (test hook: candidate lists are filled with 0xff..ff keys before every tail).
+ * "poison_cand" (test hook: candidate lists are filled with 0xff..ff keys before every tail),
+ * "poison_bins" (test hook: before a search's scan, the bin records of every query slot its passes cover are filled with 0xff bytes).
  * "scan8" = 1 measures where the ladder STARTS when the image is built (64 stored rows searched as queries through every rung, the
  *   fastest rung that certifies wins; "scan8_calibrated_rows", "scan8_calib_ms_<class><rung>", "scan8_calib_unc_<class><rung>" report it).
  * Read-only: "repaired_queries" (queries that came back uncertified and were repaired, all rungs of the ladder), "scan8_used" (searches that scanned the int8 image), "scan8_row_err" (worst row's relative int8 error, -1 = image
@@ -192,6 +193,11 @@ rq_index* rq_load(const char* path, int n_devices, const int* device_ids);
 /* Test hook: copy the scan's approximate per-bin maxima of query `query` of the LAST search enqueued on `stream`
  * (bin b = rows 64 b .. 64 b + 63) to the host.  Returns the number of bins copied. */
 int64_t rq_debug_pooled(rq_index* idx, void* stream, int query, float* out, int64_t max_bins);
+/* Test hook: the raw 8-byte bin records (x, y: csrc/rq_device.h) of query slots q0 .. q0 + nq - 1 of the LAST search enqueued on
+ * `stream`, as out[nq][bins][2] uint32 words; synchronises the device.  A search's slots are its queries followed by the pad slots of its
+ * passes (a scanned-ahead pair: the call's own 64-slot half).  RQ_EINVAL on a multi-device index, when that search ran no approximate
+ * scan (exact route, empty shard) or when q0 + nq exceeds the slots its passes covered.  Returns the number of bins per slot copied. */
+int64_t rq_debug_bin_records(rq_index* idx, void* stream, int q0, int nq, uint32_t* out, int64_t max_bins);
 /* Test hook: the int8 image's worst relative row error of every bin (fp32, rounded up), i.e. what the tail may lift its candidate
  * threshold by per bin (option "bin_bound").  Fails unless the image is built and up to date.  Returns the number of bins copied. */
 int64_t rq_debug_bin_err(rq_index* idx, float* out, int64_t max_bins);

@@ -216,10 +216,11 @@ def test_every_kernel_variant_is_exact(corpus100k, opts):
 
 
 @pytest.mark.parametrize("opts", [dict(wide_batch=1), dict(wide_batch=3), dict(wide_batch=2), dict(wide_batch=0),
-                                  # every variant built in csrc/rq_scan_wide.hip: 128-query passes 0 / 1 / 4 / 5 / 6 / 7 / 8, 256-query passes 11 / 2
+                                  # every variant built in csrc/rq_scan_wide.hip: 128-query passes 0 / 1 / 4 / 5 / 6 / 7, 256-query pass 2;
+                                  # 0 and 2 named explicitly where their asm forms 8 / 11 stood (withdrawn: test_withdrawn_wide_variants_are_rejected)
                                   dict(wide_batch=3, wide128=1), dict(wide_batch=3, wide128=4), dict(wide_batch=3, wide128=5),
-                                  dict(wide_batch=3, wide128=6), dict(wide_batch=3, wide128=7), dict(wide_batch=3, wide128=8),
-                                  dict(wide_batch=1, wide256=11),     # (2 is the default since round 3)
+                                  dict(wide_batch=3, wide128=6), dict(wide_batch=3, wide128=7), dict(wide_batch=3, wide128=0),
+                                  dict(wide_batch=1, wide256=2),
                                   dict(wide_batch=1, nt=1), dict(wide_batch=1, cu_count=5)])
 def test_every_wide_pass_variant_is_exact(corpus100k, opts):
     """Calls with more than 64 queries are cut into passes of 256 / 128 / 64 queries (csrc/rq_api.hip run_pipeline).
@@ -238,6 +239,21 @@ def test_every_wide_pass_variant_is_exact(corpus100k, opts):
         _check(idx, x, q, k)
     _check(idx, x, 2.5 * orc.synthetic_queries(130, 768, seed=3), 10, nat.METRIC_IP)
     assert idx.timing()["exact_scans"] == 0
+    idx.close()
+
+
+def test_withdrawn_wide_variants_are_rejected(corpus100k):
+    """wide128 = 8 and wide256 = 11 (asm fragment reads with counted lgkmcnt waits) are withdrawn: rq_set_option
+    rejects them with RQ_EINVAL; the variants they were A/B forms of (0 / 2) stay selectable and exact."""
+    _, x16 = corpus100k
+    idx = nat.NativeIndex(768, 0)
+    idx.add_f16(x16[:30_011])
+    for name, bad, good in (("wide128", 8, 0), ("wide256", 11, 2)):
+        idx.set_option(name, good)
+        with pytest.raises(nat.RqError, match="withdrawn"):
+            idx.set_option(name, bad)
+    idx.set_option("wide_batch", 1)
+    _check(idx, x16[:30_011], orc.synthetic_queries(333, 768, seed=5), 10)      # 256 + 128: the passes that remain
     idx.close()
 
 
