@@ -174,6 +174,11 @@ class NativeIndex:
     def __len__(self) -> int:
         return int(self._lib.rq_index_size(self._h))
 
+    @property
+    def row_pad(self) -> int:
+        """Elements per stored row: 384 (dim <= 384) or 768 (include/rq.h option "row_pad"; settable with set_option while empty)."""
+        return int(self.get_option("row_pad"))
+
     # -- build ------------------------------------------------------------------------------
     def reserve(self, n_rows: int) -> None:
         _check(self._lib.rq_index_reserve(self._h, int(n_rows)), "rq_index_reserve")

@@ -1,7 +1,7 @@
 // rq_api.hip -- the C ABI of include/rq.h: shard storage in HBM, search orchestration, persistence.
 //
 // One rq_index = one row shard resident on one MI355X.  Layout in HBM:
-//   x          [cap][768] fp16, cap % 64 == 0, rows >= n are zero      (the only large array)
+//   x          [cap][dpad] fp16 (dpad = 768, or 384 for dim <= 384: option "row_pad"), cap % 64 == 0, rows >= n are zero   (the only large array)
 //   rownorm64  [cap]      fp64 L2 norm of the stored row               (exact re-score)
 //   inv_norm   [cap]      fp32 2^-12 / norm, 0 for zero rows, NaN for pad rows (scan, cosine; the queries carry 2^12)
 //   ones       [cap]      fp32 2^-12 for rows < n, NaN beyond                  (scan, inner product; lazy)
@@ -62,7 +62,8 @@ static int grow(rq_index* idx, int64_t want_rows) {
     if (int r = flush_all(idx)) return r;
     HIPCHK(hipDeviceSynchronize());   // searches in flight on any stream still read the old buffers
     char* nx = nullptr; double* nn = nullptr; float* ni = nullptr;
-    hipError_t e = hipMalloc((void**)&nx, (size_t)cap * RQ_DPAD * 2);
+    const size_t rowb = idx->rowb();
+    hipError_t e = hipMalloc((void**)&nx, (size_t)cap * rowb);
     if (e != hipSuccess) return set_err(RQ_ENOMEM, "hipMalloc of %lld corpus rows failed: %s", (long long)cap, hipGetErrorString(e));
     if ((e = hipMalloc((void**)&nn, (size_t)cap * sizeof(double))) != hipSuccess || (e = hipMalloc((void**)&ni, (size_t)cap * sizeof(float))) != hipSuccess) {
         (void)hipFree(nx);
@@ -71,11 +72,11 @@ static int grow(rq_index* idx, int64_t want_rows) {
     }
     const int64_t keep = idx->n;
     if (keep > 0) {
-        HIPCHK(hipMemcpyAsync(nx, idx->x, (size_t)keep * RQ_DPAD * 2, hipMemcpyDeviceToDevice, idx->own_stream));
+        HIPCHK(hipMemcpyAsync(nx, idx->x, (size_t)keep * rowb, hipMemcpyDeviceToDevice, idx->own_stream));
         HIPCHK(hipMemcpyAsync(nn, idx->rownorm64, (size_t)keep * sizeof(double), hipMemcpyDeviceToDevice, idx->own_stream));
         HIPCHK(hipMemcpyAsync(ni, idx->inv_norm, (size_t)keep * sizeof(float), hipMemcpyDeviceToDevice, idx->own_stream));
     }
-    HIPCHK(hipMemsetAsync(nx + (size_t)keep * RQ_DPAD * 2, 0, (size_t)(cap - keep) * RQ_DPAD * 2, idx->own_stream));
+    HIPCHK(hipMemsetAsync(nx + (size_t)keep * rowb, 0, (size_t)(cap - keep) * rowb, idx->own_stream));
     HIPCHK(hipMemsetAsync(nn + keep, 0, (size_t)(cap - keep) * sizeof(double), idx->own_stream));
     // row scales of the pad rows are NaN (0xffffffff): their scan scores sort last without a per-score row test
     // (rq_scan_wide.hip); rq_scan.hip masks rows >= n on its own
@@ -99,6 +100,7 @@ extern "C" rq_index* rq_index_create(int dim, int n_devices, const int* device_i
     if (device_ids[0] < 0 || device_ids[0] >= ndev) { set_err(RQ_EINVAL, "device %d outside 0..%d", device_ids[0], ndev - 1); return nullptr; }
     rq_index* idx = new rq_index();
     idx->dim = dim;
+    idx->dpad = dim <= 384 ? 384 : RQ_DPAD;   // the rule of "row_pad"
     idx->device = device_ids[0];
     DeviceGuard dg_(idx->device);
     hipDeviceProp_t prop;
@@ -189,7 +191,7 @@ extern "C" int rq_index_reserve(rq_index* idx, int64_t n_rows) {
 static int finish_add(rq_index* idx, int64_t n_new) {
     hipStream_t s = idx->own_stream;
     const int64_t b = idx->n, e = idx->n + n_new;
-    HIPCHK(rq_rownorm_launch(idx->x, b, e, idx->rownorm64, (unsigned long long*)idx->d_maxnorm, s));
+    HIPCHK(rq_rownorm_launch(idx->x, idx->dpad, b, e, idx->rownorm64, (unsigned long long*)idx->d_maxnorm, s));
     HIPCHK(rq_rowscale_launch(idx->rownorm64, b, e, idx->inv_norm, s));
     double st[3] = {0.0, 0.0, 0.0};
     HIPCHK(hipMemcpyAsync(st, idx->d_maxnorm, sizeof(st), hipMemcpyDeviceToHost, s));
@@ -212,10 +214,10 @@ static int add_device_common(rq_index* idx, const void* d_rows, int64_t n_rows, 
     if (int r = flush_all(idx)) return r;
     HIPCHK(hipDeviceSynchronize());
     if (int r = grow(idx, idx->n + n_rows)) return r;
-    char* dst = idx->x + (size_t)idx->n * RQ_DPAD * 2;
-    if (is_f32) HIPCHK(rq_convert_f32_launch((const float*)d_rows, idx->dim, n_rows, normalize, dst, idx->own_stream));
-    else if (idx->dim == RQ_DPAD) HIPCHK(hipMemcpyAsync(dst, d_rows, (size_t)n_rows * RQ_DPAD * 2, hipMemcpyDeviceToDevice, idx->own_stream));
-    else HIPCHK(rq_pad_f16_launch(d_rows, idx->dim, n_rows, dst, idx->own_stream));
+    char* dst = idx->x + (size_t)idx->n * idx->rowb();
+    if (is_f32) HIPCHK(rq_convert_f32_launch((const float*)d_rows, idx->dim, n_rows, normalize, dst, idx->dpad, idx->own_stream));
+    else if (idx->dim == idx->dpad) HIPCHK(hipMemcpyAsync(dst, d_rows, (size_t)n_rows * idx->rowb(), hipMemcpyDeviceToDevice, idx->own_stream));
+    else HIPCHK(rq_pad_f16_launch(d_rows, idx->dim, n_rows, dst, idx->dpad, idx->own_stream));
     return finish_add(idx, n_rows);
 }
 extern "C" int rq_index_add_f16_device(rq_index* idx, const void* d_rows, int64_t n_rows) { return add_device_common(idx, d_rows, n_rows, false, 0); }
@@ -260,7 +262,7 @@ extern "C" int rq_index_get_rows_f16(const rq_index* idx, int64_t row_begin, int
     if (n_rows == 0) return RQ_OK;
     if (!idx->shards.empty()) return rq_multi_get_rows(idx, row_begin, n_rows, out);
     RQ_ON_DEVICE(idx);
-    HIPCHK(hipMemcpy2D(out, (size_t)idx->dim * 2, idx->x + (size_t)row_begin * RQ_DPAD * 2, (size_t)RQ_DPAD * 2, (size_t)idx->dim * 2,
+    HIPCHK(hipMemcpy2D(out, (size_t)idx->dim * 2, idx->x + (size_t)row_begin * idx->rowb(), idx->rowb(), (size_t)idx->dim * 2,
                        (size_t)n_rows, hipMemcpyDeviceToHost));
     return RQ_OK;
 }
@@ -286,12 +288,31 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
             idx->stripe = (int64_t)v;
             return RQ_OK;
         }
+        // (the children take the same row length, before the first append: a child that is still empty later must not be given another)
+        if (std::string(name) == "row_pad" && idx->n != 0) return set_err(RQ_EINVAL, "row_pad can only be set on an empty index");
         for (rq_index* c : idx->shards)
             if (int r = rq_set_option(c, name, v)) return r;
         return RQ_OK;
     }
     const std::string s(name);
-    if (s == "ring") { if (v < 2 || v > 6) return set_err(RQ_EINVAL, "ring must be 2..6"); idx->ring = (int)v; }
+    if (s == "row_pad") {   // stored row length: 384 (dim <= 384 only) or 768, while no row is stored
+        if (v != 384 && v != RQ_DPAD) return set_err(RQ_EINVAL, "row_pad must be 384 or %d", RQ_DPAD);
+        if (v == 384 && idx->dim > 384) return set_err(RQ_EINVAL, "row_pad 384 needs dim <= 384 (dim is %d)", idx->dim);
+        if (idx->n != 0) return set_err(RQ_EINVAL, "row_pad can only be set on an empty index");
+        if ((int)v != idx->dpad) {
+            RQ_ON_DEVICE(idx);
+            const int64_t reserved = idx->cap;   // a reservation is made again with the new row length
+            if (int r = flush_all(idx)) return r;
+            HIPCHK(hipDeviceSynchronize());
+            void* p[] = {idx->x, idx->rownorm64, idx->inv_norm, idx->ones};
+            for (void* q : p) if (q) (void)hipFree(q);
+            idx->x = nullptr; idx->rownorm64 = nullptr; idx->inv_norm = nullptr; idx->ones = nullptr; idx->ones_valid = 0; idx->cap = 0;
+            drop_x8(idx);
+            idx->dpad = (int)v;
+            if (reserved > 0) return grow(idx, reserved);
+        }
+    }
+    else if (s == "ring") { if (v < 2 || v > 6) return set_err(RQ_EINVAL, "ring must be 2..6"); idx->ring = (int)v; }
     else if (s == "wide_batch") { if (v < 0 || v > 3) return set_err(RQ_EINVAL, "wide_batch must be 0..3"); idx->wide_batch = (int)v; }
     // (8 and 11, the fp16 forms with asm fragment reads and counted LDS waits, are withdrawn: csrc/rq_scan_wide.hip)
     else if (s == "wide128") { if (v < 0 || v > 99 || v == 8) return set_err(RQ_EINVAL, "wide128: a 128-query variant of csrc/rq_scan_wide.hip (8 is withdrawn)"); idx->wide128 = (int)v; }
@@ -342,6 +363,7 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
         return v;
     }
     const std::string s(name);
+    if (s == "row_pad") return idx->dpad;
     if (s == "ring") return idx->ring;
     if (s == "prefetch") return idx->prefetch;
     if (s == "kstage") return idx->kstage;
@@ -480,7 +502,7 @@ static int scan8_calibrate(rq_index* idx, hipStream_t s) {
     std::vector<float> h32((size_t)S * idx->dim);
     for (int i = 0; i < S; ++i) {
         const int64_t row = (int64_t)((double)i + 0.5) * idx->n / S;
-        HIPCHK(hipMemcpy(h16.data() + (size_t)i * RQ_DPAD, idx->x + (size_t)std::min(row, idx->n - 1) * RQ_DPAD * 2, RQ_DPAD * 2, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h16.data() + (size_t)i * RQ_DPAD, idx->x + (size_t)std::min(row, idx->n - 1) * idx->rowb(), idx->rowb(), hipMemcpyDeviceToHost));
         for (int j = 0; j < idx->dim; ++j) {
             _Float16 v; __builtin_memcpy(&v, &h16[(size_t)i * RQ_DPAD + j], 2);
             h32[(size_t)i * idx->dim + j] = (float)v;
@@ -742,6 +764,7 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
     // but a 125k-row document-structured shard takes 64 us against 34 in the same loop (profiles/r02_shard_shapes.txt).  Its bound does not
     // involve fp16 subnormals (the image is relative to each row's largest element), so it is decided BEFORE `exact` below.
     bool use8 = false;
+    const bool narrow = idx->narrow();   // rows of 384 elements (rq_scan_narrow.hip): no int8 image, passes of 64 / 128 queries, no scanned-ahead pair
     const int kclass = k <= RQ_SCAN8_SMALL_K ? 0 : 1;
     // Calls of more than 64 queries: passes of 128 queries over the image (two 16-query groups per wave, rq_scan.hip I8 = 3) while
     // the class runs with one image per query and "wide8" is on; otherwise the fp16 passes of rq_scan_wide.hip.
@@ -752,7 +775,7 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
         return lvl == 0 || (lvl == 1 && idx->scan8_split < 0 && !idx->wide1_off[kclass] && (idx->scan8 == 2 || idx->wide1_ok[kclass] || idx->calib_rows == 0));
     };
     const bool wide_ok = B <= 64 || (idx->wide8 && idx->wide_batch != 0 && wide_level_ok());
-    if (allow8 && idx->scan8 && idx->scan8_level[kclass] < 2 && nb >= 0 && 2 * (int64_t)nb < nbins && wide_ok && !force_generic && idx->fast_tail &&
+    if (allow8 && !narrow && idx->scan8 && idx->scan8_level[kclass] < 2 && nb >= 0 && 2 * (int64_t)nb < nbins && wide_ok && !force_generic && idx->fast_tail &&
         k <= RQ_FAST_MAX_K && (idx->scan8 == 2 || (idx->n >= RQ_SCAN8_MIN_ROWS && k <= RQ_SCAN8_AUTO_MAX_K))) {
         if (int r = ensure_x8(idx, s)) return r;   // (may calibrate: the class's level is read again below)
         use8 = idx->x8 && idx->x8_valid == idx->n && idx->max_e8 <= RQ_SCAN8_MAX_ROW_ERR && idx->scan8_level[kclass] < 2 &&
@@ -781,7 +804,8 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
         const int big = wb == 1 ? 256 : (wb == 2 || wb == 3 ? 128 : 64);
         for (int left = B; left > 0;) {
             int qb = 64;
-            if (use8 && B > 64) {                               // int8 image: passes of 256 (rq_scan_wide.hip I8), 128 (rq_scan.hip I8 = 3) and 64 queries
+            if (narrow) qb = (wb != 0 && left > 64) ? 128 : 64;   // rows of 384 elements: 128 then 64 (rq_scan_narrow.hip)
+            else if (use8 && B > 64) {                               // int8 image: passes of 256 (rq_scan_wide.hip I8), 128 (rq_scan.hip I8 = 3) and 64 queries
                 if (idx->wide256_8 && big >= 256 && left > 128) qb = 256;
                 else if (left > 64 || !idx->wide256_8) qb = 128;
             }
@@ -814,8 +838,8 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
     // scans BOTH in one 128-query pass (rq_scan_wide.hip variant 0: 266-268 us at 1M rows against 237 us for 64 queries); the
     // next call, if it brings the announced batch, only runs the two tails (pair_second).  Only on shards the Infinity Cache
     // cannot hold (the rule of the non-temporal loads below): smaller shards are not bound by HBM bytes.
-    const bool pair = fused && !use8 && idx->scan_ahead && cx.hint_q && cx.hint_B <= 64 &&
-                      idx->n * (int64_t)(RQ_DPAD * 2) > ((int64_t)208 << 20);
+    const bool pair = fused && !use8 && !narrow && idx->scan_ahead && cx.hint_q && cx.hint_B <= 64 &&
+                      idx->n * (int64_t)idx->rowb() > ((int64_t)208 << 20);
     int par = 0, slot = -1;
     if (fused) {
         slot = (int)(cx.calls % 3);
@@ -902,7 +926,8 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
     // the 64-query passes and the int8 128-query pass run wg_per_cu 256-thread workgroups per CU.  A call's passes are cut widest first,
     // so its wide passes precede its narrow ones: the tail is told where the second grid starts (nwg_split).  Until round 3 the first
     // pass's grid served the whole call, and the remainder pass of e.g. 384 int8 queries ran at half its occupancy (232 us instead of 150).
-    auto pass_wide = [&](int qb) { return qb > 64 && (!use8 || qb == 256); };
+    // (rows of 384 elements: both forms are 256-thread workgroups)
+    auto pass_wide = [&](int qb) { return qb > 64 && !narrow && (!use8 || qb == 256); };
     int wg_cu = idx->wg_per_cu;
     // Small int8 shards searched from SEVERAL caller streams (the per-rank shape of a multi-GPU run: 125k rows, two streams): two fused
     // launches are resident at once, so ONE scan workgroup per CU and launch already keeps two per CU streaming, and each lives twice as
@@ -926,7 +951,12 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
         if (int r = poison_bins(idx, w.bins, w.bins_stride, slots, s)) return r;
         // non-temporal loads only for shards that cannot stay in the 256 MiB Infinity Cache between two scans
         // (measured: 192 MB shard 36 us with default policy vs 39 us nt; 1.5 GB shard 250 us nt vs 285 us default)
-        const bool nt = idx->nt < 0 ? (idx->n * (int64_t)(use8 ? RQ_DPAD : RQ_DPAD * 2) > ((int64_t)208 << 20)) : idx->nt != 0;
+        const int64_t scan_rowb = use8 ? RQ_DPAD : (int64_t)idx->rowb();   // bytes a scan reads per row
+        const bool nt = idx->nt < 0 ? (idx->n * scan_rowb > ((int64_t)208 << 20)) : idx->nt != 0;
+        // the fused launch of this layout
+        auto scan_tail = [&](const RqScanArgs& sa, const RqTailArgs& t, int tb, const RqPrepArgs& p, int grid, hipEvent_t e0, hipEvent_t e1) {
+            return narrow ? rq_scan_narrow_tail_launch(sa, t, tb, p, nt, grid, s, e0, e1) : rq_scan_tail_launch(sa, t, tb, p, nt, grid, idx->epi, s, e0, e1);
+        };
         for (int blk = 0, q0 = 0; blk < npass; q0 += pass_q[blk], ++blk) {
             const int qb = pass_q[blk];
             const int grid = q0 >= nwg_split ? grid_narrow : grid_wide;
@@ -964,16 +994,17 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
                 cx.fused_pending = false;
                 if (int r = poison_cand(idx, cx.fused_tail, cx.fused_B, s)) return r;
                 if (idx->tail_stop == 9) {   // development: fused kernel without its tail workgroups, tail launched after it
-                    HIPCHK(rq_scan_tail_launch(a, cx.fused_tail, 0, pa, nt, grid, idx->epi, s, e0, e1));
+                    HIPCHK(scan_tail(a, cx.fused_tail, 0, pa, grid, e0, e1));
                     RqTailArgs t9 = cx.fused_tail; t9.stop_after = 0;
                     HIPCHK(rq_tail_launch(t9, cx.fused_B, s));
                 } else
-                HIPCHK(rq_scan_tail_launch(a, cx.fused_tail, cx.fused_B, pa, nt, grid, idx->epi, s, e0, e1));
+                HIPCHK(scan_tail(a, cx.fused_tail, cx.fused_B, pa, grid, e0, e1));
             } else if (fused && pa.nslots) {   // first call of a loop: no tail to carry yet, but queries to prepare
                 RqTailArgs none{};
                 none.nbins = nbins; none.m = none.k = 1; none.thr_mult = 2.25f; none.thr_slack = 0.f;
-                HIPCHK(rq_scan_tail_launch(a, none, 0, pa, nt, grid, idx->epi, s, e0, e1));
-            } else if (fused) HIPCHK(rq_scan_launch(a, 3, 1, 2, 4, nt, grid, idx->epi, s, e0, e1));
+                HIPCHK(scan_tail(a, none, 0, pa, grid, e0, e1));
+            } else if (narrow) HIPCHK(rq_scan_narrow_launch(a, qb, nt, grid, s, e0, e1));   // 64 queries, or 128 (two query groups per wave)
+            else if (fused) HIPCHK(rq_scan_launch(a, 3, 1, 2, 4, nt, grid, idx->epi, s, e0, e1));
             else if (use8 && qb == 256) HIPCHK(rq_scan_wide_launch(a, idx->wide256_8, 256, nt, grid, s, e0, e1));   // 256 queries over the int8 image
             else if (use8) HIPCHK(rq_scan_launch(a, 3, 1, 2, 4, nt, grid, 1, s, e0, e1));   // 64 queries, or 128 (a.i8 = 3)
             else if (qb == 256) HIPCHK(rq_scan_wide_launch(a, idx->wide256, 256, nt, grid, s, e0, e1));
@@ -984,7 +1015,7 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
                 cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = (slot + 1) % 3;
                 cx.hint_q = nullptr;
             }
-            if (prof) { if (idx->profile_legacy) HIPCHK(hipEventRecord(idx->events[idx->ev_used].second, s)); idx->ev_used++; idx->ev_bytes += idx->n * (int64_t)(use8 ? RQ_DPAD : RQ_DPAD * 2); }
+            if (prof) { if (idx->profile_legacy) HIPCHK(hipEventRecord(idx->events[idx->ev_used].second, s)); idx->ev_used++; idx->ev_bytes += idx->n * scan_rowb; }
         }
         if (fast) {
             hipStream_t ts = s;
@@ -994,7 +1025,7 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
                 ts = cx.tail;
             }
             RqTailArgs ta;
-            ta.q = d_q; ta.dim = idx->dim; ta.x = idx->x; ta.rownorm64 = idx->rownorm64; ta.n_rows = idx->n;
+            ta.q = d_q; ta.dim = idx->dim; ta.x = idx->x; ta.dpad = idx->dpad; ta.rownorm64 = idx->rownorm64; ta.n_rows = idx->n;
             ta.bins = w.bins; ta.bins_stride = w.bins_stride; ta.nbins = nbins;
             ta.wgmax = w.wgmax; ta.wgmax_stride = RQ_WGMAX_STRIDE; ta.nwg = grid_wide; ta.nwg_split = nwg_split; ta.nwg2 = grid_narrow;
             ta.m = (int)std::min<int64_t>(k, idx->n); ta.metric = metric; ta.k = k;
@@ -1043,14 +1074,14 @@ static int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metri
             }
             if (int r = poison_cand(idx, ta, B, ts)) return r;
             HIPCHK(rq_tail_launch(ta, B, ts));
-            if (tprof) { HIPCHK(hipEventRecord(idx->events[idx->ev_used].second, ts)); idx->ev_used++; idx->ev_bytes += idx->n * (int64_t)(use8 ? RQ_DPAD : RQ_DPAD * 2); }
+            if (tprof) { HIPCHK(hipEventRecord(idx->events[idx->ev_used].second, ts)); idx->ev_used++; idx->ev_bytes += idx->n * (use8 ? (int64_t)RQ_DPAD : (int64_t)idx->rowb()); }
             if (piped) { HIPCHK(hipEventRecord(cx.ev_tail[par], cx.tail)); cx.tail_pending[par] = true; }
             return RQ_OK;
         }
         HIPCHK(rq_select_bins_launch(w.bins, w.bins_stride, nbins, B, m, w.binkeys, s));
     }
     RqRescoreArgs ra;
-    ra.x = idx->x; ra.q32 = w.q32; ra.qnorm64 = w.qn; ra.rownorm64 = idx->rownorm64;
+    ra.x = idx->x; ra.dpad = idx->dpad; ra.q32 = w.q32; ra.qnorm64 = w.qn; ra.rownorm64 = idx->rownorm64;
     ra.binkeys = exact ? nullptr : w.binkeys; ra.binkeys_stride = m; ra.nb = nb; ra.metric = metric;
     ra.n_rows = idx->n; ra.cand = w.cand;
     if (exact && idx->exact_mfma) HIPCHK(rq_exact_scan_launch(ra, B, idx->cu_count, s));   // the whole shard: fp64 contraction on the matrix cores
@@ -1344,7 +1375,7 @@ extern "C" double rq_debug_read_bandwidth(rq_index* idx, int iters, int nt, int 
     if (!dg_.ok) { set_err(RQ_EHIP, "cannot select device %d", idx->device); return -1.0; }
     if (idx->n == 0) { set_err(RQ_EINVAL, "empty index"); return -1.0; }
     if (flush_all(idx)) return -1.0;
-    const int64_t bytes = idx->n * (int64_t)(RQ_DPAD * 2);
+    const int64_t bytes = idx->n * (int64_t)idx->rowb();
     const bool use_nt = nt < 0 ? bytes > ((int64_t)208 << 20) : nt != 0;
     uint32_t* sink = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;

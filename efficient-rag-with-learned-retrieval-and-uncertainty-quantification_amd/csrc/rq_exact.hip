@@ -25,7 +25,11 @@ typedef double rq_double4 __attribute__((ext_vector_type(4)));
 
 // grid (G, ceil(B / 32)); 256 threads, one workgroup per CU (LDS).  a.binkeys must be null (exact mode: cand is [B][nb * 64] and
 // row r of query q lands at cand[q * nb * 64 + r]).
+// DP: stored row length (768 or 384 elements): the row stride and the k-steps multiplied (DP / 32 chunks of 8 per lane; the rest of
+// a 384-element row would be zeros, which change no sum).
+template <int DP>
 __global__ __launch_bounds__(256, 1) void rq_exact_scan_kernel(RqRescoreArgs a, int B) {
+    constexpr int NJ = DP / 32;
     __shared__ __attribute__((aligned(16))) float qs[RQ_EXACT_QB * RQ_EXACT_QPITCH];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -48,12 +52,12 @@ __global__ __launch_bounds__(256, 1) void rq_exact_scan_kernel(RqRescoreArgs a, 
     const char* xb = (const char*)a.x;
     uint64_t* out = a.cand + (int64_t)(live_q ? q : 0) * rows_alloc;
 
-    rq_half8 cur[24], nxt[24];
-    auto load_tile = [&](int64_t t, rq_half8 (&dst)[24]) {
+    rq_half8 cur[NJ], nxt[NJ];
+    auto load_tile = [&](int64_t t, rq_half8 (&dst)[NJ]) {
         // rows beyond the shard's end inside the last quad are zero padded storage (cap % 64 == 0): readable, keyed 0 below
-        const char* r = xb + (t * 16 + c16) * (int64_t)(RQ_DPAD * 2) + 16 * kq;
+        const char* r = xb + (t * 16 + c16) * (int64_t)(DP * 2) + 16 * kq;
 #pragma unroll
-        for (int j = 0; j < 24; ++j) dst[j] = *(const rq_half8*)(r + 64 * j);
+        for (int j = 0; j < NJ; ++j) dst[j] = *(const rq_half8*)(r + 64 * j);
     };
     const int64_t tstep = 2 * (int64_t)gridDim.x;
     int64_t t = 2 * (int64_t)blockIdx.x + par;
@@ -63,7 +67,7 @@ __global__ __launch_bounds__(256, 1) void rq_exact_scan_kernel(RqRescoreArgs a, 
         if (tn < ntiles) load_tile(tn, nxt);                         // the next tile's 24 KiB travel while this one is multiplied
         rq_double4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int j = 0; j < 24; ++j) {
+        for (int j = 0; j < NJ; ++j) {
             const float4 b0 = *(const float4*)(qrow + 32 * j), b1 = *(const float4*)(qrow + 32 * j + 4);
             const float bq[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
@@ -86,7 +90,7 @@ __global__ __launch_bounds__(256, 1) void rq_exact_scan_kernel(RqRescoreArgs a, 
         }
         if (tn < ntiles) {
 #pragma unroll
-            for (int j = 0; j < 24; ++j) cur[j] = nxt[j];
+            for (int j = 0; j < NJ; ++j) cur[j] = nxt[j];
         }
     }
     // the slots between the last tile and the end of the last bin (rows_alloc is a multiple of 64, tiles are 16 rows): empty keys
@@ -99,6 +103,8 @@ hipError_t rq_exact_scan_launch(const RqRescoreArgs& a, int B, int cu_count, hip
     if (a.binkeys != nullptr || a.nb <= 0 || B <= 0 || (int64_t)a.nb * RQ_BIN_ROWS < a.n_rows) return hipErrorInvalidValue;
     const int64_t npairs = ((a.n_rows + 15) / 16 + 1) / 2;
     const int gx = (int)std::min<int64_t>(std::max<int64_t>(npairs, 1), std::max(cu_count, 1));
-    hipLaunchKernelGGL(rq_exact_scan_kernel, dim3(gx, (B + RQ_EXACT_QB - 1) / RQ_EXACT_QB), dim3(256), 0, stream, a, B);
+    if (a.dpad == 384) hipLaunchKernelGGL(rq_exact_scan_kernel<384>, dim3(gx, (B + RQ_EXACT_QB - 1) / RQ_EXACT_QB), dim3(256), 0, stream, a, B);
+    else if (a.dpad == RQ_DPAD) hipLaunchKernelGGL(rq_exact_scan_kernel<RQ_DPAD>, dim3(gx, (B + RQ_EXACT_QB - 1) / RQ_EXACT_QB), dim3(256), 0, stream, a, B);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -114,6 +114,12 @@ struct StreamCtx {
 // 2 x 168 + 168 <= 512 VGPRs; LDS: 3 x 53 760 B <= 160 KB) for a tail workgroup to be resident beside the scan.
 struct rq_index {
     int dim = 0, device = 0, cu_count = 256;
+    // Stored row length in elements (option "row_pad"): 384 for dim <= 384, else 768 (RQ_DPAD); fixed before the first row is stored.
+    // Everything that addresses corpus rows takes its stride from here (rowb()).  384 = the narrow layout (rq_scan_narrow.hip): rows of
+    // 768 bytes, no int8 image, passes of 64 / 128 queries.  The query-side buffers (qh, q32, rings) are 768 elements wide in both.
+    int dpad = RQ_DPAD;
+    bool narrow() const { return dpad != RQ_DPAD; }
+    size_t rowb() const { return (size_t)dpad * 2; }   // bytes per stored fp16 row
     int64_t n = 0, cap = 0, row_offset = 0;
     char* x = nullptr;
     double* rownorm64 = nullptr;

@@ -4,7 +4,7 @@
 #include <stdint.h>
 
 struct RqScanArgs {
-    const void* x;            // fp16 corpus shard [rows_padded][768], rows_padded % 64 == 0, pad rows zero
+    const void* x;            // fp16 corpus shard [rows_padded][768] (rq_scan_narrow_launch: [rows_padded][384]), rows_padded % 64 == 0, pad rows zero
     const float* row_scale;   // [rows_padded] 2^-12 / ||row|| (cosine) or 2^-12 (inner product); pad entries NaN
     const _Float16* qh;       // [QB][768] fp16(q / ||q|| * 2^12) of this block (QB = 64, 128 or 256), unused slots zero
     uint2* bins;              // [QB][bins_stride] per (query, quad) record, see rq_device.h
@@ -38,13 +38,20 @@ hipError_t rq_scan_launch(const RqScanArgs& a, int S, int pf, int ks, int qw, bo
 hipError_t rq_scan_wide_launch(const RqScanArgs& a, int variant, int queries, bool nt, int grid, hipStream_t stream,
                                hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// Rows of 384 elements (rq_scan_narrow.hip; rq_index.h dpad = 384): a.x = fp16 rows of 768 bytes, a.qh = prepared queries in their
+// usual 768-element slots, a.i8 = 0.  queries = 64 (one 16-query group per wave) or 128 (two: records of 128 queries parked in LDS,
+// two workgroups per CU); 256-thread workgroups, ring of 3 x 12 KiB stages, prefetch 1, med3 selection.  One built form each.
+hipError_t rq_scan_narrow_launch(const RqScanArgs& a, int queries, bool nt, int grid, hipStream_t stream,
+                                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
+// dpad (here and below): stored row length in elements, 768 or 384 (rq_index.h); rows are dpad * 2 bytes apart.
 // Row statistics at add time: row_norm64[i] = sqrt(sum x^2) in fp64; stats[3] (device, running maxima as double bits):
 // largest norm, largest relative and absolute mass of fp16-subnormal elements in a row (see rq_select.hip).
-hipError_t rq_rownorm_launch(const void* x, int64_t row_begin, int64_t row_end, double* norm64, unsigned long long* stats, hipStream_t stream);
+hipError_t rq_rownorm_launch(const void* x, int dpad, int64_t row_begin, int64_t row_end, double* norm64, unsigned long long* stats, hipStream_t stream);
 
 // fp32 rows (device) -> fp16 rows, optionally L2-normalised first (see include/rq.h rq_index_add_f32).
-hipError_t rq_convert_f32_launch(const float* src, int dim, int64_t n, int normalize, void* dst_rows_f16, hipStream_t stream);
-hipError_t rq_pad_f16_launch(const void* src, int dim, int64_t n, void* dst_rows_f16, hipStream_t stream);
+hipError_t rq_convert_f32_launch(const float* src, int dim, int64_t n, int normalize, void* dst_rows_f16, int dpad, hipStream_t stream);
+hipError_t rq_pad_f16_launch(const void* src, int dim, int64_t n, void* dst_rows_f16, int dpad, hipStream_t stream);
 
 // Query preparation: qnorm64[q] = ||q|| (fp64); qh = fp16(q / ||q|| * 2^12) padded to 768, slots >= B zero.
 // One 256-thread workgroup per query slot (rq_device.h rq_prep_body); run by rq_prep_queries_kernel or, for the NEXT batch
@@ -76,6 +83,7 @@ hipError_t rq_select_bins_launch(const uint2* bins, int64_t bins_stride, int64_t
 // Pass 3: exact fp64 re-score of every row of the first nb bins of each query -> candidate keys (score, local row).
 struct RqRescoreArgs {
     const void* x;
+    int dpad;                  // stored row length of x in elements (768 or 384)
     const float* q32;          // [B][768] raw fp32 queries, zero padded
     const double* qnorm64;     // [B]
     const double* rownorm64;   // [rows_padded]
@@ -122,6 +130,7 @@ hipError_t rq_final_launch(const RqFinalArgs& a, int B, hipStream_t stream);
 struct RqTailArgs {
     const float* q; int dim;                       // raw fp32 queries [B][dim]
     const void* x; const double* rownorm64; int64_t n_rows;
+    int dpad;                                      // stored row length of x in elements (768 or 384): selects the tail kernel's instantiation
     const uint2* bins; int64_t bins_stride; int64_t nbins;
     const float* wgmax; int wgmax_stride; int nwg;
     int nwg_split, nwg2;                           // queries >= nwg_split were scanned by a grid of nwg2 workgroups (a call's narrow passes follow its wide ones)
@@ -145,6 +154,10 @@ struct RqTailArgs {
 // preparation `pa` of a LATER batch
 hipError_t rq_scan_tail_launch(const RqScanArgs& sa, const RqTailArgs& ta, int tail_B, const RqPrepArgs& pa, bool nt, int scan_grid, int epi, hipStream_t stream,
                                hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// the same launch over rows of 384 elements (rq_scan_narrow.hip): scan workgroups of rq_scan_narrow_launch's 64-query form, tail
+// workgroups that read rows of 768 bytes, the same preparation workgroups
+hipError_t rq_scan_narrow_tail_launch(const RqScanArgs& sa, const RqTailArgs& ta, int tail_B, const RqPrepArgs& pa, bool nt, int scan_grid, hipStream_t stream,
+                                      hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 hipError_t rq_tail_launch(const RqTailArgs& a, int B, hipStream_t stream);
 // Tails of the two batches of a scanned-ahead pair (one 128-query pass, rq_api.hip "scan_ahead") in ONE launch, plus pa.nslots
 // workgroups that prepare the queries of the batch announced after them: grid = chunks x (B0 + B1) tail workgroups, then pa.

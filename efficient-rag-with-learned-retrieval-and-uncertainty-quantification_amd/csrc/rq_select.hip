@@ -21,18 +21,21 @@
 // sqrt(sum of their squares) * |q| by Cauchy-Schwarz.  stats[1] / stats[2] keep the shard's largest such mass relative to
 // the row norm (cosine) and absolute (inner product); rq_api.hip adds them to the certificate's error bound.
 // stats[0] = largest row norm.  (Bits of non-negative doubles order as integers.)
+// dpad = stored row length (768 or 384 elements): a lane skips the loads that lie beyond it -- the zeros the longer layout holds
+// there add nothing, so norms and sums come out the same bits in both layouts (the same holds for the kernels below).
 // --------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rq_rownorm_kernel(const char* x, int64_t row_begin, int64_t row_end, double* norm64,
+__global__ __launch_bounds__(256) void rq_rownorm_kernel(const char* x, int dpad, int64_t row_begin, int64_t row_end, double* norm64,
                                                          unsigned long long* stats) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     double mx_norm = 0.0, mx_rel = 0.0, mx_abs = 0.0;
     for (int64_t row = row_begin + wave; row < row_end; row += nwaves) {
-        const char* r = x + row * (RQ_DPAD * 2);
+        const char* r = x + row * (int64_t)(dpad * 2);
         double acc = 0.0, sub = 0.0;
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
+            if (p * 256 + 4 * lane >= dpad) continue;
             const rq_half4 v = *(const rq_half4*)(r + p * 512 + lane * 8);
             const ushort4 b = *(const ushort4*)(r + p * 512 + lane * 8);
             const unsigned short bits[4] = {b.x, b.y, b.z, b.w};
@@ -58,11 +61,12 @@ __global__ __launch_bounds__(256) void rq_rownorm_kernel(const char* x, int64_t 
         if (mx_abs > 0.0) atomicMax(&stats[2], (unsigned long long)__double_as_longlong(mx_abs));
     }
 }
-hipError_t rq_rownorm_launch(const void* x, int64_t row_begin, int64_t row_end, double* norm64, unsigned long long* stats, hipStream_t stream) {
+hipError_t rq_rownorm_launch(const void* x, int dpad, int64_t row_begin, int64_t row_end, double* norm64, unsigned long long* stats, hipStream_t stream) {
+    if (dpad != 384 && dpad != RQ_DPAD) return hipErrorInvalidValue;
     if (row_end <= row_begin) return hipSuccess;
     int64_t rows = row_end - row_begin;
     int grid = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
-    hipLaunchKernelGGL(rq_rownorm_kernel, dim3(grid), dim3(256), 0, stream, (const char*)x, row_begin, row_end, norm64, stats);
+    hipLaunchKernelGGL(rq_rownorm_kernel, dim3(grid), dim3(256), 0, stream, (const char*)x, dpad, row_begin, row_end, norm64, stats);
     return hipGetLastError();
 }
 
@@ -81,9 +85,9 @@ hipError_t rq_rowscale_launch(const double* norm64, int64_t row_begin, int64_t r
 
 // --------------------------------------------------------------------------------------------
 // fp32 -> fp16 rows (optionally unit-normalised with the fp64 norm), fp16 -> padded fp16 rows
-// one wave per row; source row has `dim` elements, destination RQ_DPAD (zero padded)
+// one wave per row; source row has `dim` elements, destination dpad (768 or 384, zero padded)
 // --------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rq_convert_f32_kernel(const float* src, int dim, int64_t n, int normalize, _Float16* dst) {
+__global__ __launch_bounds__(256) void rq_convert_f32_kernel(const float* src, int dim, int64_t n, int normalize, _Float16* dst, int dpad) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * 4;
@@ -102,9 +106,10 @@ __global__ __launch_bounds__(256) void rq_convert_f32_kernel(const float* src, i
             }
         double nrm = 1.0;
         if (normalize) { acc = rq_wave_sum(acc); nrm = sqrt(acc); if (!(nrm > 0.0)) nrm = 1.0; }
-        _Float16* d = dst + row * RQ_DPAD;
+        _Float16* d = dst + row * dpad;
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
+            if (p * 256 + 4 * lane >= dpad) continue;
             rq_half4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -115,22 +120,24 @@ __global__ __launch_bounds__(256) void rq_convert_f32_kernel(const float* src, i
         }
     }
 }
-hipError_t rq_convert_f32_launch(const float* src, int dim, int64_t n, int normalize, void* dst, hipStream_t stream) {
+hipError_t rq_convert_f32_launch(const float* src, int dim, int64_t n, int normalize, void* dst, int dpad, hipStream_t stream) {
+    if ((dpad != 384 && dpad != RQ_DPAD) || dim > dpad) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
     int grid = (int)((n + 3) / 4 < 4096 ? (n + 3) / 4 : 4096);
-    hipLaunchKernelGGL(rq_convert_f32_kernel, dim3(grid), dim3(256), 0, stream, src, dim, n, normalize, (_Float16*)dst);
+    hipLaunchKernelGGL(rq_convert_f32_kernel, dim3(grid), dim3(256), 0, stream, src, dim, n, normalize, (_Float16*)dst, dpad);
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void rq_pad_f16_kernel(const _Float16* src, int dim, int64_t n, _Float16* dst) {
+__global__ __launch_bounds__(256) void rq_pad_f16_kernel(const _Float16* src, int dim, int64_t n, _Float16* dst, int dpad) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int64_t row = wave; row < n; row += nwaves) {
         const _Float16* s = src + row * dim;
-        _Float16* d = dst + row * RQ_DPAD;
+        _Float16* d = dst + row * dpad;
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
+            if (p * 256 + 4 * lane >= dpad) continue;
             rq_half4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const int i = p * 256 + 4 * lane + e; o[e] = i < dim ? s[i] : (_Float16)0.f; }
@@ -138,10 +145,11 @@ __global__ __launch_bounds__(256) void rq_pad_f16_kernel(const _Float16* src, in
         }
     }
 }
-hipError_t rq_pad_f16_launch(const void* src, int dim, int64_t n, void* dst, hipStream_t stream) {
+hipError_t rq_pad_f16_launch(const void* src, int dim, int64_t n, void* dst, int dpad, hipStream_t stream) {
+    if ((dpad != 384 && dpad != RQ_DPAD) || dim > dpad) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
     int grid = (int)((n + 3) / 4 < 4096 ? (n + 3) / 4 : 4096);
-    hipLaunchKernelGGL(rq_pad_f16_kernel, dim3(grid), dim3(256), 0, stream, (const _Float16*)src, dim, n, (_Float16*)dst);
+    hipLaunchKernelGGL(rq_pad_f16_kernel, dim3(grid), dim3(256), 0, stream, (const _Float16*)src, dim, n, (_Float16*)dst, dpad);
     return hipGetLastError();
 }
 
@@ -332,10 +340,11 @@ __global__ __launch_bounds__(256) void rq_rescore_kernel(RqRescoreArgs a) {
     for (int j = wave; j < binrows; j += 4) {
         const int64_t row = bin * RQ_BIN_ROWS + j;
         if (row >= a.n_rows) { if (lane == 0) out[j] = 0; continue; }
-        const char* r = xb + row * (RQ_DPAD * 2);
+        const char* r = xb + row * (int64_t)(a.dpad * 2);
         double dot = 0.0;
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
+            if (p * 256 + 4 * lane >= a.dpad) continue;   // (a 384-element row: the rest would be zeros)
             const rq_half4 v = *(const rq_half4*)(r + p * 512 + lane * 8);
 #pragma unroll
             for (int e = 0; e < 4; ++e) dot += (double)qv[p * 4 + e] * (double)(float)v[e];
@@ -349,7 +358,7 @@ __global__ __launch_bounds__(256) void rq_rescore_kernel(RqRescoreArgs a) {
     }
 }
 hipError_t rq_rescore_launch(const RqRescoreArgs& a, int B, hipStream_t stream) {
-    if (a.nb <= 0 || B <= 0) return hipErrorInvalidValue;
+    if (a.nb <= 0 || B <= 0 || (a.dpad != 384 && a.dpad != RQ_DPAD)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(rq_rescore_kernel, dim3(a.nb, B), dim3(256), 0, stream, a);
     return hipGetLastError();
 }

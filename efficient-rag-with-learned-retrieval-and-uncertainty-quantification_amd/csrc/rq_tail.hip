@@ -21,22 +21,24 @@
 #include "rq_kernels.h"
 #include "rq_tail_body.h"
 
-template <int NV>
+template <int NV, int DP>
 __global__ __launch_bounds__(256) void rq_tail_kernel(RqTailArgs a) {
     __shared__ RqTailLds lds;
-    rq_tail_body<NV>(a, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, lds);
+    rq_tail_body<NV, DP>(a, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, lds);
 }
 
-template <int NV>
+template <int NV, int DP = RQ_DPAD>
 static hipError_t rq_tail_launch_nv(const RqTailArgs& a, int B, hipStream_t stream) {
     const int64_t chunks = (a.nbins + 512 * NV - 1) / (512 * NV);
     if (chunks < 1 || chunks > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((rq_tail_kernel<NV>), dim3((unsigned)chunks, B), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((rq_tail_kernel<NV, DP>), dim3((unsigned)chunks, B), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 
 hipError_t rq_tail_launch(const RqTailArgs& a, int B, hipStream_t stream) {
     if (a.m < 1 || a.m > RQ_FAST_MAX_M || a.k < 1 || a.k > RQ_FAST_MAX_K) return hipErrorInvalidValue;
+    if (a.dpad == 384) return rq_tail_small_chunks(a.nbins, B) ? rq_tail_launch_nv<1, 384>(a, B, stream) : rq_tail_launch_nv<4, 384>(a, B, stream);
+    if (a.dpad != RQ_DPAD) return hipErrorInvalidValue;
     return rq_tail_small_chunks(a.nbins, B) ? rq_tail_launch_nv<1>(a, B, stream) : rq_tail_launch_nv<4>(a, B, stream);
 }
 
@@ -68,6 +70,7 @@ static hipError_t rq_pair_tail_launch_nv(const RqTailArgs& t0, int B0, const RqT
 hipError_t rq_pair_tail_launch(const RqTailArgs& t0, int B0, const RqTailArgs& t1, int B1, const RqPrepArgs& pa, hipStream_t stream) {
     for (const RqTailArgs* t : {&t0, &t1})
         if (t->m < 1 || t->m > RQ_FAST_MAX_M || t->k < 1 || t->k > RQ_FAST_MAX_K) return hipErrorInvalidValue;
+    if (t0.dpad != RQ_DPAD || t1.dpad != RQ_DPAD) return hipErrorInvalidValue;   // (pairs are scanned over rows of 768 elements only)
     if (B0 < 1 || B1 < 1 || t0.nbins != t1.nbins || pa.nslots < 0 || pa.nslots > 64) return hipErrorInvalidValue;
     return rq_tail_small_chunks(t0.nbins, B0 + B1) ? rq_pair_tail_launch_nv<1>(t0, B0, t1, B1, pa, stream)
                                                    : rq_pair_tail_launch_nv<4>(t0, B0, t1, B1, pa, stream);

@@ -24,7 +24,10 @@ template <int N> struct RqInt { static constexpr int value = N; };
 
 // One tail workgroup: chunk `chunk` (of `nchunks`) of query `q`.  256 threads.
 // NV: 16-byte loads (two bin records each) per thread: chunk = 512 * NV bins per workgroup
-template <int NV>
+// DP: stored row length in elements (768 or 384, rq_index.h dpad): the row stride, and how much of a row the re-score reads.  The
+//     elements a 384-element row lacks are zeros in the 768-element layout: they add nothing to the fp64 sums, whose order is the
+//     same, so both layouts give the same bits.
+template <int NV, int DP = RQ_DPAD>
 __device__ __forceinline__ void rq_tail_body(const RqTailArgs& a, const int chunk, const int q, const int nchunks, RqTailLds& L) {
     float* const qs = L.qs;
     double* const qpart = L.qpart;
@@ -178,7 +181,9 @@ __device__ __forceinline__ void rq_tail_body(const RqTailArgs& a, const int chun
         const char* xb = (const char*)a.x;
         uint64_t* out = a.cand + (int64_t)q * RQ_CAND_CAP;
         for (int j0 = wave * 8; j0 < njob; j0 += 32) {
-            rq_half8 xv[2][6];
+            constexpr int NP = DP / 128;   // 16-byte loads per lane and row
+            static_assert(DP == 384 || DP == RQ_DPAD, "stored row length");
+            rq_half8 xv[2][NP];
             int64_t rows[2];
             double rn[2];
             int pos[2];
@@ -193,13 +198,13 @@ __device__ __forceinline__ void rq_tail_body(const RqTailArgs& a, const int chun
                 rows[u] = (int64_t)hits[job >> 6] * RQ_BIN_ROWS + (job & 63);
                 const int64_t rr = rows[u] < a.n_rows ? rows[u] : 0;
                 rn[u] = a.rownorm64[rr];
-                const char* r = xb + rr * (RQ_DPAD * 2) + sub * 16;
+                const char* r = xb + rr * (DP * 2) + sub * 16;
 #pragma unroll
-                for (int pp = 0; pp < 6; ++pp) xv[u][pp] = *(const rq_half8*)(r + pp * 256);
+                for (int pp = 0; pp < NP; ++pp) xv[u][pp] = *(const rq_half8*)(r + pp * 256);
             }
             double dot[2] = {0.0, 0.0};
 #pragma unroll
-            for (int pp = 0; pp < 6; ++pp) {
+            for (int pp = 0; pp < NP; ++pp) {
                 const float4 qlo = *(const float4*)&qs[pp * 128 + 8 * sub], qhi = *(const float4*)&qs[pp * 128 + 8 * sub + 4];
                 const float qq[8] = {qlo.x, qlo.y, qlo.z, qlo.w, qhi.x, qhi.y, qhi.z, qhi.w};
 #pragma unroll

@@ -617,7 +617,9 @@ class DenseIndex:
 
     def _apply_backend_options(self) -> None:
         for name, value in self.backend_options.items():
-            if name == "stripe_rows" and len(self._index):      # the stripe layout of a multi-device index is fixed by its first rows
+            # the stripe layout of a multi-device index and the stored row length are fixed by the first rows (a persisted collection
+            # comes back with the row length of the library's rule, include/rq.h "row_pad")
+            if name in ("stripe_rows", "row_pad") and len(self._index):
                 continue
             self._index.set_option(name, float(value))
 

@@ -46,6 +46,9 @@ enum { RQ_METRIC_COSINE = 0, RQ_METRIC_IP = 1 };
 int rq_device_count(void);
 
 /* Create an empty index of `dim`-element rows (1 <= dim <= RQ_MAX_DIM).  NULL on error.
+ * Stored row length: rows are kept zero padded to 384 fp16 elements (768 B per row) when dim <= 384 and to 768 elements
+ *   (1 536 B) otherwise; option "row_pad" reads it and, on an empty index, changes it.  Results do not depend on it (scores are
+ *   bit-identical); memory and the bytes every scan streams do.
  * n_devices == 1: one row shard on device_ids[0] (the form every *_device call works on; shards in other processes
  *   are merged with rq_merge_keys_device).
  * n_devices  > 1: the rows are sharded across device_ids[0..n_devices) inside the library: every appended block is cut
@@ -163,6 +166,18 @@ int rq_merge_keys_device(const uint64_t* d_keys_in, int n_per_query, int B, int 
  * "tail_local" (A/B hook, default 1: a tail workgroup with more than k re-scored rows publishes only its own k best keys),
  * "poison_cand" (test hook: candidate lists are filled with 0xff..ff keys before every tail),
  * "poison_bins" (test hook: before a search's scan, the bin records of every query slot its passes cover are filled with 0xff bytes).
+ * "row_pad" (elements per stored row: 384 or 768.  Always readable.  Default: 384 for dim <= 384, else 768 -- also for an index
+ *   that rq_load creates, whatever layout the saved index had: the files are the same.  Settable to 384 or 768 only while the
+ *   index holds no rows (a reservation made before is made again with the new row length); RQ_EINVAL for any other value, for
+ *   384 when dim > 384, and once rows are stored.  On a multi-device index it is passed to every device's shard.
+ *   768 on an index of dim <= 384 keeps the wide layout and every kernel and option of it: the A/B hook.
+ *   An index with "row_pad" = 384 (the NARROW layout, csrc/rq_scan_narrow.hip) stores and streams 768 B per row and has ONE built
+ *   scan form per pass size: "ring" / "kstage" / "prefetch" / "epi" are accepted and ignored.  Deliberately not built for it: the
+ *   int8 image ("scan8" is treated as 0: "scan8_used" stays 0, "scan8_row_err" stays -1 -- an image of a 768-byte row would save
+ *   nothing); the 256-query pass (calls of more than 64 queries are cut into passes of 128, then 64; "wide_batch" 0 = 64 only;
+ *   "wide128" / "wide256" / "wide8" / "wide256_8" do not apply); the "scan_ahead" pairing (an announced batch still gets its
+ *   queries prepared by the fused launch).  The certificate's "eps" stays the bound derived for 768 elements, which holds for
+ *   shorter rows too.)
  * "scan8" = 1 measures where the ladder STARTS when the image is built (64 stored rows searched as queries through every rung, the
  *   fastest rung that certifies wins; "scan8_calibrated_rows", "scan8_calib_ms_<class><rung>", "scan8_calib_unc_<class><rung>" report it).
  * Read-only: "repaired_queries" (queries that came back uncertified and were repaired, all rungs of the ladder), "scan8_used" (searches that scanned the int8 image), "scan8_row_err" (worst row's relative int8 error, -1 = image
@@ -177,7 +192,7 @@ double rq_get_option(const rq_index* idx, const char* name);
 typedef struct rq_timing {
     double scan_ms;          /* sum of HIP-event durations of the scan kernel launches recorded */
     int64_t scan_launches;   /* launches recorded (profile on) */
-    int64_t scan_bytes;      /* algorithmic corpus bytes of those launches: rows * 2 * dim_padded each */
+    int64_t scan_bytes;      /* algorithmic corpus bytes of those launches: rows * 2 * "row_pad" each over the fp16 rows (rows * 768 over the int8 image) */
     int64_t searches;        /* rq_search* calls */
     int64_t queries;         /* queries searched */
     int64_t widened;         /* queries re-run with a wider candidate set */
