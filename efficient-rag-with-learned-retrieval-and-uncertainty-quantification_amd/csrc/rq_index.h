@@ -1,5 +1,6 @@
-// rq_index.h -- internal definitions shared by rq_api.hip (single-device index, the C ABI) and rq_multi.hip (the
-// multi-device parent): error channel, the index object, the per-stream workspaces, the device guard.
+// rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
+// rq_search.hip (search orchestration), rq_scan8.hip (the int8 image and its ladder) and rq_multi.hip (the multi-device
+// parent): error channel, the index object, the per-stream workspaces, the device guard.
 // Not part of the public boundary (that is include/rq.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,22 +31,31 @@ RQ_INTERNAL const char* rq_err_text();
         if (e_ != hipSuccess) return set_err(RQ_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// hipFree every pointer of the list that is set, and null it
+template <class... T>
+static inline void free_dev(T*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+
 // ---------------------------------------------------------------------------------------------
 // index object
 // ---------------------------------------------------------------------------------------------
+// One set of prepared queries (rq_kernels.h RqPrepArgs): RQ_DPAD-wide slots in both row layouts.
+struct QuerySet {
+    _Float16* qh = nullptr;       // unit-norm fp16 query fragments for the scan
+    float* q32 = nullptr;         // padded fp32 queries / fp64 norms for the tails
+    double* qn = nullptr;
+    signed char* q8 = nullptr;    // int8 scan: the queries' int8 image, their scales and quantisation errors
+    float* qscale8 = nullptr;
+    float* qeps8 = nullptr;
+    signed char* q8lo = nullptr;  // second int8 image (the residual) and the error left after both
+    float* qeps8s = nullptr;
+};
+
 struct Workspace {
     int bcap = 0;                 // query slots (multiple of 64)
     int64_t bins_stride = 0;      // bin records per query
     int64_t binkeys_cap = 0;      // entries per query
     size_t cand_elems = 0;        // candidate keys allocated in total (queries of a call x keys per query)
-    _Float16* qh = nullptr;
-    float* q32 = nullptr;
-    double* qn = nullptr;
-    signed char* q8 = nullptr;    // int8 scan: the queries' int8 image, their scales and quantisation errors (rq_kernels.h RqPrepArgs)
-    float* qscale8 = nullptr;
-    float* qeps8 = nullptr;
-    signed char* q8lo = nullptr;  // second int8 image (the residual) and the error left after both
-    float* qeps8s = nullptr;
+    QuerySet qs;                  // [bcap] the call's prepared queries
     uint2* bins = nullptr;        // [bcap][bins_stride] scan output: one record per (query, quad), see rq_device.h
     uint64_t* binkeys = nullptr;
     uint64_t* cand = nullptr;
@@ -80,14 +90,7 @@ struct StreamCtx {
     // "pipeline" = 2 keeps the prepared queries of three consecutive calls apart (slot = call number mod 3): call i scans
     // slot i, the tail of call i - 1 that rides with it reads slot i - 1, and the extra workgroups of the same launch prepare
     // the hinted queries of call i + 1 into slot i + 1 (rq_search_hint_next_device)
-    _Float16* ring_qh[3] = {nullptr, nullptr, nullptr};
-    float* ring_q32[3] = {nullptr, nullptr, nullptr};
-    double* ring_qn[3] = {nullptr, nullptr, nullptr};
-    signed char* ring_q8[3] = {nullptr, nullptr, nullptr};
-    float* ring_qscale8[3] = {nullptr, nullptr, nullptr};
-    float* ring_qeps8[3] = {nullptr, nullptr, nullptr};
-    signed char* ring_q8lo[3] = {nullptr, nullptr, nullptr};
-    float* ring_qeps8s[3] = {nullptr, nullptr, nullptr};
+    QuerySet ring[3];                   // 64 slots each
     const float* hint_q = nullptr;      // queries announced for the next fused call, not yet prepared
     int hint_B = 0;
     const float* prepped_q = nullptr;   // queries a launch has already prepared ...
@@ -194,10 +197,6 @@ struct rq_index {
 //   (4.88e-4 + 8e-7 + 1.83e-4 + 1.2e-7 + 7.6e-6 = 6.8e-4).  See DESIGN.md "certificate".
 static const float RQ_EPS_DEFAULT = 7.0e-4f;
 
-// Bound on |scan score - exact score| handed to the tail kernels, which use it as is for cosine and multiplied by the
-// largest row norm for the inner product: the derived bound (or option "eps") plus what the matrix cores drop by flushing
-// the fp16-subnormal elements of a stored row (rq_select.hip rq_rownorm_kernel).
-RQ_INTERNAL float scan_eps(const rq_index* idx, int metric);
 // Beyond this bound the approximate pass cannot narrow anything down (cosine scores live in [-1, 1]): scan exactly.
 static const float RQ_EPS_USELESS = 0.05f;
 
@@ -221,7 +220,23 @@ struct DeviceGuard {
     if (!dg_.ok) return set_err(RQ_EHIP, "cannot select device %d", (idx)->device)
 
 
-// ---- entry points shared between the two translation units ------------------------------------------------
+// ---- entry points shared between the translation units -----------------------------------------------------
+// How run_pipeline is called.
+enum CallFlags : unsigned {
+    CALL_MAY_DEFER = 1,       // the caller accepts results that are complete only after rq_search_flush_device ("pipeline" option)
+    CALL_FORCE_GENERIC = 2,   // the generic sorted tail, whatever "fast_tail" says
+    CALL_ALLOW8 = 4,          // the int8 image may be the scan operand
+};
+struct SearchOut { float* scores; int64_t* rows; uint64_t* keys; int* status; };   // a call's device outputs (keys may be null)
+// rq_search.hip
+RQ_INTERNAL int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags);
+RQ_INTERNAL int flush_all(rq_index* idx);   // launches every tail still waiting for a scan ("pipeline" = 2)
+RQ_INTERNAL void free_ctx(StreamCtx& c);
+// rq_scan8.hip
+RQ_INTERNAL void drop_x8(rq_index* idx);
+RQ_INTERNAL void scan8_reset_levels(rq_index* idx);
+RQ_INTERNAL int ensure_x8(rq_index* idx, hipStream_t s);
+RQ_INTERNAL void scan8_account(rq_index* idx, int k, int checked, int repaired);
 RQ_INTERNAL int rq_add_host_common(rq_index* idx, const void* rows, int64_t n_rows, bool is_f32, int normalize);
 RQ_INTERNAL int rq_search_begin(rq_index* idx, const float* queries, int B, int k, int metric);      // stage + enqueue, no wait
 RQ_INTERNAL int rq_search_end(rq_index* idx, int B, int k, int metric, float* out_scores, int64_t* out_rows);   // wait, repair, hand over

@@ -9,12 +9,12 @@ check_records() tests exactly that premise against the exact scores.  Used by te
 GPU) and tests/test_bin_records.py (this module against hand-made bit patterns and planted faults).
 
 The bound `beta` is the one the tail itself uses for |approximate - exact| (unit-query units):
-  * fp16, cosine: beta = eps_cosine (option), = scan_eps(COSINE) (rq_api.hip:27-31) -- the derived 7e-4 (or option "eps") plus the
+  * fp16, cosine: beta = eps_cosine (option), = scan_eps(COSINE) (rq_plan.h scan_eps) -- the derived 7e-4 (or option "eps") plus the
     fp16-subnormal share of the worst row.  The tail tests bins against T with it (rq_tail_body.h:36, 98) and the certificate
     bounds a row left out by T + eps (rq_final_body.h:172).
   * fp16, inner product: the scan scores the UNIT query, so its records compare with E_ip / ||q||_64; the tail scales the bound by
-    the largest row norm (rq_tail_body.h:98, rq_api.hip:989 max_row_norm * (1 + 1e-6)), so beta = eps_ip * max_row_norm * (1 + 1e-6).
-  * int8 image (rq_api.hip:588 scan8_eps, 978-989): |approx - exact| <= e_q + (1 + e_q) e_rows, e_rows the worst relative error of
+    the largest row norm (rq_tail_body.h:98, rq_search.hip tail_args: max_row_norm * (1 + 1e-6)), so beta = eps_ip * max_row_norm * (1 + 1e-6).
+  * int8 image (rq_plan.h scan8_eps, rq_search.hip tail_args): |approx - exact| <= e_q + (1 + e_q) e_rows, e_rows the worst relative error of
     the bin's rows.  With option "bin_bound" the tail tests bin b with its own rows' error (rq_tail_body.h:117-125), so per bin
     beta_b = e_q + (1 + e_q)(binerr_b * 1.000001 + 2e-5), binerr_b from rq_debug_bin_err and e_q the query's one-image (or split)
     error recomputed in numpy (int8_query_error); times max_row_norm for the inner product.

@@ -117,8 +117,9 @@ def test_record_codec_properties_on_the_host(tmp_path):
 def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     """CPU-only sanitizer builds (the GPU boxes of this pool cannot run sanitizers): -fsanitize=address,undefined over (a) the
     record / key codecs of csrc/rq_device.h, (b) the multi-device parent of csrc/rq_multi.hip -- stripe arithmetic, row read-back,
-    k-way merge incl. its threads, the poisoned / failed-search paths -- behind STUBBED shards (tests/native/multi_check.cpp), and
-    (c) librq_bm25's scorer (csrc/rq_bm25.cpp compiled into tests/native/bm25_check.cpp).  Any report aborts the program."""
+    k-way merge incl. its threads, the poisoned / failed-search paths -- behind STUBBED shards (tests/native/multi_check.cpp),
+    (c) librq_bm25's scorer (csrc/rq_bm25.cpp compiled into tests/native/bm25_check.cpp), (d) the call plan of csrc/rq_plan.h --
+    route, pass cutting, scan grids, non-temporal rule -- on a host-built rq_index (tests/native/plan_check.cpp).  Any report aborts the program."""
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -129,7 +130,8 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     native = os.path.join(os.path.dirname(__file__), "native")
     jobs = [([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "codec_check.cpp")], "codec"),
             ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "multi_check.cpp")], "multi"),
-            ([gxx, *san, "-I", os.path.join(ROOT, "include"), os.path.join(native, "bm25_check.cpp"), os.path.join(CSRC, "rq_bm25.cpp")], "bm25")]
+            ([gxx, *san, "-I", os.path.join(ROOT, "include"), os.path.join(native, "bm25_check.cpp"), os.path.join(CSRC, "rq_bm25.cpp")], "bm25"),
+            ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "plan_check.cpp")], "plan")]
     for cmd, name in jobs:
         exe = str(tmp_path / f"{name}_san")
         subprocess.run(cmd + ["-o", exe], check=True, timeout=600, capture_output=True)

@@ -223,7 +223,7 @@ def test_every_kernel_variant_is_exact(corpus100k, opts):
                                   dict(wide_batch=1, wide256=2),
                                   dict(wide_batch=1, nt=1), dict(wide_batch=1, cu_count=5)])
 def test_every_wide_pass_variant_is_exact(corpus100k, opts):
-    """Calls with more than 64 queries are cut into passes of 256 / 128 / 64 queries (csrc/rq_api.hip run_pipeline).
+    """Calls with more than 64 queries are cut into passes of 256 / 128 / 64 queries (csrc/rq_plan.h plan_call).
     B = 333 -> 256 + 128 (77 valid); B = 100 -> 128; B = 200 -> 256; ragged shard (30 011 rows), duplicates, a zero query."""
     _, x16 = corpus100k
     x = x16[:30_011].copy()
@@ -642,7 +642,7 @@ def test_fused_headline_instantiation_matches_oracle(n, expect_nv, scan8):
     nbins = (n + 63) // 64
     wgs = lambda nv: ((nbins + 512 * nv - 1) // (512 * nv)) * 64          # rq_scan_tail_launch's rule (csrc/rq_scan.hip)
     assert (1 if wgs(1) <= 384 else 4 if wgs(4) <= 384 else 8) == expect_nv
-    assert n * 1536 > (208 << 20)                                          # -> non-temporal corpus loads (csrc/rq_api.hip)
+    assert n * 1536 > (208 << 20)                                          # -> non-temporal corpus loads (csrc/rq_plan.h)
     idx.set_option("pipeline", 2)
     idx.set_option("poison_cand", 1)
     idx.set_option("scan8", scan8)            # 2: the int8 scan (rq_scan_tail_kernel<..., 2>, what bench.py times by default) for every k of the plan
@@ -1073,7 +1073,7 @@ def test_multi_device_index_persistence_and_row_offset(tmp_path):
 
 
 def test_many_caller_streams_do_not_pile_up_workspaces():
-    """One search workspace per caller stream (csrc/rq_api.hip): 40 streams in a row must not keep 40 workspaces
+    """One search workspace per caller stream (csrc/rq_search.hip): 40 streams in a row must not keep 40 workspaces
     (the library drops idle ones beyond 8), and rq_stream_release frees one explicitly."""
     import torch
     dev = torch.device("cuda:0")
@@ -1175,7 +1175,7 @@ def _pooled_error(idx, x16, q, queries):
 @pytest.mark.parametrize("B", [64, 128])
 def test_fp16_subnormals_are_covered_by_the_error_bound(B):
     """The matrix cores flush fp16 SUBNORMAL operands to zero (this test found it: an all-subnormal corpus scores 0 in the
-    scan).  What the bound eps = 7e-4 of the certificate rests on instead (csrc/rq_select.hip, csrc/rq_api.hip scan_eps):
+    scan).  What the bound eps = 7e-4 of the certificate rests on instead (csrc/rq_select.hip, csrc/rq_plan.h scan_eps):
       * queries reach the matrix cores as fp16(q/|q| * 2^12), so a query element is flushed only below 2^-26 of the unit
         query: a query whose unit image is 4 ordinary + 764 tiny elements must keep its bin maxima within eps;
       * the share of a stored row's norm that sits in subnormal elements is measured at add time; its shard maximum is

@@ -1,4 +1,4 @@
-"""Option "scan_ahead" (csrc/rq_api.hip): a pipeline = 2 call over the fp16 rows whose stream has announced its next
+"""Option "scan_ahead" (csrc/rq_search.hip run_pipeline): a pipeline = 2 call over the fp16 rows whose stream has announced its next
 batch (rq_search_hint_next_device) scans both batches in ONE 128-query pass; the next call, if it brings exactly the announced
 batch and metric, enqueues no scan and only runs the two tails.  Every query of every call is compared with the oracle (rows
 identical, |score difference| <= 1e-6, status 0) with the candidate lists poisoned before every tail (poison_cand), and the

@@ -52,8 +52,8 @@ def test_every_narrow_form_is_a_gpu_record_case():
     fbuilt = {(1 if nt == "true" else 0, int(nv)) for nt, nv in re.findall(r"rq_scan_narrow_tail_launch_t<(true|false), (\d+)>", fused)}
     assert fbuilt == {(nt, nv) for nt in (0, 1) for nv in (1, 4, 8)}, fbuilt
     assert fbuilt <= set(gpu.NARROW_FUSED_FORMS), fbuilt - set(gpu.NARROW_FUSED_FORMS)
-    # the dispatch in rq_api.hip reaches the narrow launchers and nothing else on a narrow index
-    api = _src("rq_api.hip")
+    # the dispatch in rq_search.hip (scan_passes) reaches the narrow launchers and nothing else on a narrow index
+    api = _src("rq_search.hip")
     assert "rq_scan_narrow_launch(a, qb," in api and "rq_scan_narrow_tail_launch(" in api
     assert "rq_scan_narrow.hip" in open(os.path.join(CSRC, "Makefile")).read()
 
