@@ -59,6 +59,15 @@ _SIGNATURES = {
     "rq_search_fixup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_flush_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rq_filter_create": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "rq_filter_create_device": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rq_filter_count": (C.c_int64, [C.c_void_p]),
+    "rq_filter_destroy": (None, [C.c_void_p]),
+    "rq_search_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rq_search_filtered_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_fixup_filtered_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int]),
     "rq_nb_rope_table_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
@@ -142,6 +151,50 @@ def _ptr(a) -> C.c_void_p:
     raise TypeError(f"cannot take the address of {type(a)!r}")
 
 
+def pack_row_mask(mask_or_rows, n_rows: int) -> np.ndarray:
+    """The bitmap rq_filter_create reads (include/rq.h): bit r % 32 of uint32 word r / 32 set = local row r is allowed.  A boolean
+    array of n_rows entries is a mask; anything else is a list of row numbers (out-of-range rows raise, duplicates are harmless)."""
+    a = np.asarray(mask_or_rows)
+    if a.dtype == np.bool_:
+        if a.shape != (int(n_rows),):
+            raise ValueError(f"expected a boolean mask of {n_rows} rows, got shape {a.shape}")
+        mask = a
+    else:
+        rows = a.astype(np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= n_rows):
+            raise ValueError(f"row numbers outside 0..{int(n_rows) - 1}")
+        mask = np.zeros(int(n_rows), dtype=np.bool_)
+        mask[rows] = True
+    packed = np.packbits(mask, bitorder="little")
+    packed = np.concatenate([packed, np.zeros((-packed.size) % 4, np.uint8)])        # whole uint32 words
+    return np.ascontiguousarray(packed).view("<u4").astype(np.uint32)
+
+
+class RowFilter:
+    """Owner of one rq_filter: the rows a filtered search may return.  Holds its index (the C object belongs to it: an index that
+    was closed first has already freed it, and close() then only forgets the handle)."""
+
+    def __init__(self, index: "NativeIndex", handle: int):
+        self._index = index
+        self._h = C.c_void_p(handle)
+        self.count = int(index._lib.rq_filter_count(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            if getattr(self._index, "_h", None):
+                self._index._lib.rq_filter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return self.count
+
+
 class NativeIndex:
     """Thin owner of one rq_index handle: one row shard on one GPU, or -- `devices=[...]` with more than one entry -- rows
     sharded across several GPUs inside the library (host-buffer calls only, see include/rq.h rq_index_create)."""
@@ -212,8 +265,23 @@ class NativeIndex:
         _check(self._lib.rq_index_get_rows_f16(self._h, int(row_begin), int(n_rows), _ptr(out)), "rq_index_get_rows_f16")
         return out.view(np.float16)
 
+    # -- filters ----------------------------------------------------------------------------
+    def make_filter(self, mask_or_rows) -> RowFilter:
+        """A filter over this index's current rows from a boolean mask [len(self)] or a list of LOCAL row numbers
+        (include/rq.h rq_filter_create).  An append makes it stale."""
+        bits = pack_row_mask(mask_or_rows, len(self))
+        h = self._lib.rq_filter_create(self._h, _ptr(bits) if bits.size else None, len(self))
+        if not h:
+            raise RqError(f"rq_filter_create: {last_error()}")
+        return RowFilter(self, h)
+
+    def _filter_handle(self, row_filter: RowFilter) -> C.c_void_p:
+        if not isinstance(row_filter, RowFilter) or not row_filter._h:
+            raise ValueError("row_filter must be an open RowFilter (NativeIndex.make_filter)")
+        return row_filter._h
+
     # -- search -----------------------------------------------------------------------------
-    def search(self, queries: np.ndarray, k: int, metric: int = METRIC_COSINE) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, queries: np.ndarray, k: int, metric: int = METRIC_COSINE, *, row_filter: Optional[RowFilter] = None) -> Tuple[np.ndarray, np.ndarray]:
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -222,14 +290,29 @@ class NativeIndex:
         B = q.shape[0]
         scores = np.empty((B, int(k)), dtype=np.float32)
         rows = np.empty((B, int(k)), dtype=np.int64)
+        if row_filter is not None:
+            _check(self._lib.rq_search_filtered(self._h, self._filter_handle(row_filter), _ptr(q), B, int(k), int(metric), _ptr(scores), _ptr(rows)),
+                   "rq_search_filtered")
+            return scores, rows
         _check(self._lib.rq_search(self._h, _ptr(q), B, int(k), int(metric), _ptr(scores), _ptr(rows)), "rq_search")
         return scores, rows
 
-    def search_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_keys, d_status, stream: int = 0) -> None:
+    def search_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_keys, d_status, stream: int = 0, *,
+                      row_filter: Optional[RowFilter] = None) -> None:
+        if row_filter is not None:
+            _check(self._lib.rq_search_filtered_device(self._h, self._filter_handle(row_filter), _ptr(d_queries), int(B), int(k), int(metric),
+                                                       _ptr(d_scores), _ptr(d_rows), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)),
+                   "rq_search_filtered_device")
+            return
         _check(self._lib.rq_search_device(self._h, _ptr(d_queries), int(B), int(k), int(metric), _ptr(d_scores), _ptr(d_rows),
                                           _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)), "rq_search_device")
 
-    def search_fixup_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_keys, d_status, stream: int = 0) -> int:
+    def search_fixup_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_keys, d_status, stream: int = 0, *,
+                            row_filter: Optional[RowFilter] = None) -> int:
+        if row_filter is not None:
+            return _check(self._lib.rq_search_fixup_filtered_device(self._h, self._filter_handle(row_filter), _ptr(d_queries), int(B), int(k),
+                                                                    int(metric), _ptr(d_scores), _ptr(d_rows), _ptr(d_keys), _ptr(d_status),
+                                                                    C.c_void_p(stream)), "rq_search_fixup_filtered_device")
         return _check(self._lib.rq_search_fixup_device(self._h, _ptr(d_queries), int(B), int(k), int(metric), _ptr(d_scores),
                                                        _ptr(d_rows), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)),
                       "rq_search_fixup_device")

@@ -6,8 +6,8 @@
 //   inv_norm   [cap]      fp32 2^-12 / norm, 0 for zero rows, NaN for pad rows (scan, cosine; the queries carry 2^12)
 //   ones       [cap]      fp32 2^-12 for rows < n, NaN beyond                  (scan, inner product; lazy)
 // plus one workspace per stream (query fragments, per-bin scan records, bin keys, candidate keys).
-// Internal definitions: rq_index.h; searches: rq_search.hip (what a call does: rq_plan.h); the int8 image: rq_scan8.hip; the
-// multi-device parent (n_devices > 1): rq_multi.hip.
+// Internal definitions: rq_index.h; searches: rq_search.hip (what a call does: rq_plan.h); the int8 image: rq_scan8.hip; filtered
+// searches: rq_filter.hip; the multi-device parent (n_devices > 1): rq_multi.hip.
 #include "rq_plan.h"
 
 hipError_t rq_rowscale_launch(const double* norm64, int64_t row_begin, int64_t row_end, float* inv_norm, hipStream_t stream);
@@ -115,6 +115,7 @@ extern "C" void rq_index_destroy(rq_index* idx) {
     DeviceGuard dg_(idx->device);
     (void)hipDeviceSynchronize();
     for (auto& kv : idx->ctx) free_ctx(kv.second);
+    free_filters(idx);   // the filters nobody destroyed (include/rq.h rq_filter_destroy)
     for (auto& ev : idx->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (idx->hs_pin) (void)hipHostFree(idx->hs_pin);
     if (idx->hs_pin_q) (void)hipHostFree(idx->hs_pin_q);
@@ -284,6 +285,7 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     else if (s == "tail_local") idx->tail_local = (int)v != 0;   // A/B: 0 = every re-scored row's key goes to the query's global list
     else if (s == "use_hint") idx->use_hint = (int)v != 0;   // 0: rq_search_hint_next_device is ignored (A/B of the folded query preparation)
     else if (s == "scan_ahead") idx->scan_ahead = (int)v != 0;   // 0: a hinted batch is never scanned together with the call before it (A/B)
+    else if (s == "filter_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "filter_route must be -1 (rule), 1 (gather), 2 (scan) or 3 (exact)"); idx->filter_route = (int)v; }   // rq_filter_plan.h
     else if (s == "poison_cand") idx->poison_cand = (int)v;   // test hook: candidate lists are filled with 0xff..ff keys before every tail
     else if (s == "poison_bins") idx->poison_bins = (int)v;   // test hook: the query slots a call's passes cover are filled with 0xff bytes before its scan
     else return set_err(RQ_EINVAL, "unknown option '%s'", name);
@@ -347,6 +349,9 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
             if (c >= 0 && c < 2 && l >= 0 && l < 3) return unc ? (double)idx->calib_unc[c][l] : (double)idx->calib_ms[c][l];
         }
     }
+    if (s == "filter_route") return idx->filter_route;
+    if (s == "filter_route_last") return idx->filter_route_last;   // the route the last filtered call took (0: no row allowed; -1: none yet)
+    if (s == "filter_repaired") return (double)idx->filter_repaired;   // queries of filtered calls that were repaired
     if (s == "repaired_queries") return (double)idx->repaired_total;   // queries rq_search_fixup_device (or the blocking rq_search) had to repair so far
     if (s == "scan8_used") return (double)idx->scan8_used;   // searches that scanned the int8 image
     if (s == "hints_used") return (double)idx->hints_used;   // searches that found their queries prepared by the launch before them

@@ -103,15 +103,23 @@ __device__ __forceinline__ int rq_select_winners(const uint64_t (&key)[16], cons
 // The keys were published by other workgroups of the SAME launch with sc1 (write-through) stores and a ticket; the caller
 // (rq_tail_body.h, section D) has run an agent-scope acquire + workgroup barrier before this point, and every load of the
 // keys is an sc1 load (relaxed agent-scope atomic load) besides.
-__device__ __forceinline__ void rq_final_body(const RqFinalCore& a, int total, int overflow, float T, double qn, RqFinalLds& L) {
+// FILT (a filtered search, rq_kernels.h RqFilterArgs): the rows that must be returned are min(k, allowed rows), and a zero-norm
+// query answers with the first allowed rows instead of rows 0 .. kk-1.
+template <bool FILT = false>
+__device__ __forceinline__ void rq_final_body(const RqFinalCore& a, int total, int overflow, float T, double qn, RqFinalLds& L,
+                                              const RqFilterArgs* f = nullptr) {
     const int tid = threadIdx.x;
-    const int64_t kk = a.k < a.n_rows ? a.k : a.n_rows;
+    int64_t rows_in_play = a.n_rows;
+    if constexpr (FILT) rows_in_play = f->na;
+    const int64_t kk = a.k < rows_in_play ? a.k : rows_in_play;
     if (qn == 0.0) {   // every score is exactly 0: rows 0 .. kk-1 (score desc, row asc)
         for (int j = tid; j < a.k; j += 256) {
             const bool v = j < kk;
+            int64_t r = j;
+            if constexpr (FILT) r = v ? (int64_t)f->first[j] : 0;
             a.out_scores[j] = 0.f;
-            a.out_rows[j] = v ? a.row_offset + j : -1;
-            if (a.out_keys) a.out_keys[j] = v ? rq_make_key(0.f, (uint32_t)(a.row_offset + j)) : 0;
+            a.out_rows[j] = v ? a.row_offset + r : -1;
+            if (a.out_keys) a.out_keys[j] = v ? rq_make_key(0.f, (uint32_t)(a.row_offset + r)) : 0;
         }
         if (tid == 0) *a.out_status = 0;
         return;

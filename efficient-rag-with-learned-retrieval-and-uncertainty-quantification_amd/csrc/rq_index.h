@@ -1,6 +1,6 @@
 // rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
-// rq_search.hip (search orchestration), rq_scan8.hip (the int8 image and its ladder) and rq_multi.hip (the multi-device
-// parent): error channel, the index object, the per-stream workspaces, the device guard.
+// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_scan8.hip (the int8 image and its ladder) and
+// rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard.
 // Not part of the public boundary (that is include/rq.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -112,6 +112,21 @@ struct StreamCtx {
     int rec_B = 0, rec_slots = 0;
 };
 
+// A row filter (include/rq.h rq_filter): the set of local rows a filtered search may return.  It belongs to one index at one size
+// (n): an append makes it stale.  The bookkeeping is done once, on the host, from the bitmap; device arrays beyond the bitmap are
+// built by the first search that needs them.
+struct rq_filter {
+    rq_index* idx = nullptr;
+    int64_t n = 0, na = 0;               // rows of the index at creation, allowed rows
+    std::vector<uint32_t> bits;          // host copy of the bitmap, bits >= n clear
+    std::vector<int32_t> occ_prefix;     // [bins + 1] bins before bin b that hold an allowed row (rq_filter_plan.h)
+    uint32_t* d_bits = nullptr;          // [ceil(n / 32)]
+    uint32_t* d_first = nullptr;         // [min(na, RQ_MAX_K)] first allowed rows
+    uint32_t* d_list = nullptr;          // [na] every allowed row, ascending (gather route; lazy)
+    float* scale[2] = {nullptr, nullptr};   // [scale_cap] masked row scales per metric (scan route; lazy)
+    int64_t scale_cap[2] = {0, 0};
+};
+
 // Default scan variant: half-row stages (kstage 2), ring of 3, one LDS fragment ahead (prefetch 1, <= 168 VGPRs),
 // 2 workgroups per CU.  All variants stream at the same rate; this one leaves room on every CU (registers:
 // 2 x 168 + 168 <= 512 VGPRs; LDS: 3 x 53 760 B <= 160 KB) for a tail workgroup to be resident beside the scan.
@@ -187,6 +202,11 @@ struct rq_index {
     size_t ev_used = 0;
     int64_t ev_bytes = 0;          // algorithmic corpus bytes of the launches those events time (fp16 rows or their int8 image)
     rq_timing t = {};
+    // filtered searches (rq_filter.hip)
+    std::vector<rq_filter*> filters;   // the filters this index still owns
+    int filter_route = -1;             // option "filter_route": -1 = the rule (rq_filter_plan.h), 1 gather, 2 scan, 3 exact
+    int filter_route_last = -1;        // the route the last filtered call took (0 = empty filter)
+    int64_t filter_repaired = 0;       // queries of filtered calls that came back uncertified and were repaired
 };
 
 // Derived bound on |approximate scan score - exact score| for unit queries and cosine scaling:
@@ -229,7 +249,19 @@ enum CallFlags : unsigned {
 };
 struct SearchOut { float* scores; int64_t* rows; uint64_t* keys; int* status; };   // a call's device outputs (keys may be null)
 // rq_search.hip
-RQ_INTERNAL int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags);
+// filt (optional): the call ranks the filter's rows only (the caller has checked that it belongs to idx and is not stale)
+RQ_INTERNAL int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags,
+                             const rq_filter* filt = nullptr);
+// the repair ladder of rq_search_fixup_device; filt: of rq_search_fixup_filtered_device (no int8 rung, no int8 accounting)
+RQ_INTERNAL int fixup_ladder(rq_index* idx, const rq_filter* filt, const float* d_queries, int B, int k, int metric, float* d_scores,
+                             int64_t* d_rows, uint64_t* d_keys, int* d_status, hipStream_t s);
+RQ_INTERNAL int check_search_args(const rq_index* idx, const void* q, int B, int k, int metric, const void* sc, const void* rows);
+RQ_INTERNAL int flush_tails(rq_index* idx, hipStream_t s);
+RQ_INTERNAL int ensure_ones(rq_index* idx, hipStream_t s);
+RQ_INTERNAL int filter_workspace(rq_index* idx, hipStream_t s, int bpad, size_t cand_elems, const QuerySet** qs, uint64_t** cand);
+// rq_filter.hip
+RQ_INTERNAL void free_filters(rq_index* idx);   // rq_index_destroy: the filters the index still owns
+RQ_INTERNAL int ensure_filter_scale(rq_index* idx, const rq_filter* f, int metric, hipStream_t s);
 RQ_INTERNAL int flush_all(rq_index* idx);   // launches every tail still waiting for a scan ("pipeline" = 2)
 RQ_INTERNAL void free_ctx(StreamCtx& c);
 // rq_scan8.hip

@@ -167,6 +167,35 @@ hipError_t rq_pair_tail_launch(const RqTailArgs& t0, int B0, const RqTailArgs& t
 // (enough to spread the hits, few enough to be one dispatch round), else 2048-bin chunks
 static inline bool rq_tail_small_chunks(int64_t nbins, int B) { return ((nbins + 511) / 512) * B <= 1536; }
 
+// ---- filtered searches (rq_filter.hip, include/rq.h rq_filter): only the rows whose bit is set take part ----
+// What the filtered tail kernel gets beside its RqTailArgs (a SECOND kernel argument: RqTailArgs and every kernel that takes
+// it alone stay as they are).
+struct RqFilterArgs {
+    const uint32_t* bits;     // [ceil(n_rows / 32)] bit r % 32 of word r / 32: local row r is allowed; bits >= n_rows are clear
+    const uint32_t* first;    // [min(na, RQ_MAX_K)] the first allowed rows, ascending: the answer of a zero-norm query
+    int64_t na;               // allowed rows
+};
+// rq_tail_launch with the filter: rq_tail_kernel<NV, DP, true>.  a.m must be min(k, na).
+hipError_t rq_tail_filtered_launch(const RqTailArgs& a, const RqFilterArgs& f, int B, hipStream_t stream);
+// out[i] = src[i] for an allowed row i < n_rows, NaN for every other i < cap: the scan's row scales under a filter.
+hipError_t rq_mask_scale_launch(const float* src, const uint32_t* bits, int64_t n_rows, int64_t cap, float* out, hipStream_t stream);
+// cand[i] = 0 for every candidate key (score, LOCAL row) whose row is not allowed; n keys in all.
+hipError_t rq_mask_keys_launch(uint64_t* cand, int64_t n, const uint32_t* bits, hipStream_t stream);
+// Exact fp64 re-score of the listed rows for B queries: cand[q * cand_stride + j] = key(score(q, list[j]), list[j]), j < nlist.
+// The per-row arithmetic is rq_tail_body.h's (16 lanes per row, the same summation order).
+struct RqGatherArgs {
+    const void* x; int dpad;  // stored rows and their length in elements (768 or 384)
+    const double* rownorm64;
+    const float* q32;         // [B][768] raw fp32 queries, zero padded (rq_prep_body)
+    const double* qnorm64;    // [B]
+    const uint32_t* list;     // [nlist] local rows, each < the shard's rows
+    int64_t nlist;
+    int metric;
+    uint64_t* cand; int64_t cand_stride;
+};
+#define RQ_GATHER_MAX_CHUNKS 65535   // chunks of 256 listed rows per launch (grid y); rq_gather_score_launch loops beyond
+hipError_t rq_gather_score_launch(const RqGatherArgs& a, int B, hipStream_t stream);
+
 // Merge G sorted key lists per query (cross-shard): in [B][G*k] -> top-k scores/rows/keys.
 hipError_t rq_merge_keys_launch(const uint64_t* keys, int n_per_query, int B, int k, float* out_scores, int64_t* out_rows,
                                 uint64_t* out_keys, hipStream_t stream);

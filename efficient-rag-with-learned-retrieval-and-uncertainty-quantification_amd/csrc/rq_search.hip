@@ -77,7 +77,7 @@ static int ensure_ws(Workspace& w, int bpad, int64_t stride, int64_t m, size_t c
     return RQ_OK;
 }
 
-static int ensure_ones(rq_index* idx, hipStream_t s) {
+int ensure_ones(rq_index* idx, hipStream_t s) {
     if (idx->ones && idx->ones_valid == idx->n) return RQ_OK;
     if (!idx->ones) HIPCHK(hipMalloc((void**)&idx->ones, (size_t)idx->cap * sizeof(float)));
     std::vector<float> h((size_t)idx->cap, std::nanf(""));   // pad rows: NaN, like inv_norm (see grow)
@@ -171,7 +171,7 @@ static int launch_waiting_tail(const rq_index* idx, StreamCtx& c, hipStream_t s)
 
 // Make `s` wait for every tail still running on the internal tail stream of `s` (pipeline = 1) and launch the
 // tail that was waiting for the next scan (pipeline = 2).
-static int flush_tails(rq_index* idx, hipStream_t s) {
+int flush_tails(rq_index* idx, hipStream_t s) {
     auto it = idx->ctx.find(s);
     if (it == idx->ctx.end()) return RQ_OK;
     StreamCtx& c = it->second;
@@ -260,7 +260,8 @@ struct Call {
     CallMode mode = CALL_PLAIN;
     bool pair = false;               // this call's pass also scans the batch its stream announced ("scan_ahead")
     int par = 0, slot = -1;          // workspace of the stream, ring slot of the queries (fused)
-    const float* scale = nullptr;    // row scales of the metric
+    const float* scale = nullptr;    // row scales of the metric (a filtered call: the filter's masked copy)
+    const rq_filter* filt = nullptr; // the call ranks these rows only (include/rq.h rq_search_filtered)
     int grid_narrow = 0, nwg_split = 0;
 };
 
@@ -333,6 +334,10 @@ static int scan_passes(rq_index* idx, StreamCtx& cx, const Workspace& w, const Q
     const CallPlan& p = c.p;
     hipStream_t s = c.s;
     const bool fused = c.mode == CALL_FUSED, narrow = p.narrow, nt = p.nt;
+    // a filtered call masks rows by their NaN scale, which the compare / select form ("epi" = 0, and with it "wide_batch" = 2's
+    // 8-wave pass) does not honour beyond the shard's end: it keeps to the forms that do
+    const int epi = c.filt ? 1 : idx->epi;
+    const bool wave8 = idx->wide_batch == 2 && !c.filt;
     // the fused launch of this layout
     auto scan_tail = [&](const RqScanArgs& sa, const RqTailArgs& t, int tb, int grid, hipEvent_t e0, hipEvent_t e1) {
         return narrow ? rq_scan_narrow_tail_launch(sa, t, tb, pa, nt, grid, s, e0, e1) : rq_scan_tail_launch(sa, t, tb, pa, nt, grid, idx->epi, s, e0, e1);
@@ -373,9 +378,9 @@ static int scan_passes(rq_index* idx, StreamCtx& cx, const Workspace& w, const Q
         else if (p.use8 && qb == 256) HIPCHK(rq_scan_wide_launch(a, idx->wide256_8, 256, nt, grid, s, e0, e1));   // 256 queries over the int8 image
         else if (p.use8) HIPCHK(rq_scan_launch(a, 3, 1, 2, 4, nt, grid, 1, s, e0, e1));   // 64 queries, or 128 (a.i8 = 3)
         else if (qb == 256) HIPCHK(rq_scan_wide_launch(a, idx->wide256, 256, nt, grid, s, e0, e1));
-        else if (qb == 128 && idx->wide_batch == 2) HIPCHK(rq_scan_launch(a, 3, 4, 1, 8, nt, grid, 0, s, e0, e1));   // round 1's 8-wave pass
+        else if (qb == 128 && wave8) HIPCHK(rq_scan_launch(a, 3, 4, 1, 8, nt, grid, 0, s, e0, e1));   // round 1's 8-wave pass
         else if (qb == 128) HIPCHK(rq_scan_wide_launch(a, idx->wide128, 128, nt, grid, s, e0, e1));
-        else HIPCHK(rq_scan_launch(a, idx->ring, idx->prefetch, idx->kstage, 4, nt, grid, idx->epi, s, e0, e1));
+        else HIPCHK(rq_scan_launch(a, idx->ring, idx->prefetch, idx->kstage, 4, nt, grid, epi, s, e0, e1));
         if (fused && pa.nslots) {
             cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = (c.slot + 1) % 3;
             cx.hint_q = nullptr;
@@ -394,7 +399,7 @@ static RqTailArgs tail_args(const rq_index* idx, const Call& c, const Workspace&
     ta.q = c.d_q; ta.dim = idx->dim; ta.x = idx->x; ta.dpad = idx->dpad; ta.rownorm64 = idx->rownorm64; ta.n_rows = idx->n;
     ta.bins = w.bins; ta.bins_stride = w.bins_stride; ta.nbins = p.nbins;
     ta.wgmax = w.wgmax; ta.wgmax_stride = RQ_WGMAX_STRIDE; ta.nwg = p.grid_wide; ta.nwg_split = c.nwg_split; ta.nwg2 = c.grid_narrow;
-    ta.m = (int)std::min<int64_t>(c.k, idx->n); ta.metric = c.metric; ta.k = c.k;
+    ta.m = (int)std::min<int64_t>(c.k, c.filt ? c.filt->na : idx->n); ta.metric = c.metric; ta.k = c.k;
     ta.eps = use8 ? scan8_eps(idx) : scan_eps(idx, c.metric);
     ta.qeps = use8 ? (p.split8 ? qs.qeps8s : qs.qeps8) : nullptr;
     ta.binerr = use8 && idx->bin_bound ? idx->binerr8 : nullptr;
@@ -442,7 +447,8 @@ static int launch_tail(rq_index* idx, StreamCtx& cx, const Call& c, const RqTail
         if (e0) HIPCHK(hipEventRecord(e0, ts));
     }
     if (int r = poison_cand(idx, ta, c.B, ts)) return r;
-    HIPCHK(rq_tail_launch(ta, c.B, ts));
+    if (c.filt) HIPCHK(rq_tail_filtered_launch(ta, RqFilterArgs{c.filt->d_bits, c.filt->d_first, c.filt->na}, c.B, ts));
+    else HIPCHK(rq_tail_launch(ta, c.B, ts));
     if (e0) { HIPCHK(hipEventRecord(e1, ts)); idx->ev_used++; idx->ev_bytes += idx->n * c.p.scan_rowb; }
     if (c.mode == CALL_PIPED) { HIPCHK(hipEventRecord(cx.ev_tail[c.par], cx.tail)); cx.tail_pending[c.par] = true; }
     return RQ_OK;
@@ -459,17 +465,34 @@ static int generic_tail(rq_index* idx, const Call& c, const Workspace& w) {
     ra.n_rows = idx->n; ra.cand = w.cand;
     if (p.exact && idx->exact_mfma) HIPCHK(rq_exact_scan_launch(ra, c.B, idx->cu_count, s));   // the whole shard: fp64 contraction on the matrix cores
     else HIPCHK(rq_rescore_launch(ra, c.B, s));
+    // a filtered call: the keys of excluded rows become 0 = "no row" before anything ranks them
+    if (c.filt) HIPCHK(rq_mask_keys_launch(w.cand, (int64_t)c.B * p.ncand, c.filt->d_bits, s));
     RqFinalArgs fa;
     fa.cand = w.cand; fa.ncand = (int)p.ncand; fa.binkeys = w.binkeys; fa.binkeys_stride = p.m; fa.nb = p.nb; fa.nbins = p.exact ? p.nb : p.nbins;
     fa.qnorm64 = w.qs.qn; fa.metric = c.metric; fa.eps = scan_eps(idx, c.metric);
-    fa.max_row_norm = (float)(idx->max_row_norm * (1.0 + 1e-6)); fa.k = c.k; fa.row_offset = idx->row_offset; fa.n_rows = idx->n;
+    fa.max_row_norm = (float)(idx->max_row_norm * (1.0 + 1e-6)); fa.k = c.k; fa.row_offset = idx->row_offset; fa.n_rows = c.filt ? c.filt->na : idx->n;   // (n_rows: the rows that can be returned)
     fa.out_scores = c.out.scores; fa.out_rows = c.out.rows; fa.out_keys = c.out.keys; fa.out_status = c.out.status;
     HIPCHK(rq_final_launch(fa, c.B, s));
     return RQ_OK;
 }
 
+// The stream's workspace for a filtered call that runs no scan (rq_filter.hip: gather route, empty filter): bpad prepared-query
+// slots and cand_elems candidate keys; the stream's last call then has no bin records.
+int filter_workspace(rq_index* idx, hipStream_t s, int bpad, size_t cand_elems, const QuerySet** qs, uint64_t** cand) {
+    if (idx->ctx.find(s) == idx->ctx.end() && idx->ctx.size() >= RQ_MAX_STREAM_CTX)
+        if (int r = release_contexts(idx, nullptr)) return r;
+    StreamCtx& cx = idx->ctx[s];
+    Workspace& w = cx.w[0];
+    if (bpad > 0)
+        if (int r = ensure_ws(w, bpad, 64, 1, cand_elems)) return r;
+    set_records(cx, nullptr, 0, 0, 0);
+    *qs = &w.qs; *cand = w.cand;
+    return RQ_OK;
+}
+
 // One pass of the pipeline for B queries.  nb < 0: exact scan (every bin re-scored, no corpus scan).  flags: CallFlags (rq_index.h).
-int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags) {
+int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags,
+                 const rq_filter* filt) {
     if (idx->n == 0) {
         if (auto it = idx->ctx.find(s); it != idx->ctx.end()) set_records(it->second, nullptr, 0, 0, 0);
         return fill_empty(B, k, out, s);
@@ -481,6 +504,7 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
         use8 = scan8_usable(idx, B, k);
     }
     Call c{d_q, B, k, metric, out, s};
+    c.filt = filt;
     if (int r = plan_call(idx, B, k, metric, nb, use8, flags, &c.p)) return r;
     const CallPlan& p = c.p;
     // Workspaces are kept per caller stream.  A caller that keeps creating streams (torch hands out a pool of 32) would
@@ -508,6 +532,10 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
     if (int r = ensure_ws(w, c.pair ? 128 : p.bpad, p.exact ? 64 : p.stride, p.exact ? 1 : p.m, (size_t)(c.pair ? 128 : B) * (size_t)p.ncand)) return r;
     c.scale = idx->inv_norm;
     if (metric == RQ_METRIC_IP) { if (int r = ensure_ones(idx, s)) return r; c.scale = idx->ones; }
+    if (filt) {   // excluded rows get a NaN scale, like pad rows: no scan form tests a row's validity
+        if (int r = ensure_filter_scale(idx, filt, metric, s)) return r;
+        c.scale = filt->scale[metric];
+    }
 
     // counter protocol of the tail kernel: rowcount/done/ovf are zero on entry and the kernel leaves them zero
     if (p.fast && !w.counters_zero) {
@@ -556,7 +584,7 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
 }
 
 // ---- entry points -------------------------------------------------------------------------------
-static int check_search_args(const rq_index* idx, const void* q, int B, int k, int metric, const void* sc, const void* rows) {
+int check_search_args(const rq_index* idx, const void* q, int B, int k, int metric, const void* sc, const void* rows) {
     if (!idx || !q || !sc || !rows) return set_err(RQ_EINVAL, "null argument");
     if (B < 1 || B > 65535) return set_err(RQ_EINVAL, "B %d outside 1..65535", B);
     if (k < 1 || k > RQ_MAX_K) return set_err(RQ_EINVAL, "k %d outside 1..%d", k, RQ_MAX_K);
@@ -631,17 +659,22 @@ extern "C" int rq_search_fixup_device(rq_index* idx, const float* d_queries, int
     if (!d_status) return set_err(RQ_EINVAL, "d_status is required");
     if (!idx->shards.empty()) return set_err(RQ_EUNSUPPORTED, "device-pointer searches on a multi-device index: use rq_search (host buffers), or one index per device");
     RQ_ON_DEVICE(idx);
-    hipStream_t s = (hipStream_t)stream;
+    return fixup_ladder(idx, nullptr, d_queries, B, k, metric, d_scores, d_rows, d_keys, d_status, (hipStream_t)stream);
+}
+
+int fixup_ladder(rq_index* idx, const rq_filter* filt, const float* d_queries, int B, int k, int metric, float* d_scores,
+                 int64_t* d_rows, uint64_t* d_keys, int* d_status, hipStream_t s) {
     if (int r = flush_tails(idx, s)) return r;
     std::vector<int> st((size_t)B);
     HIPCHK(hipMemcpyAsync(st.data(), d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     std::vector<int> bad;
     for (int q = 0; q < B; ++q) if (st[q] != 0) bad.push_back(q);
-    scan8_account(idx, k, B, (int)bad.size());
+    if (!filt) scan8_account(idx, k, B, (int)bad.size());   // (filtered calls never touch the int8 image or its ladder)
     if (bad.empty()) return 0;
     const int repaired = (int)bad.size();
     idx->repaired_total += repaired;
+    if (filt) idx->filter_repaired += repaired;
     Workspace& w = idx->ctx[s].w[0];
     const int fb = (int)bad.size();
     if (fb > w.fix_bcap || k > w.fix_k) {
@@ -656,7 +689,8 @@ extern "C" int rq_search_fixup_device(rq_index* idx, const float* d_queries, int
     // ladder: (queries that came from the int8 scan: the fp16 scan, whose threshold certifies by construction,) 4x wider
     // candidate set, then the full fp64 scan
     const int nb1 = std::min(RQ_NB_MAX, 4 * nb_default(idx, k));
-    const bool from8 = idx->last_use8 && idx->x8 && idx->scan8;
+    const bool from8 = !filt && idx->last_use8 && idx->x8 && idx->scan8;
+    const unsigned allow8 = filt ? 0u : (unsigned)CALL_ALLOW8;
     const SearchOut fix_out{w.fix_scores, w.fix_rows, w.fix_keys, w.fix_status};
     for (int level = from8 ? -1 : 0; level < 2 && !bad.empty(); ++level) {
         const int nbq = (int)bad.size();
@@ -664,11 +698,11 @@ extern "C" int rq_search_fixup_device(rq_index* idx, const float* d_queries, int
             HIPCHK(hipMemcpyAsync(w.fix_q + (size_t)i * idx->dim, d_queries + (size_t)bad[i] * idx->dim, (size_t)idx->dim * sizeof(float),
                                   hipMemcpyDeviceToDevice, s));
         if (level < 0) {
-            if (int r = run_pipeline(idx, w.fix_q, nbq, k, metric, nb_default(idx, k), fix_out, s, 0)) return r;
+            if (int r = run_pipeline(idx, w.fix_q, nbq, k, metric, nb_default(idx, k), fix_out, s, 0, filt)) return r;
         } else if (level == 0) {
             idx->t.widened += nbq;
             // (the fast tail fails only when its candidate lists overflow: the wider pass uses the generic sorted tail)
-            if (int r = run_pipeline(idx, w.fix_q, nbq, k, metric, nb1, fix_out, s, CALL_FORCE_GENERIC | CALL_ALLOW8)) return r;
+            if (int r = run_pipeline(idx, w.fix_q, nbq, k, metric, nb1, fix_out, s, CALL_FORCE_GENERIC | allow8, filt)) return r;
         } else {
             idx->t.exact_scans += nbq;
             // bound the candidate memory: a few queries per exact pass
@@ -677,7 +711,7 @@ extern "C" int rq_search_fixup_device(rq_index* idx, const float* d_queries, int
             for (int off = 0; off < nbq; off += group) {
                 const int g = std::min(group, nbq - off);
                 if (int r = run_pipeline(idx, w.fix_q + (size_t)off * idx->dim, g, k, metric, -1,
-                                         {w.fix_scores + (size_t)off * k, w.fix_rows + (size_t)off * k, w.fix_keys + (size_t)off * k, w.fix_status + off}, s, CALL_ALLOW8))
+                                         {w.fix_scores + (size_t)off * k, w.fix_rows + (size_t)off * k, w.fix_keys + (size_t)off * k, w.fix_status + off}, s, allow8, filt))
                     return r;
             }
         }

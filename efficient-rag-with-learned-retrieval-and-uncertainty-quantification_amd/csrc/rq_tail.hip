@@ -26,6 +26,13 @@ __global__ __launch_bounds__(256) void rq_tail_kernel(RqTailArgs a) {
     __shared__ RqTailLds lds;
     rq_tail_body<NV, DP>(a, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, lds);
 }
+// The tail of a filtered search (include/rq.h rq_search_filtered): the same workgroups with the filter as a second argument.
+template <int NV, int DP, bool FILT>
+__global__ __launch_bounds__(256) void rq_tail_kernel(RqTailArgs a, RqFilterArgs f) {
+    static_assert(FILT, "the unfiltered tail takes RqTailArgs alone");
+    __shared__ RqTailLds lds;
+    rq_tail_body<NV, DP, true>(a, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, lds, &f);
+}
 
 template <int NV, int DP = RQ_DPAD>
 static hipError_t rq_tail_launch_nv(const RqTailArgs& a, int B, hipStream_t stream) {
@@ -40,6 +47,22 @@ hipError_t rq_tail_launch(const RqTailArgs& a, int B, hipStream_t stream) {
     if (a.dpad == 384) return rq_tail_small_chunks(a.nbins, B) ? rq_tail_launch_nv<1, 384>(a, B, stream) : rq_tail_launch_nv<4, 384>(a, B, stream);
     if (a.dpad != RQ_DPAD) return hipErrorInvalidValue;
     return rq_tail_small_chunks(a.nbins, B) ? rq_tail_launch_nv<1>(a, B, stream) : rq_tail_launch_nv<4>(a, B, stream);
+}
+
+template <int NV, int DP>
+static hipError_t rq_tail_filtered_launch_nv(const RqTailArgs& a, const RqFilterArgs& f, int B, hipStream_t stream) {
+    const int64_t chunks = (a.nbins + 512 * NV - 1) / (512 * NV);
+    if (chunks < 1 || chunks > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((rq_tail_kernel<NV, DP, true>), dim3((unsigned)chunks, B), dim3(256), 0, stream, a, f);
+    return hipGetLastError();
+}
+
+hipError_t rq_tail_filtered_launch(const RqTailArgs& a, const RqFilterArgs& f, int B, hipStream_t stream) {
+    if (a.m < 1 || a.m > RQ_FAST_MAX_M || a.k < 1 || a.k > RQ_FAST_MAX_K || !f.bits || !f.first || f.na < 1 || a.m > f.na) return hipErrorInvalidValue;
+    const bool small = rq_tail_small_chunks(a.nbins, B);
+    if (a.dpad == 384) return small ? rq_tail_filtered_launch_nv<1, 384>(a, f, B, stream) : rq_tail_filtered_launch_nv<4, 384>(a, f, B, stream);
+    if (a.dpad != RQ_DPAD) return hipErrorInvalidValue;
+    return small ? rq_tail_filtered_launch_nv<1, RQ_DPAD>(a, f, B, stream) : rq_tail_filtered_launch_nv<4, RQ_DPAD>(a, f, B, stream);
 }
 
 // Tails of a scanned-ahead pair (both batches' records come from one 128-query pass) + the preparation of the next batch.

@@ -27,8 +27,13 @@ template <int N> struct RqInt { static constexpr int value = N; };
 // DP: stored row length in elements (768 or 384, rq_index.h dpad): the row stride, and how much of a row the re-score reads.  The
 //     elements a 384-element row lacks are zeros in the 768-element layout: they add nothing to the fp64 sums, whose order is the
 //     same, so both layouts give the same bits.
-template <int NV, int DP = RQ_DPAD>
-__device__ __forceinline__ void rq_tail_body(const RqTailArgs& a, const int chunk, const int q, const int nchunks, RqTailLds& L) {
+// FILT: a filtered search (rq_kernels.h RqFilterArgs `f`; a.m = min(k, allowed rows) comes from the host).  A row job's key stays 0
+//     unless the row's bit is set (looked up where the job's row is formed, before the row loads: the re-score keeps the
+//     unfiltered kernel's registers) -- an excluded row that a 64-row job touches is dropped before publication, so it can neither
+//     enter the top-k nor count as a candidate -- and the final step knows how many rows can be returned (rq_final_body.h).
+template <int NV, int DP = RQ_DPAD, bool FILT = false>
+__device__ __forceinline__ void rq_tail_body(const RqTailArgs& a, const int chunk, const int q, const int nchunks, RqTailLds& L,
+                                             const RqFilterArgs* f = nullptr) {
     float* const qs = L.qs;
     double* const qpart = L.qpart;
     int* const hits = L.hits;
@@ -196,6 +201,8 @@ __device__ __forceinline__ void rq_tail_body(const RqTailArgs& a, const int chun
                 const int job = jobs[live ? jb : 0];
                 pos[u] = (live && base + jb < RQ_CAND_CAP) ? base + jb : -1;   // -1: nothing stored (padding or list full)
                 rows[u] = (int64_t)hits[job >> 6] * RQ_BIN_ROWS + (job & 63);
+                // a filtered search: an excluded row is treated like a row beyond the shard's end from here on (its key stays 0)
+                if constexpr (FILT) { if (rows[u] < a.n_rows && !((f->bits[rows[u] >> 5] >> (rows[u] & 31)) & 1u)) rows[u] = a.n_rows; }
                 const int64_t rr = rows[u] < a.n_rows ? rows[u] : 0;
                 rn[u] = a.rownorm64[rr];
                 const char* r = xb + rr * (DP * 2) + sub * 16;
@@ -299,5 +306,5 @@ __device__ __forceinline__ void rq_tail_body(const RqTailArgs& a, const int chun
     c.max_row_norm = a.max_row_norm; c.k = a.k; c.row_offset = a.row_offset; c.n_rows = a.n_rows;
     c.out_scores = a.out_scores + (int64_t)q * a.k; c.out_rows = a.out_rows + (int64_t)q * a.k;
     c.out_keys = a.out_keys ? a.out_keys + (int64_t)q * a.k : nullptr; c.out_status = a.out_status + q;
-    rq_final_body(c, total_s, ovf_s, T, qn, L.flds);
+    rq_final_body<FILT>(c, total_s, ovf_s, T, qn, L.flds, f);
 }

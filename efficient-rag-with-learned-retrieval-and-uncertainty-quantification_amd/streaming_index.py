@@ -238,6 +238,16 @@ class BM25Index:
             scores[r] += c
         return scores
 
+    def _row_of_id(self) -> Dict[str, int]:
+        """id -> row (first occurrence), rebuilt when documents were added"""
+        c = self.__dict__.get("_row_of_cache")
+        if c is None or c[0] != len(self.doc_ids):
+            table: Dict[str, int] = {}
+            for i, d in enumerate(self.doc_ids):
+                table.setdefault(d, i)
+            c = self.__dict__["_row_of_cache"] = (len(self.doc_ids), table)
+        return c[1]
+
     @staticmethod
     def _select_topk(scores: np.ndarray, top_k: int) -> np.ndarray:
         """Rows of the reference's selection (:172-177: argsort, reversed, first top_k, score > 0 only) without sorting the whole
@@ -256,9 +266,18 @@ class BM25Index:
 
     SINGLE_NATIVE_AFTER: Optional[int] = 4   # one-query searches in a row over an unchanged corpus before they pay for the batch scorer's arrays (None: never)
 
-    def search(self, query: str, top_k: int = 10) -> List[Tuple[str, float]]:
+    def search(self, query: str, top_k: int = 10, *, allowed_ids=None) -> List[Tuple[str, float]]:
         if self.bm25 is None or not self.doc_ids:
             return []
+        if allowed_ids is not None:
+            # restricted to a set of ids (extension, the `where` of a Chroma query on the sparse side): the scores of every other
+            # passage are masked to 0 before the reference's selection, which keeps positive scores only.  Unknown ids are ignored.
+            scores = self.get_scores(self._tokenize(query))
+            keep = np.zeros(len(scores), dtype=bool)
+            rows = [r for r in (self._row_of_id().get(d) for d in allowed_ids) if r is not None]
+            keep[rows] = True
+            scores = np.where(keep, scores, 0.0)
+            return [(self.doc_ids[i], float(scores[i])) for i in self._select_topk(scores, top_k).tolist()]
         # One query per call is the reference's evaluation loop (experiments/run_evaluation.py:157-206).  The path below allocates and
         # selects over one float64 per PASSAGE per query (20 ms at 1M passages); the batch scorer (librq_bm25.so) walks the same posting
         # lists in 3.4 ms -- same additions, same bits -- but needs the CSR form of the index, which every add invalidates (2.3 s to
@@ -749,12 +768,36 @@ class DenseIndex:
             if gc_was_on:
                 gc.enable()
 
-    def search_vectors(self, vectors: np.ndarray, top_k: int = 10) -> List[List[Tuple[str, float, str]]]:
+    # ---- filtered searches (extension: the `where` of reference :355-359's collection.query) -------------------------
+    def make_filter(self, ids) -> "_native.RowFilter":
+        """A reusable filter that restricts searches to the passages with these ids (`allowed_ids=` accepts it as well as the ids
+        themselves).  Unknown ids are ignored.  It describes the collection as it is now: adding documents makes it stale."""
+        if self._index is None or not hasattr(self._index, "make_filter"):
+            raise _native.RqError("filtered searches need a single-device index that holds rows")
+        rows = [r for r in (self._row_of.get(d) for d in ids) if r is not None]
+        return self._index.make_filter(np.asarray(rows, dtype=np.int64))
+
+    def _filtered_rows(self, vectors: np.ndarray, top_k: int, allowed_ids) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores, rows) of the top_k over the allowed passages only: k = min(top_k, rows of the index); entries beyond the allowed
+        count are (0.0, -1).  Ids (rather than a `make_filter` result) cost a filter's whole set-up and tear-down per call: O(rows) on the
+        host, two device allocations, the masked scale, a device synchronisation -- reuse a filter for repeated questions."""
+        k = min(int(top_k), len(self._ids), _native.MAX_K)
+        own = not isinstance(allowed_ids, _native.RowFilter)
+        flt = self.make_filter(allowed_ids) if own else allowed_ids
+        try:
+            return self._index.search(vectors, k, self.metric, row_filter=flt)
+        finally:
+            if own:
+                flt.close()
+
+    def search_vectors(self, vectors: np.ndarray, top_k: int = 10, *, allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
         vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
         if self._index is None or len(self._ids) == 0 or top_k <= 0:
             return [[] for _ in range(vectors.shape[0])]
         if vectors.shape[1] != self.dim:
             raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
+        if allowed_ids is not None:
+            return self._assemble(*self._filtered_rows(vectors, top_k, allowed_ids))
         k = min(int(top_k), len(self._ids), _native.MAX_K)
         scores, rows = self._index.search(vectors, k, self.metric)
         return self._assemble(scores, rows)
@@ -803,12 +846,15 @@ class DenseIndex:
         scores = host[2 * B * k: 3 * B * k].view(np.float32).reshape(B, k)
         return scores, rows
 
-    def search_rows_batch(self, queries: Sequence[str], top_k: int = 10) -> Tuple[np.ndarray, np.ndarray]:
+    def search_rows_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
         """`search_batch` without the (doc_id, score, text) tuples: (scores float32 [B][k], rows int64 [B][k], -1 padded; row r is
-        `self._ids[r]`), k = min(top_k, len(self)).  What HybridRetriever's batched fusion consumes (extension)."""
+        `self._ids[r]`), k = min(top_k, len(self)).  What HybridRetriever's batched fusion consumes (extension).
+        `allowed_ids` (ids or a `make_filter` result): only those passages are ranked; the queries then take the host path."""
         B = len(queries)
         if self._index is None or len(self._ids) == 0 or top_k <= 0 or B == 0:
             return np.zeros((B, 0), np.float32), np.zeros((B, 0), np.int64)
+        if allowed_ids is not None:
+            return self._filtered_rows(self._embed_matrix(list(queries)), top_k, allowed_ids)
         if hasattr(self.embedder, "embed_device"):
             try:
                 d_q = self.embedder.embed_device(list(queries))
@@ -820,9 +866,11 @@ class DenseIndex:
         k = min(int(top_k), len(self._ids), _native.MAX_K)
         return self._index.search(self._embed_matrix(list(queries)), k, self.metric)
 
-    def search_batch(self, queries: Sequence[str], top_k: int = 10) -> List[List[Tuple[str, float, str]]]:
+    def search_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
         if not queries:
             return []
+        if allowed_ids is not None:   # (ids or a `make_filter` result: only those passages are ranked)
+            return self.search_vectors(self._embed_matrix(list(queries)), top_k, allowed_ids=allowed_ids)
         # an embedder that can leave its output in HBM (embedders.NomicBertEmbedder.embed_device) feeds the search directly: no
         # device -> host -> numpy -> pinned -> device round trip of the query matrix
         if hasattr(self.embedder, "embed_device") and self._index is not None and len(self._ids):
@@ -835,8 +883,11 @@ class DenseIndex:
                 return self.search_device_vectors(d_q, top_k)
         return self.search_vectors(self._embed_matrix(list(queries)), top_k)
 
-    def search(self, query: str, top_k: int = 10) -> List[Tuple[str, float, str]]:
-        """List of (doc_id, score, text), best first; score = cosine similarity (= 1 - Chroma distance)."""
+    def search(self, query: str, top_k: int = 10, *, allowed_ids=None) -> List[Tuple[str, float, str]]:
+        """List of (doc_id, score, text), best first; score = cosine similarity (= 1 - Chroma distance).  `allowed_ids` (keyword-only
+        extension: ids, or a `make_filter` result for reuse) restricts the ranking to those passages, like a Chroma `where`."""
+        if allowed_ids is not None:
+            return self.search_batch([query], top_k, allowed_ids=allowed_ids)[0]
         return self.search_batch([query], top_k)[0]
 
     def __len__(self) -> int:
@@ -934,14 +985,20 @@ class HybridRetriever:
         stats["total_documents"] = len(self.documents)
         return stats
 
-    def bm25_search(self, query: str, top_k: int = 20) -> List[Tuple[str, float]]:
+    # `allowed_ids` (keyword-only extension on the per-query calls): only passages with these ids are ranked, on both sides -- the
+    # `where` of a Chroma query.  The sparse side needs the ids themselves; the dense side also takes a DenseIndex.make_filter result.
+    def bm25_search(self, query: str, top_k: int = 20, *, allowed_ids=None) -> List[Tuple[str, float]]:
         if self.bm25_index is None:
             return []
+        if allowed_ids is not None:
+            return self.bm25_index.search(query, top_k, allowed_ids=allowed_ids)
         return self.bm25_index.search(query, top_k)
 
-    def dense_search(self, query: str, top_k: int = 20) -> List[Tuple[str, float]]:
+    def dense_search(self, query: str, top_k: int = 20, *, allowed_ids=None) -> List[Tuple[str, float]]:
         if self.dense_index is None:
             return []
+        if allowed_ids is not None:
+            return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids)]
         return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k)]
 
     def dense_search_batch(self, queries: Sequence[str], top_k: int = 20) -> List[List[Tuple[str, float]]]:
@@ -981,12 +1038,16 @@ class HybridRetriever:
             out.append(RetrievalResult(doc_id=doc_id, text=doc.text, bm25_score=bs, dense_score=ds, hybrid_score=hs, title=doc.title, metadata=doc.metadata))
         return out
 
-    def hybrid_search(self, query: str, top_k: int = 10, retrieval_pool_size: int = 50) -> List[RetrievalResult]:
+    def hybrid_search(self, query: str, top_k: int = 10, retrieval_pool_size: int = 50, *, allowed_ids=None) -> List[RetrievalResult]:
+        if allowed_ids is not None:
+            allowed_ids = list(allowed_ids)      # (walked twice)
+            return self._fuse(self.bm25_search(query, retrieval_pool_size, allowed_ids=allowed_ids),
+                              self.dense_search(query, retrieval_pool_size, allowed_ids=allowed_ids), top_k)
         return self._fuse(self.bm25_search(query, retrieval_pool_size), self.dense_search(query, retrieval_pool_size), top_k)
 
     def hybrid_search_batch(self, queries: Sequence[str], top_k: int = 10, retrieval_pool_size: int = 50) -> List[List[RetrievalResult]]:
         """All dense pools from one GPU batch, all BM25 pools from one pass over the posting lists on the host cores (librq_bm25.so);
-        fusion per query."""
+        fusion per query.  (`allowed_ids` is an extension of the per-query calls only: the batch fusions are not extended.)"""
         fused = self._fuse_batch_rows(queries, top_k, retrieval_pool_size)
         if fused is not None:
             ids, b, de, hy, count = fused
@@ -1027,14 +1088,17 @@ class HybridRetriever:
             texts += [""] * pad
         return bm25_scores, dense_scores, doc_ids, texts
 
-    def get_scores_for_router(self, query: str, num_passages: int = 20, *, retrieval_pool_size: int = 50
+    def get_scores_for_router(self, query: str, num_passages: int = 20, *, retrieval_pool_size: int = 50, allowed_ids=None
                               ) -> Tuple[List[float], List[float], List[str], List[str]]:
         """Reference :525-557 (its pools are always 50, :537); `retrieval_pool_size` is a keyword-only extension for
-        BASELINE.json configs[4] (top-100 pools)."""
+        BASELINE.json configs[4] (top-100 pools), `allowed_ids` restricts both pools to those passages."""
+        if allowed_ids is not None:
+            return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size, allowed_ids=allowed_ids),
+                                       num_passages)
         return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size), num_passages)
 
     def get_scores_for_router_batch(self, queries: Sequence[str], num_passages: int = 20, *, retrieval_pool_size: int = 50):
-        """`[get_scores_for_router(q, ...) for q in queries]` with the pools of the whole batch computed at once.  When both sides are
+        """`[get_scores_for_router(q, ...) for q in queries]` (without `allowed_ids`: the batch fusions are not extended) with the pools of the whole batch computed at once.  When both sides are
         this module's own indexes the fusion itself runs on the whole batch in row space (`_fuse_batch_rows`); otherwise per query on the
         fused columns (no RetrievalResult objects in between)."""
         fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size)

@@ -137,6 +137,47 @@ int rq_search_fixup_device(rq_index* idx, const float* d_queries, int B, int k, 
 int rq_merge_keys_device(const uint64_t* d_keys_in, int n_per_query, int B, int k, float* d_scores, int64_t* d_rows,
                          uint64_t* d_keys_out, void* stream);
 
+/* ---- filtered searches: the top-k over an allowed set of rows (the `where` of the collection.query this backend replaces,
+ * reference rag_uq/streaming_index.py:355-359) --------------------------------------------------------------------------
+ * A filter is a bitmap over the LOCAL rows of one single-device index: bit r % 32 of word r / 32 set = row r is allowed (local:
+ * without row_offset; outputs still carry row_offset + row).  n_rows must equal rq_index_size (bits beyond it are ignored).  A
+ * filter belongs to its index and to that size: after an append every call that takes it returns RQ_EINVAL ("stale filter"), as
+ * does a filter of another index.  Creation blocks; the bookkeeping is done on the host from the bitmap (the device form copies
+ * its n_rows / 8 bytes back once): the allowed count, the first RQ_MAX_K allowed rows, which bins hold an allowed row.  NULL on
+ * error (rq_last_error); RQ_EUNSUPPORTED on a multi-device index, as the *_device calls (a striped filter is not built).
+ * Memory: n_rows / 8 bytes of HBM, + 4 n_rows bytes per metric once a search has scanned with it (the masked row scales), + 4 bytes
+ * per allowed row once a search has taken the gather route; n_rows / 8 + n_rows / 16 bytes on the host.
+ * rq_index_destroy frees the filters it still owns: a filter must not be used, or destroyed, after its index. */
+typedef struct rq_filter rq_filter;
+rq_filter* rq_filter_create(rq_index* idx, const uint32_t* bits, int64_t n_rows);                        /* host bitmap */
+rq_filter* rq_filter_create_device(rq_index* idx, const uint32_t* d_bits, int64_t n_rows, void* stream);  /* device bitmap, complete on `stream` */
+int64_t rq_filter_count(const rq_filter* f);                                                             /* allowed rows */
+void rq_filter_destroy(rq_filter* f);
+/* rq_search / rq_search_device / rq_search_fixup_device over the allowed rows only.  Score definition as above with the top-k
+ * taken over the allowed rows in the canonical order (score descending, then row ascending); k_eff = min(k, allowed rows), missing
+ * entries (0.0, -1); a zero-norm query returns the first k_eff allowed rows with score 0.  Results are exact and never depend on
+ * the route taken.
+ * A filtered call behaves like a "pipeline" = 0 call: its results are complete in stream order, and it first completes whatever
+ * `stream` still defers (a fused tail, a scanned-ahead pair, a hint), as rq_search_fixup_device does.  Not extended:
+ * rq_search_train_device, hints, "scan_ahead", "pipeline" 1 and 2.  Filtered calls never touch the int8 image ("scan8_used" and
+ * its ladder stay as they are), and their scans keep to the selection forms that honour a NaN row scale: "epi" = 0 and
+ * "wide_batch" = 2 are ignored by a filtered call (it runs "epi" = 1 and the default 128-query pass).
+ * Outputs of rq_search_filtered_device are repaired with rq_search_fixup_filtered_device and the SAME filter only: the unfiltered
+ * rq_search_fixup_device would replace every uncertified query of theirs with unfiltered results.
+ * Routes (csrc/rq_filter_plan.h), tried in this order: no row allowed -> padding; GATHER: exactly the allowed rows are re-scored
+ * in fp64 (cost grows with B x allowed rows, not with the shard) -- taken when B x allowed <= rows and 4 x allowed <= rows (measured), or when the allowed rows
+ * sit in fewer than two bins per wanted bin; SCAN: the usual scan passes over row scales in which excluded rows are NaN, a tail
+ * that drops excluded rows, the same certificate -- only when enough of the tail's partitions hold an allowed row for its
+ * threshold to narrow; else gather when at most a quarter of the rows is allowed, else EXACT: the fp64 scan of the shard.
+ * Options: "filter_route" (-1 = that rule (default), 1 = gather, 2 = scan, 3 = exact: forces a route, for tests and A/B);
+ * read-only "filter_route_last" (the route the last filtered call took: 0 = no row allowed, 1..3, -1 = none yet) and
+ * "filter_repaired" (queries of filtered calls that came back uncertified and were repaired). */
+int rq_search_filtered(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int metric, float* out_scores, int64_t* out_rows);
+int rq_search_filtered_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int metric, float* d_scores,
+                              int64_t* d_rows, uint64_t* d_keys, int* d_status, void* stream);
+int rq_search_fixup_filtered_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int metric, float* d_scores,
+                                    int64_t* d_rows, uint64_t* d_keys, int* d_status, void* stream);
+
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
  * "wg_per_cu", "nt" (non-temporal corpus loads: 0, 1, -1 = auto), "slack_bins" (extra bins beyond k, -1 = auto),
