@@ -68,6 +68,9 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_fixup_filtered_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_mmr_select_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "rq_search_mmr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int]),
     "rq_nb_rope_table_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
@@ -316,6 +319,44 @@ class NativeIndex:
         return _check(self._lib.rq_search_fixup_device(self._h, _ptr(d_queries), int(B), int(k), int(metric), _ptr(d_scores),
                                                        _ptr(d_rows), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)),
                       "rq_search_fixup_device")
+
+    # -- diversified search (include/rq.h "diversified search") --------------------------------------
+    @staticmethod
+    def _check_mmr(k: int, m: int, lambda_mult: float, what: str) -> None:
+        if not (isinstance(lambda_mult, (int, float, np.floating, np.integer)) and 0.0 <= float(lambda_mult) <= 1.0):   # (NaN fails)
+            raise ValueError(f"lambda_mult must lie within [0, 1], got {lambda_mult!r}")
+        if not 1 <= int(m) <= MAX_K:
+            raise ValueError(f"{what} {m} outside 1..{MAX_K}")
+        if not 1 <= int(k) <= int(m):
+            raise ValueError(f"k {k} outside 1..{what} = {m}")
+
+    def search_mmr(self, queries: np.ndarray, k: int, fetch_k: int, lambda_mult: float = 0.5, metric: int = METRIC_COSINE, *,
+                   row_filter: Optional[RowFilter] = None, return_mmr: bool = False):
+        """k of the exact top fetch_k rows per query by greedy maximal marginal relevance (include/rq.h rq_search_mmr): (scores, rows)
+        in selection order, the scores being the rows' own search scores; return_mmr adds the value v of every pick."""
+        self._check_mmr(k, fetch_k, lambda_mult, "fetch_k")
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [B][{self.dim}] float32 queries, got {q.shape}")
+        B = q.shape[0]
+        scores = np.empty((B, int(k)), dtype=np.float32)
+        rows = np.empty((B, int(k)), dtype=np.int64)
+        mmr = np.empty((B, int(k)), dtype=np.float32) if return_mmr else None
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        _check(self._lib.rq_search_mmr(self._h, flt, _ptr(q), B, int(k), int(fetch_k), float(lambda_mult), int(metric), _ptr(scores), _ptr(rows),
+                                       _ptr(mmr)), "rq_search_mmr")
+        return (scores, rows, mmr) if return_mmr else (scores, rows)
+
+    def mmr_select_device(self, d_cand_rows, d_cand_rel, B: int, m: int, k: int, lambda_mult: float, metric: int, d_scores, d_rows, d_mmr=None,
+                          stream: int = 0) -> None:
+        """Asynchronous selection over a caller's candidates [B][m] in device memory (include/rq.h rq_mmr_select_device)."""
+        self._check_mmr(k, m, lambda_mult, "m")
+        if int(B) < 1:
+            raise ValueError(f"B {B} must be at least 1")
+        _check(self._lib.rq_mmr_select_device(self._h, _ptr(d_cand_rows), _ptr(d_cand_rel), int(B), int(m), int(k), float(lambda_mult), int(metric),
+                                              _ptr(d_scores), _ptr(d_rows), _ptr(d_mmr), C.c_void_p(stream)), "rq_mmr_select_device")
 
     def search_hint_next_device(self, d_next_queries, B: int, stream: int = 0) -> None:
         """Announce the queries of the NEXT search_device call on `stream` (include/rq.h: rq_search_hint_next_device)."""

@@ -9,6 +9,7 @@
 // excluded rows' keys emptied.  Replaces the `where` restriction of the collection.query of reference
 // rag_uq/streaming_index.py:355-359.
 #include "rq_filter_plan.h"
+#include "rq_rowdot.h"
 
 // ---- kernels ------------------------------------------------------------------------------------
 __device__ __forceinline__ bool rq_filter_bit(const uint32_t* bits, int64_t row) { return (bits[row >> 5] >> (row & 31)) & 1u; }
@@ -42,7 +43,8 @@ hipError_t rq_mask_keys_launch(uint64_t* cand, int64_t n, const uint32_t* bits, 
 // grid (B, ceil(nlist / 256)): query = blockIdx.x, so that the workgroups in flight together re-score the SAME 256 rows for
 // different queries (the rows come from the caches after their first reader); 256 threads.  The arithmetic of one row is
 // rq_tail_body.h phase C's: 16 lanes per row (sub = lane & 15 owns elements pp * 128 + 8 * sub + e), a wave takes 8 rows per
-// round, fp64 products in element order, xor butterfly over the 16 lanes -- the same summation order, hence the same bits.
+// round, fp64 products in element order, xor butterfly over the 16 lanes -- the same summation order, hence the same bits
+// (rq_rowdot.h, shared with rq_mmr.hip).
 template <int DP>
 __global__ __launch_bounds__(256) void rq_gather_score_kernel(RqGatherArgs a) {
     static_assert(DP == 384 || DP == RQ_DPAD, "stored row length");
@@ -74,21 +76,11 @@ __global__ __launch_bounds__(256) void rq_gather_score_kernel(RqGatherArgs a) {
 #pragma unroll
             for (int pp = 0; pp < NP; ++pp) xv[u][pp] = *(const rq_half8*)(r + pp * 256);
         }
-        double dot[2] = {0.0, 0.0};
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp) {
-            const float4 qlo = *(const float4*)&qs[pp * 128 + 8 * sub], qhi = *(const float4*)&qs[pp * 128 + 8 * sub + 4];
-            const float qq[8] = {qlo.x, qlo.y, qlo.z, qlo.w, qhi.x, qhi.y, qhi.z, qhi.w};
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) dot[u] += (double)qq[e] * (double)(float)xv[u][pp][e];
-        }
+        double dot[2];
+        rq_rowdot16<NP, 2>(xv, qs, sub, dot);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            double d = dot[u];
-#pragma unroll
-            for (int off = 8; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
+            const double d = dot[u];
             if (sub == 0 && lv[u]) {
                 double sc = d;
                 if (a.metric == 0) sc = d / (qn * rn[u] + 1e-30);
@@ -225,7 +217,7 @@ static int ensure_filter_list(rq_filter* f) {
 }
 
 // ---- searches -------------------------------------------------------------------------------------
-static int check_filter(const rq_index* idx, const rq_filter* f) {
+int check_filter(const rq_index* idx, const rq_filter* f) {
     if (!f) return set_err(RQ_EINVAL, "null filter");
     if (!idx->shards.empty()) return set_err(RQ_EUNSUPPORTED, "filtered searches on a multi-device index: use one index per device");
     if (f->idx != idx) return set_err(RQ_EINVAL, "the filter belongs to another index");
@@ -270,7 +262,7 @@ static int gather_route(rq_index* idx, rq_filter* f, const float* d_q, int B, in
     return RQ_OK;
 }
 
-static int search_filtered_device(rq_index* idx, const rq_filter* cf, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s) {
+int search_filtered_device(rq_index* idx, const rq_filter* cf, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s) {
     rq_filter* f = const_cast<rq_filter*>(cf);
     // like a "pipeline" = 0 call: whatever the stream still defers (fused tail, scanned-ahead pair, hint) is completed first
     if (int r = flush_tails(idx, s)) return r;

@@ -1,5 +1,5 @@
 // rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
-// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_scan8.hip (the int8 image and its ladder) and
+// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_scan8.hip (the int8 image and its ladder) and
 // rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard.
 // Not part of the public boundary (that is include/rq.h).
 #pragma once
@@ -207,6 +207,7 @@ struct rq_index {
     int filter_route = -1;             // option "filter_route": -1 = the rule (rq_filter_plan.h), 1 gather, 2 scan, 3 exact
     int filter_route_last = -1;        // the route the last filtered call took (0 = empty filter)
     int64_t filter_repaired = 0;       // queries of filtered calls that came back uncertified and were repaired
+    int64_t mmr_calls = 0;             // option "mmr_calls": MMR selections launched (rq_mmr.hip)
 };
 
 // Derived bound on |approximate scan score - exact score| for unit queries and cosine scaling:
@@ -262,6 +263,8 @@ RQ_INTERNAL int filter_workspace(rq_index* idx, hipStream_t s, int bpad, size_t 
 // rq_filter.hip
 RQ_INTERNAL void free_filters(rq_index* idx);   // rq_index_destroy: the filters the index still owns
 RQ_INTERNAL int ensure_filter_scale(rq_index* idx, const rq_filter* f, int metric, hipStream_t s);
+RQ_INTERNAL int check_filter(const rq_index* idx, const rq_filter* f);   // null, another index's, stale, multi-device
+RQ_INTERNAL int search_filtered_device(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s);
 RQ_INTERNAL int flush_all(rq_index* idx);   // launches every tail still waiting for a scan ("pipeline" = 2)
 RQ_INTERNAL void free_ctx(StreamCtx& c);
 // rq_scan8.hip

@@ -196,6 +196,22 @@ struct RqGatherArgs {
 #define RQ_GATHER_MAX_CHUNKS 65535   // chunks of 256 listed rows per launch (grid y); rq_gather_score_launch loops beyond
 hipError_t rq_gather_score_launch(const RqGatherArgs& a, int B, hipStream_t stream);
 
+// ---- MMR selection (rq_mmr.hip, include/rq.h rq_mmr_select_device): k of m candidate rows per query, greedily by
+// v = lambda rel - (1 - lambda) max similarity to the rows already picked; one workgroup per query ----
+struct RqMmrArgs {
+    const void* x; int dpad;      // stored rows and their length in elements (768 or 384)
+    const double* rownorm64;
+    int64_t n_rows, row_offset;   // candidates carry GLOBAL rows: row_offset + local row; anything outside the shard is absent
+    const int64_t* cand_rows;     // [B][m], -1 = absent
+    const float* cand_rel;        // [B][m] relevance, NaN = absent
+    int m, k, metric;             // 1 <= k <= m <= RQ_MAX_K
+    double lambda;
+    float* out_scores;            // [B][k] the picked candidates' relevance, unchanged
+    int64_t* out_rows;            // [B][k] global rows in selection order, -1 padded
+    float* out_mmr;               // [B][k] fp32(v) at the moment of selection, or null
+};
+hipError_t rq_mmr_launch(const RqMmrArgs& a, int B, hipStream_t stream);
+
 // Merge G sorted key lists per query (cross-shard): in [B][G*k] -> top-k scores/rows/keys.
 hipError_t rq_merge_keys_launch(const uint64_t* keys, int n_per_query, int B, int k, float* out_scores, int64_t* out_rows,
                                 uint64_t* out_keys, hipStream_t stream);

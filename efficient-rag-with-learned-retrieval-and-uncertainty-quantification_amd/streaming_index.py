@@ -802,6 +802,45 @@ class DenseIndex:
         scores, rows = self._index.search(vectors, k, self.metric)
         return self._assemble(scores, rows)
 
+    # ---- diversified searches (extension: what LangChain's max_marginal_relevance_search does on the host with the fetch_k
+    # embeddings of reference :355-359's collection.query) -----------------------------------------------------------------
+    def search_mmr_vectors(self, vectors: np.ndarray, top_k: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, *,
+                           allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
+        """`search_vectors` with the top_k chosen among the exact top fetch_k by greedy maximal marginal relevance (include/rq.h
+        rq_search_mmr): (doc_id, score, text) in SELECTION order, the score still the cosine.  lambda_mult = 1 is the plain search,
+        0 looks at diversity alone.  fetch_k is clamped to [top_k, min(len(self), MAX_K)].  The queries take the host path."""
+        vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
+        if not 0.0 <= float(lambda_mult) <= 1.0:
+            raise ValueError(f"lambda_mult must lie within [0, 1], got {lambda_mult!r}")
+        if self._index is None or len(self._ids) == 0 or top_k <= 0:
+            return [[] for _ in range(vectors.shape[0])]
+        if vectors.shape[1] != self.dim:
+            raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
+        if not hasattr(self._index, "search_mmr"):
+            raise _native.RqError("MMR searches need a single-device index")
+        limit = min(len(self._ids), _native.MAX_K)
+        k = min(int(top_k), limit)
+        fetch = min(max(int(fetch_k), k), limit)
+        if allowed_ids is None:
+            return self._assemble(*self._index.search_mmr(vectors, k, fetch, float(lambda_mult), self.metric))
+        own = not isinstance(allowed_ids, _native.RowFilter)
+        flt = self.make_filter(allowed_ids) if own else allowed_ids
+        try:
+            return self._assemble(*self._index.search_mmr(vectors, k, fetch, float(lambda_mult), self.metric, row_filter=flt))
+        finally:
+            if own:
+                flt.close()
+
+    def search_mmr_batch(self, queries: Sequence[str], top_k: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, *,
+                         allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
+        if not queries:
+            return []
+        return self.search_mmr_vectors(self._embed_matrix(list(queries)), top_k, fetch_k, lambda_mult, allowed_ids=allowed_ids)
+
+    def search_mmr(self, query: str, top_k: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, *, allowed_ids=None) -> List[Tuple[str, float, str]]:
+        """top_k passages that are relevant and not copies of each other: see `search_mmr_vectors`."""
+        return self.search_mmr_batch([query], top_k, fetch_k, lambda_mult, allowed_ids=allowed_ids)[0]
+
     def search_device_vectors(self, d_vectors, top_k: int = 10) -> List[List[Tuple[str, float, str]]]:
         """Queries that are already in HBM (a CUDA tensor [B][dim] fp32, e.g. `NomicBertEmbedder.embed_device`): searched where they
         are (rq_search_device on torch's current stream), repaired if a certificate failed, ONE device-to-host copy of rows + scores."""
@@ -1000,6 +1039,12 @@ class HybridRetriever:
         if allowed_ids is not None:
             return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids)]
         return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k)]
+
+    def dense_search_mmr(self, query: str, top_k: int = 20, fetch_k: int = 50, lambda_mult: float = 0.5, *, allowed_ids=None) -> List[Tuple[str, float]]:
+        """`dense_search` diversified: top_k of the exact top fetch_k by maximal marginal relevance, in selection order (DenseIndex.search_mmr)."""
+        if self.dense_index is None:
+            return []
+        return [(doc_id, score) for doc_id, score, _ in self.dense_index.search_mmr(query, top_k, fetch_k, lambda_mult, allowed_ids=allowed_ids)]
 
     def dense_search_batch(self, queries: Sequence[str], top_k: int = 20) -> List[List[Tuple[str, float]]]:
         if self.dense_index is None:

@@ -178,6 +178,45 @@ int rq_search_filtered_device(rq_index* idx, const rq_filter* f, const float* d_
 int rq_search_fixup_filtered_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int metric, float* d_scores,
                                     int64_t* d_rows, uint64_t* d_keys, int* d_status, void* stream);
 
+/* ---- diversified search: MMR selection over candidate rows (what a max_marginal_relevance_search(query, k, fetch_k, lambda_mult)
+ * does on the host with the fetch_k embeddings of the collection.query of reference rag_uq/streaming_index.py:355-359) ----------
+ * Greedy maximal marginal relevance: k of m candidates per query, each step taking the candidate that is most relevant and least
+ * similar to the rows already taken.  Per query: candidate positions 0..m-1, each a global row c_i and a relevance rel_i (fp32).
+ *   absent candidate: c_i = -1 or any row outside [row_offset, row_offset + rq_index_size), or a NaN rel_i.  It is never selected
+ *     and its row is never read.  Duplicates are not checked: the candidate rows must be distinct.
+ *   pair similarity: the score definition above with STORED rows on both sides: d = sum_e (double)x_i[e] * (double)x_j[e];
+ *     cosine: sim(i, j) = fp32( d / (n_i * n_j + 1e-30) ), n = the stored fp64 row norm; ip: sim(i, j) = fp32(d); a NaN sim
+ *     counts as -inf, as for every score.
+ *   penalty: pen_i (fp32) = 0 before the first pick, afterwards the maximum of sim(i, j) over the selected j.
+ *   value: v_i = lambda * (double)rel_i - (1.0 - lambda) * (double)pen_i in fp64: two products and one subtraction, each
+ *     rounded, no fused multiply-add.  A NaN v (0 x inf) counts as -inf.
+ *   step: among the present, unselected candidates the greatest v wins, the lowest position on equal v;
+ *     k_eff = min(k, present candidates) steps.
+ *   outputs, in selection order: d_rows / out_rows the global rows; d_scores / out_scores the candidate's relevance, passed through
+ *     unchanged (for a search: its cosine, so everything downstream keeps working); d_mmr / out_mmr (may be NULL) fp32(v) at the
+ *     moment of selection; entries beyond k_eff are (0.0, -1, 0.0).
+ *   Hence lambda = 1 returns the candidates in relevance order (on a search's own candidates: that search's top k), and at lambda = 0
+ *     the first pick is position 0 and every later d_mmr is -pen of the row picked.
+ * rq_mmr_select_device: asynchronous, pure selection over a caller's candidates [B][m] in device memory, any order, any relevance (a
+ *   fused hybrid score as well as a cosine).  It runs in stream order after whatever produced the candidates and defers nothing.
+ *   RQ_EINVAL unless 1 <= k <= m <= RQ_MAX_K, 1 <= B <= 65535, lambda finite and within [0, 1] (NaN included), a known metric and
+ *   non-null pointers (d_mmr aside); RQ_EUNSUPPORTED on a multi-device index; RQ_ENODEVICE as everywhere.
+ * rq_search_mmr: blocking, host buffers ([B][dim] queries; out_scores, out_rows, out_mmr [B][k]).  The exact top
+ *   min(fetch_k, rows) -- with a filter f (may be NULL): min(fetch_k, allowed rows), over the allowed rows only -- staged as
+ *   rq_search_filtered stages its call, then the selection, then the copies back.  It behaves like a "pipeline" = 0 call: whatever the
+ *   index's own stream still defers is completed first; uncertified queries are repaired with the usual ladder, so the candidates
+ *   are exact.  RQ_EINVAL unless 1 <= k <= fetch_k <= RQ_MAX_K and lambda within [0, 1]; the filter checks are those of
+ *   rq_search_filtered (another index's filter, a stale filter: RQ_EINVAL); RQ_EUNSUPPORTED on a multi-device index.
+ * The selection reads the stored rows: one rq_index from one thread at a time, as for a search, and no append while a selection is
+ *   in flight.  Memory: none kept; rq_search_mmr stages B x (fetch_k x 12 + k x 16) bytes for the call.
+ * Not extended: rq_search_train_device, hints, "pipeline" 1 and 2 (a deferred search's candidates are complete only after
+ *   rq_search_flush_device: flush, then select), multi-device indexes.
+ * Read-only option "mmr_calls": selections launched so far (both entry points). */
+int rq_mmr_select_device(rq_index* idx, const int64_t* d_cand_rows, const float* d_cand_rel, int B, int m, int k, double lambda, int metric,
+                         float* d_scores, int64_t* d_rows, float* d_mmr, void* stream);
+int rq_search_mmr(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int fetch_k, double lambda, int metric,
+                  float* out_scores, int64_t* out_rows, float* out_mmr);
+
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
  * "wg_per_cu", "nt" (non-temporal corpus loads: 0, 1, -1 = auto), "slack_bins" (extra bins beyond k, -1 = auto),
