@@ -21,6 +21,7 @@ METRIC_COSINE = 0
 METRIC_IP = 1
 MAX_DIM = 768
 MAX_K = 1024
+MAX_SCORE_ROWS = 65536
 
 
 class RqError(RuntimeError):
@@ -71,6 +72,8 @@ _SIGNATURES = {
     "rq_mmr_select_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rq_search_mmr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_score_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rq_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int]),
     "rq_nb_rope_table_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
@@ -357,6 +360,45 @@ class NativeIndex:
             raise ValueError(f"B {B} must be at least 1")
         _check(self._lib.rq_mmr_select_device(self._h, _ptr(d_cand_rows), _ptr(d_cand_rel), int(B), int(m), int(k), float(lambda_mult), int(metric),
                                               _ptr(d_scores), _ptr(d_rows), _ptr(d_mmr), C.c_void_p(stream)), "rq_mmr_select_device")
+
+    # -- scoring given rows (include/rq.h "scoring given rows") ------------------------------------------
+    @staticmethod
+    def _check_score(B: int, m: int, metric: int) -> None:
+        if not 1 <= int(B) <= 65535:
+            raise ValueError(f"B {B} outside 1..65535")
+        if not 1 <= int(m) <= MAX_SCORE_ROWS:
+            raise ValueError(f"m {m} outside 1..{MAX_SCORE_ROWS}")
+        if int(metric) not in (METRIC_COSINE, METRIC_IP):
+            raise ValueError(f"unknown metric {metric!r}")
+
+    def score_rows(self, queries: np.ndarray, rows: np.ndarray, metric: int = METRIC_COSINE) -> np.ndarray:
+        """The exact score of every (query, row) pair of one list of GLOBAL rows per query (include/rq.h rq_score_rows): float32
+        [B][m], position for position; an entry outside the index (-1 included) scores 0.0."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [B][{self.dim}] float32 queries, got {q.shape}")
+        r = np.asarray(rows)
+        if r.dtype.kind not in "iu":
+            raise ValueError(f"rows must be integers, got {r.dtype}")
+        if r.ndim == 1:
+            r = r[None, :]
+        if r.ndim != 2 or r.shape[0] != q.shape[0]:
+            raise ValueError(f"expected [{q.shape[0]}][m] rows, one list per query, got {r.shape}")
+        r = np.ascontiguousarray(r, dtype=np.int64)
+        B, m = r.shape
+        self._check_score(B, m, metric)
+        scores = np.empty((B, m), dtype=np.float32)
+        _check(self._lib.rq_score_rows(self._h, _ptr(q), B, _ptr(r), m, int(metric), _ptr(scores)), "rq_score_rows")
+        return scores
+
+    def score_rows_device(self, d_queries, B: int, d_rows, m: int, metric: int, d_scores, stream: int = 0) -> None:
+        """Asynchronous form over device memory: d_queries [B][dim] fp32, d_rows [B][m] int64, d_scores [B][m] fp32 (include/rq.h
+        rq_score_rows_device); complete in stream order."""
+        self._check_score(B, m, metric)
+        _check(self._lib.rq_score_rows_device(self._h, _ptr(d_queries), int(B), _ptr(d_rows), int(m), int(metric), _ptr(d_scores), C.c_void_p(stream)),
+               "rq_score_rows_device")
 
     def search_hint_next_device(self, d_next_queries, B: int, stream: int = 0) -> None:
         """Announce the queries of the NEXT search_device call on `stream` (include/rq.h: rq_search_hint_next_device)."""

@@ -353,6 +353,8 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
     if (s == "filter_route_last") return idx->filter_route_last;   // the route the last filtered call took (0: no row allowed; -1: none yet)
     if (s == "filter_repaired") return (double)idx->filter_repaired;   // queries of filtered calls that were repaired
     if (s == "mmr_calls") return (double)idx->mmr_calls;   // MMR selections launched (rq_mmr_select_device, rq_search_mmr)
+    if (s == "score_calls") return (double)idx->score_calls;   // scoring calls (rq_score_rows_device, rq_score_rows)
+    if (s == "score_pairs") return (double)idx->score_pairs;   // ... and the (query, row) pairs they were given: B x m each
     if (s == "repaired_queries") return (double)idx->repaired_total;   // queries rq_search_fixup_device (or the blocking rq_search) had to repair so far
     if (s == "scan8_used") return (double)idx->scan8_used;   // searches that scanned the int8 image
     if (s == "hints_used") return (double)idx->hints_used;   // searches that found their queries prepared by the launch before them

@@ -1,5 +1,5 @@
 // rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
-// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_scan8.hip (the int8 image and its ladder) and
+// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_scan8.hip (the int8 image and its ladder) and
 // rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard.
 // Not part of the public boundary (that is include/rq.h).
 #pragma once
@@ -208,6 +208,7 @@ struct rq_index {
     int filter_route_last = -1;        // the route the last filtered call took (0 = empty filter)
     int64_t filter_repaired = 0;       // queries of filtered calls that came back uncertified and were repaired
     int64_t mmr_calls = 0;             // option "mmr_calls": MMR selections launched (rq_mmr.hip)
+    int64_t score_calls = 0, score_pairs = 0;   // options "score_calls" / "score_pairs": scoring calls and their B x m pairs (rq_score.hip)
 };
 
 // Derived bound on |approximate scan score - exact score| for unit queries and cosine scaling:

@@ -212,6 +212,20 @@ struct RqMmrArgs {
 };
 hipError_t rq_mmr_launch(const RqMmrArgs& a, int B, hipStream_t stream);
 
+// ---- scoring given rows (rq_score.hip, include/rq.h rq_score_rows_device): scores[q][j] = score(query q, rows[q][j]), one list of
+// m global rows per query; grid (queries, tiles of RQ_SCORE_TILE positions) ----
+struct RqScoreArgs {
+    const void* x; int dpad;      // stored rows and their length in elements (768 or 384)
+    const double* rownorm64;
+    int64_t n_rows, row_offset;   // the lists carry GLOBAL rows: row_offset + local row; anything outside the shard is absent; n_rows >= 1
+    const float* q32;             // [queries][768] raw fp32 queries, zero padded (rq_prep_body)
+    const double* qnorm64;        // [queries]
+    const int64_t* rows;          // [queries][m]
+    int m, metric;
+    float* scores;                // [queries][m]: the score of a present entry, 0.0 for an absent one
+};
+hipError_t rq_score_rows_launch(const RqScoreArgs& a, int queries, hipStream_t stream);
+
 // Merge G sorted key lists per query (cross-shard): in [B][G*k] -> top-k scores/rows/keys.
 hipError_t rq_merge_keys_launch(const uint64_t* keys, int n_per_query, int B, int k, float* out_scores, int64_t* out_rows,
                                 uint64_t* out_keys, hipStream_t stream);

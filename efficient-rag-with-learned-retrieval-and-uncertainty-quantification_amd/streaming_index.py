@@ -238,6 +238,45 @@ class BM25Index:
             scores[r] += c
         return scores
 
+    def _score_rows_tokens(self, tokens: List[str], rows: np.ndarray) -> np.ndarray:
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        out = np.zeros(rows.size)
+        n_docs = len(self.doc_ids)
+        if n_docs == 0 or rows.size == 0:
+            return out
+        inside = (rows >= 0) & (rows < n_docs)
+        if not inside.any():
+            return out
+        idf = self._ensure_idf()
+        avgdl = self._total_len / n_docs
+        for tok in tokens:
+            post = self._post_rows.get(tok)
+            if not post:
+                continue
+            r, c = self._token_contribution(tok, post, idf, avgdl)
+            at = np.minimum(np.searchsorted(r, rows), len(r) - 1)      # (posting rows ascend: they are appended in row order)
+            hit = inside & (r[at] == rows)
+            out[hit] += c[at[hit]]
+        return out
+
+    def score_rows(self, query: str, rows) -> np.ndarray:
+        """`get_scores(tokens)[rows]` (float64 [m]) without one float per PASSAGE (extension): per query token, in order, the token's
+        posting rows are searched for the given rows and its cached contribution is added where a row is present -- the same
+        additions per row in the same order, hence the same bits.  Rows < 0 (and rows the index does not hold) score 0.0; rows may
+        repeat."""
+        return self._score_rows_tokens(self._tokenize(query), rows)
+
+    def score_rows_batch(self, queries: Sequence[str], rows) -> np.ndarray:
+        """`score_rows` for one list of rows per query: rows [B][m] -> float64 [B][m]."""
+        rows = np.asarray(rows, dtype=np.int64)
+        if rows.ndim != 2 or rows.shape[0] != len(queries):
+            raise ValueError(f"expected [{len(queries)}][m] rows, one list per query, got {rows.shape}")
+        out = np.zeros(rows.shape)
+        for b, q in enumerate(queries):
+            if (rows[b] >= 0).any():
+                out[b] = self._score_rows_tokens(self._tokenize(q), rows[b])
+        return out
+
     def _row_of_id(self) -> Dict[str, int]:
         """id -> row (first occurrence), rebuilt when documents were added"""
         c = self.__dict__.get("_row_of_cache")
@@ -885,6 +924,100 @@ class DenseIndex:
         scores = host[2 * B * k: 3 * B * k].view(np.float32).reshape(B, k)
         return scores, rows
 
+    # ---- scoring given passages (extension: the dense score of a passage the dense search did not return; Chroma scores only what
+    # its query returns, reference :355-359, so the reference's fusion writes 0.0 there, :498-499) -----------------------------------
+    def _scoring_index(self):
+        if self._index is not None and (not hasattr(self._index, "score_rows") or len(getattr(self._index, "devices", [0])) > 1):
+            raise _native.RqError("score_vectors / score_rows_batch / score_ids need a single-device index")
+        return self._index
+
+    def score_vectors(self, vectors: np.ndarray, rows) -> np.ndarray:
+        """The exact score (this index's metric) of every given query vector against its own list of rows: vectors [B][dim], rows
+        [B][m] (row r is `self._ids[r]`; -1 or any row the index does not hold scores 0.0) -> float32 [B][m], the values a search
+        returns for those pairs (include/rq.h rq_score_rows)."""
+        vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
+        rows = np.atleast_2d(np.asarray(rows, dtype=np.int64))
+        if rows.ndim != 2 or rows.shape[0] != vectors.shape[0]:
+            raise ValueError(f"expected [{vectors.shape[0]}][m] rows, one list per query, got {rows.shape}")
+        index = self._scoring_index()
+        if index is None or len(self._ids) == 0 or rows.size == 0:
+            return np.zeros(rows.shape, np.float32)
+        if vectors.shape[1] != self.dim:
+            raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
+        return index.score_rows(vectors, rows, self.metric)
+
+    def _score_device_rows(self, d_vectors, rows: np.ndarray) -> np.ndarray:
+        """`score_vectors` for queries that are already in HBM (rq_score_rows_device on torch's current stream)."""
+        import torch
+        B, m = rows.shape
+        dev = d_vectors.device
+        q = d_vectors.to(torch.float32).contiguous()
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            d_rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(dev, non_blocking=False)
+            d_scores = torch.empty((B, m), device=dev, dtype=torch.float32)
+            self._index.score_rows_device(q, B, d_rows, m, self.metric, d_scores, stream.cuda_stream)
+            return d_scores.cpu().numpy()
+
+    def _embed_queries(self, queries: Sequence[str], *, host_only: bool = False):
+        """The query vectors of one call, embedded ONCE: ("device", tensor in HBM) from an embedder that can leave them there and an
+        index that searches them there, else ("host", float32 matrix).  What searched is what scores."""
+        single = self._index is not None and hasattr(self._index, "search_device") and len(getattr(self._index, "devices", [0])) == 1
+        if not host_only and single and len(self._ids) and hasattr(self.embedder, "embed_device"):
+            try:
+                d_q = self.embedder.embed_device(list(queries))
+            except Exception as e:
+                logger.error(f"Device embedding failed ({e}); falling back to the host path")
+                d_q = None
+            if d_q is not None:
+                return "device", d_q
+        return "host", self._embed_matrix(list(queries))
+
+    def _search_embedded(self, qv, top_k: int, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`search_rows_batch` over vectors from `_embed_queries`."""
+        kind, vecs = qv
+        B = int(vecs.shape[0])
+        if self._index is None or len(self._ids) == 0 or top_k <= 0 or B == 0:
+            return np.zeros((B, 0), np.float32), np.zeros((B, 0), np.int64)
+        if allowed_ids is not None:
+            return self._filtered_rows(vecs, top_k, allowed_ids)
+        if kind == "device":
+            return self._search_device_rows(vecs, top_k)
+        k = min(int(top_k), len(self._ids), _native.MAX_K)
+        return self._index.search(vecs, k, self.metric)
+
+    def _score_embedded(self, qv, rows: np.ndarray) -> np.ndarray:
+        kind, vecs = qv
+        rows = np.asarray(rows, dtype=np.int64)
+        index = self._scoring_index()
+        if index is None or len(self._ids) == 0 or rows.size == 0 or not (rows >= 0).any():
+            return np.zeros(rows.shape, np.float32)
+        if kind == "device":
+            return self._score_device_rows(vecs, rows)
+        return self.score_vectors(vecs, rows)
+
+    def score_rows_batch(self, queries: Sequence[str], rows) -> np.ndarray:
+        """Embeds the query strings (once, where a search would embed them) and scores each against its own list of rows: float32
+        [B][m], see `score_vectors`."""
+        rows = np.atleast_2d(np.asarray(rows, dtype=np.int64))
+        if rows.ndim != 2 or rows.shape[0] != len(queries):
+            raise ValueError(f"expected [{len(queries)}][m] rows, one list per query, got {rows.shape}")
+        self._scoring_index()
+        if self._index is None or len(self._ids) == 0 or rows.size == 0:
+            return np.zeros(rows.shape, np.float32)
+        return self._score_embedded(self._embed_queries(list(queries)), rows)
+
+    def score_ids(self, query: str, ids: Sequence[str]) -> List[float]:
+        """The dense score of `query` for each of the passages `ids`, in their order: what `search` would report for that passage if
+        it ranked it.  An id the index does not hold scores 0.0 (the reference's value for "not scored"); an empty index returns
+        zeros."""
+        ids = list(ids)
+        self._scoring_index()
+        if self._index is None or len(self._ids) == 0 or not ids:
+            return [0.0] * len(ids)
+        rows = np.fromiter((self._row_of.get(d, -1) for d in ids), np.int64, len(ids))[None, :]
+        return self.score_rows_batch([query], rows)[0].astype(np.float64).tolist()
+
     def search_rows_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
         """`search_batch` without the (doc_id, score, text) tuples: (scores float32 [B][k], rows int64 [B][k], -1 padded; row r is
         `self._ids[r]`), k = min(top_k, len(self)).  What HybridRetriever's batched fusion consumes (extension).
@@ -1055,12 +1188,14 @@ class HybridRetriever:
             res = [self.dense_index.search(q, top_k) for q in queries]
         return [[(d, s) for d, s, _ in r] for r in res]
 
-    def _fuse_columns(self, bm25_list: List[Tuple[str, float]], dense_list: List[Tuple[str, float]], top_k: int):
+    def _fuse_columns(self, bm25_list: List[Tuple[str, float]], dense_list: List[Tuple[str, float]], top_k: int, extra=None):
         """Reference :485-523 on parallel lists: union of both pools, ids unknown to `self.documents` dropped, missing score 0.0,
         hybrid = (bm25/max_bm25 + dense/max_dense)/2 with `max(...) or 1` over ALL candidates, stable sort desc, first top_k.
         The reference walks a Python set (arbitrary order); here the union is walked in first-seen order (BM25 pool, then dense
         pool), one admissible instance of that order.  Returns (ids, bm25 scores, dense scores, hybrid scores) of the top_k --
-        the RetrievalResult objects (2 us each, 200 candidates per question) are only built for what is returned."""
+        the RetrievalResult objects (2 us each, 200 candidates per question) are only built for what is returned.
+        `extra` (`complete_scores`, from `_completions`): (bm25 scores, dense scores) by id for candidates the other pool does not
+        hold; they replace the 0.0, nothing else changes -- not the candidates, not their order."""
         bm25_results = dict(bm25_list)
         dense_results = dict(dense_list)
         documents = self.documents
@@ -1069,31 +1204,71 @@ class HybridRetriever:
             return [], [], [], []
         b = [bm25_results.get(d, 0.0) for d in ids]
         de = [dense_results.get(d, 0.0) for d in ids]
+        if extra is not None:
+            b = [x if d in bm25_results else extra[0].get(d, 0.0) for d, x in zip(ids, b)]
+            de = [y if d in dense_results else extra[1].get(d, 0.0) for d, y in zip(ids, de)]
         max_bm25 = max(b) or 1
         max_dense = max(de) or 1
         h = [(x / max_bm25 + y / max_dense) / 2 for x, y in zip(b, de)]
         order = sorted(range(len(ids)), key=lambda i: h[i] or 0, reverse=True)[:top_k]      # stable, like list.sort(reverse=True)
         return [ids[i] for i in order], [b[i] for i in order], [de[i] for i in order], [h[i] for i in order]
 
-    def _fuse(self, bm25_list: List[Tuple[str, float]], dense_list: List[Tuple[str, float]], top_k: int) -> List[RetrievalResult]:
-        ids, b, de, h = self._fuse_columns(bm25_list, dense_list, top_k)
+    def _fuse(self, bm25_list: List[Tuple[str, float]], dense_list: List[Tuple[str, float]], top_k: int, extra=None) -> List[RetrievalResult]:
+        ids, b, de, h = self._fuse_columns(bm25_list, dense_list, top_k, extra)
         out = []
         for doc_id, bs, ds, hs in zip(ids, b, de, h):
             doc = self.documents[doc_id]
             out.append(RetrievalResult(doc_id=doc_id, text=doc.text, bm25_score=bs, dense_score=ds, hybrid_score=hs, title=doc.title, metadata=doc.metadata))
         return out
 
-    def hybrid_search(self, query: str, top_k: int = 10, retrieval_pool_size: int = 50, *, allowed_ids=None) -> List[RetrievalResult]:
+    # `complete_scores` (keyword-only extension on the four fusion calls): the reference's fusion writes 0.0 for the score a passage
+    # did not get from the other retriever (:498-499) -- an artefact of the pool size that goes straight into the router's features.
+    # With True every candidate gets the score it is missing before the maxima are taken: its exact dense score if the dense index
+    # holds its id (rq_score_rows), its BM25 score if BM25 holds it.  False (default) changes nothing.
+    def _pools_completed(self, query: str, retrieval_pool_size: int, allowed_ids=None):
+        """Both pools of one query and the missing scores of their candidates: (bm25 list, dense list, (bm25 extra, dense extra)).
+        The query is embedded once: the vector that searched is the vector that scores."""
+        if allowed_ids is not None:
+            allowed_ids = list(allowed_ids)
+        bm25_list = self.bm25_search(query, retrieval_pool_size, allowed_ids=allowed_ids) if allowed_ids is not None else self.bm25_search(query, retrieval_pool_size)
+        dn, bm = self.dense_index, self.bm25_index
+        dense_list: List[Tuple[str, float]] = []
+        qv = None
+        if dn is not None:
+            if not isinstance(dn, DenseIndex):
+                raise _native.RqError("complete_scores needs this module's DenseIndex on the dense side")
+            qv = dn._embed_queries([query], host_only=allowed_ids is not None)
+            dense_list = [(d, sc) for d, sc, _ in dn._assemble(*dn._search_embedded(qv, retrieval_pool_size, allowed_ids))[0]] if len(dn) else []
+        in_b, in_d, docs = dict(bm25_list), dict(dense_list), self.documents
+        dense_extra: Dict[str, float] = {}
+        if dn is not None and len(dn):
+            miss = [d for d in in_b if d not in in_d and d in docs and d in dn._row_of]
+            if miss:
+                rows = np.fromiter((dn._row_of[d] for d in miss), np.int64, len(miss))[None, :]
+                dense_extra = dict(zip(miss, dn._score_embedded(qv, rows)[0].astype(np.float64).tolist()))
+        bm25_extra: Dict[str, float] = {}
+        if isinstance(bm, BM25Index) and len(bm):
+            row_of = bm._row_of_id()
+            miss = [d for d in in_d if d not in in_b and d in docs and d in row_of]
+            if miss:
+                bm25_extra = dict(zip(miss, bm.score_rows(query, [row_of[d] for d in miss]).tolist()))
+        return bm25_list, dense_list, (bm25_extra, dense_extra)
+
+    def hybrid_search(self, query: str, top_k: int = 10, retrieval_pool_size: int = 50, *, allowed_ids=None, complete_scores: bool = False) -> List[RetrievalResult]:
+        if complete_scores:
+            bm25_list, dense_list, extra = self._pools_completed(query, retrieval_pool_size, allowed_ids)
+            return self._fuse(bm25_list, dense_list, top_k, extra)
         if allowed_ids is not None:
             allowed_ids = list(allowed_ids)      # (walked twice)
             return self._fuse(self.bm25_search(query, retrieval_pool_size, allowed_ids=allowed_ids),
                               self.dense_search(query, retrieval_pool_size, allowed_ids=allowed_ids), top_k)
         return self._fuse(self.bm25_search(query, retrieval_pool_size), self.dense_search(query, retrieval_pool_size), top_k)
 
-    def hybrid_search_batch(self, queries: Sequence[str], top_k: int = 10, retrieval_pool_size: int = 50) -> List[List[RetrievalResult]]:
+    def hybrid_search_batch(self, queries: Sequence[str], top_k: int = 10, retrieval_pool_size: int = 50, *, complete_scores: bool = False
+                            ) -> List[List[RetrievalResult]]:
         """All dense pools from one GPU batch, all BM25 pools from one pass over the posting lists on the host cores (librq_bm25.so);
         fusion per query.  (`allowed_ids` is an extension of the per-query calls only: the batch fusions are not extended.)"""
-        fused = self._fuse_batch_rows(queries, top_k, retrieval_pool_size)
+        fused = self._fuse_batch_rows(queries, top_k, retrieval_pool_size, complete_scores)
         if fused is not None:
             ids, b, de, hy, count = fused
             idl, bl, dl, hl = ids.tolist(), b.tolist(), de.tolist(), hy.tolist()
@@ -1106,6 +1281,8 @@ class HybridRetriever:
                                                title=doc.title, metadata=doc.metadata))
                 out.append(res)
             return out
+        if complete_scores:
+            return [self.hybrid_search(q, top_k, retrieval_pool_size, complete_scores=True) for q in queries]
         dense, sparse = self._pools_batch(queries, retrieval_pool_size)
         return [self._fuse(sparse[i], dense[i], top_k) for i in range(len(queries))]
 
@@ -1133,20 +1310,24 @@ class HybridRetriever:
             texts += [""] * pad
         return bm25_scores, dense_scores, doc_ids, texts
 
-    def get_scores_for_router(self, query: str, num_passages: int = 20, *, retrieval_pool_size: int = 50, allowed_ids=None
-                              ) -> Tuple[List[float], List[float], List[str], List[str]]:
+    def get_scores_for_router(self, query: str, num_passages: int = 20, *, retrieval_pool_size: int = 50, allowed_ids=None,
+                              complete_scores: bool = False) -> Tuple[List[float], List[float], List[str], List[str]]:
         """Reference :525-557 (its pools are always 50, :537); `retrieval_pool_size` is a keyword-only extension for
-        BASELINE.json configs[4] (top-100 pools), `allowed_ids` restricts both pools to those passages."""
+        BASELINE.json configs[4] (top-100 pools), `allowed_ids` restricts both pools to those passages, `complete_scores` fills in the
+        score a passage did not get from the other retriever (see `_pools_completed`)."""
+        if complete_scores:
+            return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size, allowed_ids=allowed_ids,
+                                                          complete_scores=True), num_passages)
         if allowed_ids is not None:
             return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size, allowed_ids=allowed_ids),
                                        num_passages)
         return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size), num_passages)
 
-    def get_scores_for_router_batch(self, queries: Sequence[str], num_passages: int = 20, *, retrieval_pool_size: int = 50):
+    def get_scores_for_router_batch(self, queries: Sequence[str], num_passages: int = 20, *, retrieval_pool_size: int = 50, complete_scores: bool = False):
         """`[get_scores_for_router(q, ...) for q in queries]` (without `allowed_ids`: the batch fusions are not extended) with the pools of the whole batch computed at once.  When both sides are
         this module's own indexes the fusion itself runs on the whole batch in row space (`_fuse_batch_rows`); otherwise per query on the
         fused columns (no RetrievalResult objects in between)."""
-        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size)
+        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores)
         if fused is not None:
             ids, b, de, _, count = fused
             ids[np.arange(num_passages)[None, :] >= count[:, None]] = ""
@@ -1154,6 +1335,8 @@ class HybridRetriever:
             documents = self.documents                      # (texts are read from the store at call time, as the per-query path does)
             texts = [[documents[d].text if d else "" for d in row] for row in idl]
             return list(zip(b.tolist(), de.tolist(), idl, texts))
+        if complete_scores:
+            return [self.get_scores_for_router(q, num_passages, retrieval_pool_size=retrieval_pool_size, complete_scores=True) for q in queries]
         dense, sparse = self._pools_batch(queries, retrieval_pool_size)
         documents = self.documents
         out = []
@@ -1170,7 +1353,7 @@ class HybridRetriever:
     def _key_space(self):
         """One integer key per document either index can return: BM25 row r -> r, dense row j -> the BM25 row of the same id if BM25
         holds it, else n_bm25 + j.  Per key: the id and whether `self.documents` knows it at all (reference :491-493 skips ids it does
-        not).  Rebuilt when any of the three stores has grown."""
+        not), and the dense row that holds its id (-1: none; `complete_scores`).  Rebuilt when any of the three stores has grown."""
         bm, dn = self.bm25_index, self.dense_index
         stamp = (len(bm.doc_ids), len(dn._ids), len(self.documents))
         c = self.__dict__.get("_keys_cache")
@@ -1184,22 +1367,31 @@ class HybridRetriever:
         ids[:] = all_ids
         docs = self.documents
         known = np.fromiter((d in docs for d in all_ids), np.bool_, len(all_ids))
-        c = self.__dict__["_keys_cache"] = {"stamp": stamp, "nb": nb, "dense_key": dense_key, "ids": ids, "known": known}
+        dense_row = np.full(len(all_ids), -1, np.int64)
+        dense_row[dense_key] = np.arange(len(dn._ids), dtype=np.int64)
+        c = self.__dict__["_keys_cache"] = {"stamp": stamp, "nb": nb, "dense_key": dense_key, "ids": ids, "known": known, "dense_row": dense_row}
         return c
 
-    def _fuse_batch_rows(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int):
+    def _fuse_batch_rows(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool = False):
         """`_fuse_columns` for every query of the batch at once, on integer keys: same candidates (union of both pools in first-seen
         order -- BM25 pool, then dense pool -- ids unknown to `self.documents` dropped), same float64 arithmetic (`max(...) or 1` over all
         candidates, hybrid = (b/max_b + d/max_d)/2), same stable descending sort, first top_k.  Returns (ids [B][top_k] object,
         bm25 scores, dense scores, hybrid scores, count [B]) -- entries beyond count[b] are padding -- or None when one of the two sides
-        is not this module's own index class (then the per-query path runs)."""
+        is not this module's own index class (then the per-query path runs).
+        `complete_scores`: after both pools are drawn and before the maxima are taken, ONE dense scoring call for the batch ([B][K1]
+        dense rows of the BM25 pool, -1 where nothing is missing or no dense row exists) and one BM25 batch call for the dense-only
+        entries fill in the scores the reference leaves at 0.0; the queries are embedded once for the search and the scoring."""
         bm, dn = self.bm25_index, self.dense_index
         if not (isinstance(bm, BM25Index) and isinstance(dn, DenseIndex)) or len(queries) == 0 or top_k <= 0:
             return None
         B = len(queries)
         ks = self._key_space()
         sp_rows, sp_scores = bm.search_batch_rows(list(queries), retrieval_pool_size)
-        de_scores, de_rows = dn.search_rows_batch(list(queries), retrieval_pool_size)
+        if complete_scores:
+            qv = dn._embed_queries(list(queries))
+            de_scores, de_rows = dn._search_embedded(qv, retrieval_pool_size)
+        else:
+            de_scores, de_rows = dn.search_rows_batch(list(queries), retrieval_pool_size)
         K1, K2 = sp_rows.shape[1], de_rows.shape[1]
         sp_keys = sp_rows.astype(np.int64)
         de_keys = np.where(de_rows >= 0, ks["dense_key"][np.where(de_rows >= 0, de_rows, 0)], -1) if K2 else np.zeros((B, 0), np.int64)
@@ -1215,6 +1407,18 @@ class HybridRetriever:
         first, second = order[r, j], order[r, j + 1]
         dsc[r, first] = dsc[r, second]
         valid[r, second] = False
+        if complete_scores:
+            have_dense = np.zeros(keys.shape, dtype=bool)
+            have_dense[:, K1:] = True
+            have_dense[r, first] = True
+            need = valid[:, :K1] & ~have_dense[:, :K1]
+            d_rows = np.where(need, ks["dense_row"][np.where(need, keys[:, :K1], 0)], -1)
+            if K1 and (d_rows >= 0).any():
+                got = dn._score_embedded(qv, d_rows).astype(np.float64)
+                dsc[:, :K1] = np.where(d_rows >= 0, got, dsc[:, :K1])
+            b_rows = np.where(valid[:, K1:] & (keys[:, K1:] < ks["nb"]), keys[:, K1:], -1)      # dense-only entries that are still candidates
+            if K2 and (b_rows >= 0).any():
+                bsc[:, K1:] = np.where(b_rows >= 0, bm.score_rows_batch(list(queries), b_rows), bsc[:, K1:])
         neg_inf = -np.inf
         max_b = np.where(valid, bsc, neg_inf).max(axis=1, initial=neg_inf)
         max_d = np.where(valid, dsc, neg_inf).max(axis=1, initial=neg_inf)

@@ -217,6 +217,35 @@ int rq_mmr_select_device(rq_index* idx, const int64_t* d_cand_rows, const float*
 int rq_search_mmr(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int fetch_k, double lambda, int metric,
                   float* out_scores, int64_t* out_rows, float* out_mmr);
 
+/* ---- scoring given rows: the exact score of named (query, row) pairs (what hybrid fusion needs for a passage that only the OTHER
+ * retriever returned: reference rag_uq/streaming_index.py:485-523 writes 0.0 there, :498-499, because collection.query scores only
+ * what it returns; also re-scoring a re-ranker's candidates, checking a cached answer against the index) ---------------------------
+ * One list of m rows per query, no ranking: scores[q][j] is the score of query q and row rows[q][j], position for position.
+ *   lists: rows / d_rows [B][m] int64 GLOBAL rows (row_offset + local row), scores / d_scores [B][m] fp32.  Duplicates are allowed, a
+ *     list need not be sorted.
+ *   absent entry: a value outside [row_offset, row_offset + rq_index_size), -1 included.  Its score is 0.0 -- the reference's own
+ *     value for "not scored" -- and no row is read for it.  On an empty index every entry is absent.
+ *   score: the score definition above on the STORED fp16 row; a NaN score counts as -inf, as for every score; -0.0 is returned as
+ *     0.0, as every search returns it; a zero-norm query scores every present row 0.0 under both metrics.
+ *   same bits as every other route: the value is the one rq_search and the gather route of a filtered search return for that pair
+ *     (the queries are prepared by the same kernel, every dot product is summed in the same order: csrc/rq_rowdot.h).
+ * rq_score_rows_device: asynchronous, device pointers; its results are complete in stream order.  It behaves like a "pipeline" = 0
+ *   call, as rq_search_filtered_device does: it first completes whatever `stream` still defers (a fused tail, a scanned-ahead pair, a
+ *   hint), because it uses the stream's prepared-query slots, and it defers nothing itself.  Afterwards the stream's "last search"
+ *   has no bin records (rq_debug_bin_records: RQ_EINVAL), as after a gather-route call.  Queries are taken in groups of 1 024.
+ * rq_score_rows: blocking, host buffers, staged on the index's own stream like rq_search_filtered: B x dim x 4 + B x m x 12 bytes of
+ *   HBM for the call (RQ_ENOMEM with a message when that fails).
+ * RQ_EINVAL unless 1 <= B <= 65535, 1 <= m <= RQ_MAX_SCORE_ROWS, a known metric and non-null pointers; RQ_EUNSUPPORTED on a
+ *   multi-device index, for both forms; RQ_ENODEVICE as everywhere.  The call reads the stored rows: one rq_index from one thread at
+ *   a time, and no append while a call is in flight.
+ * Not extended: rq_search_train_device, hints, "pipeline" 1 and 2, multi-device indexes.
+ * Read-only options "score_calls" (calls so far, both entry points) and "score_pairs" (B x m per call: present pairs are not
+ *   counted separately).  rq_timing is untouched: a scoring call is not a search. */
+#define RQ_MAX_SCORE_ROWS 65536
+int rq_score_rows_device(rq_index* idx, const float* d_queries, int B, const int64_t* d_rows, int m, int metric,
+                         float* d_scores, void* stream);
+int rq_score_rows(rq_index* idx, const float* queries, int B, const int64_t* rows, int m, int metric, float* out_scores);
+
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
  * "wg_per_cu", "nt" (non-temporal corpus loads: 0, 1, -1 = auto), "slack_bins" (extra bins beyond k, -1 = auto),
