@@ -84,6 +84,8 @@ __global__ __launch_bounds__(256, 1) void rq_exact_scan_kernel(RqRescoreArgs a, 
             if (row < a.n_rows) {
                 double s = acc[i];
                 if (a.metric == 0) s = acc[i] / (qn * a.rownorm64[row] + 1e-30);
+                if (qn == 0.0) s = 0.0;   // a zero-norm query scores every row 0 (include/rq.h).  For consistency of the keys only:
+                                          // rq_final_kernel answers such a query before it reads them
                 key = rq_make_key(rq_sanitize((float)s), (uint32_t)row);
             }
             if (live_q) out[row] = key;

@@ -84,7 +84,8 @@ __global__ __launch_bounds__(256) void rq_gather_score_kernel(RqGatherArgs a) {
             if (sub == 0 && lv[u]) {
                 double sc = d;
                 if (a.metric == 0) sc = d / (qn * rn[u] + 1e-30);
-                if (qn == 0.0) sc = 0.0;   // a zero-norm query scores every row 0 (include/rq.h): the first allowed rows win
+                if (qn == 0.0) sc = 0.0;   // a zero-norm query scores every row 0 (include/rq.h).  For consistency of the keys only:
+                                           // rq_final_kernel answers such a query (RqFinalArgs::first) before it reads them
                 out[slot[u]] = rq_make_key(rq_sanitize((float)sc), (uint32_t)rows[u]);
             }
         }
@@ -253,6 +254,7 @@ static int gather_route(rq_index* idx, rq_filter* f, const float* d_q, int B, in
         RqFinalArgs fa{};
         fa.cand = cand; fa.ncand = (int)na; fa.binkeys = nullptr; fa.binkeys_stride = 0; fa.nb = 1; fa.nbins = 1;   // nbins <= nb: every row in play was re-scored
         fa.qnorm64 = qs->qn; fa.metric = metric; fa.eps = 0.f; fa.max_row_norm = 0.f; fa.k = k; fa.row_offset = idx->row_offset; fa.n_rows = na;
+        fa.first = f->d_first;
         fa.out_scores = out.scores + (size_t)off * k; fa.out_rows = out.rows + (size_t)off * k;
         fa.out_keys = out.keys ? out.keys + (size_t)off * k : nullptr; fa.out_status = out.status + off;
         HIPCHK(rq_prep_queries_launch(pa, s));

@@ -113,7 +113,8 @@ struct RqFinalArgs {
     float max_row_norm;        // for the inner-product bound
     int k;
     int64_t row_offset;        // global id of the shard's row 0
-    int64_t n_rows;
+    int64_t n_rows;            // rows that can be returned (a filtered call: the allowed rows)
+    const uint32_t* first = nullptr;   // a filtered call: RqFilterArgs::first (the answer of a zero-norm query); null = rows 0, 1, ..
     float* out_scores;         // [B][k]
     int64_t* out_rows;         // [B][k], -1 padded
     uint64_t* out_keys;        // [B][k] optional (global-row keys for cross-shard merging), may be null

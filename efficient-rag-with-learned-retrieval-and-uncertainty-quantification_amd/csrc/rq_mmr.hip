@@ -71,9 +71,11 @@ __global__ __launch_bounds__(RQ_MMR_THREADS) void rq_mmr_kernel(RqMmrArgs a) {
         int bp = -1;
         for (int i = tid; i < m; i += RQ_MMR_THREADS) {
             if (!live[i]) continue;
-            const double gain = lam * (double)rel[i], loss = oml * (double)pen[i];   // two products and one subtraction, each rounded
+            // two products and one subtraction, each rounded; a term whose weight is exactly 0 is 0 whatever its other factor
+            // (lambda = 1: v = rel, the search's order also where a penalty is infinite; lambda = 0: v = -pen)
+            const double gain = lam == 0.0 ? 0.0 : lam * (double)rel[i], loss = oml == 0.0 ? 0.0 : oml * (double)pen[i];
             double v = gain - loss;
-            if (v != v) v = -__builtin_huge_val();   // (0 x inf: ranks last, as rq_sanitize ranks a NaN score)
+            if (v != v) v = -__builtin_huge_val();   // (inf - inf: ranks last, as rq_sanitize ranks a NaN score)
             rq_mmr_better(bv, bp, v, i);
         }
 #pragma unroll

@@ -471,6 +471,7 @@ static int generic_tail(rq_index* idx, const Call& c, const Workspace& w) {
     fa.cand = w.cand; fa.ncand = (int)p.ncand; fa.binkeys = w.binkeys; fa.binkeys_stride = p.m; fa.nb = p.nb; fa.nbins = p.exact ? p.nb : p.nbins;
     fa.qnorm64 = w.qs.qn; fa.metric = c.metric; fa.eps = scan_eps(idx, c.metric);
     fa.max_row_norm = (float)(idx->max_row_norm * (1.0 + 1e-6)); fa.k = c.k; fa.row_offset = idx->row_offset; fa.n_rows = c.filt ? c.filt->na : idx->n;   // (n_rows: the rows that can be returned)
+    fa.first = c.filt ? c.filt->d_first : nullptr;
     fa.out_scores = c.out.scores; fa.out_rows = c.out.rows; fa.out_keys = c.out.keys; fa.out_status = c.out.status;
     HIPCHK(rq_final_launch(fa, c.B, s));
     return RQ_OK;

@@ -50,7 +50,10 @@ __global__ __launch_bounds__(256) void rq_rownorm_kernel(const char* x, int dpad
         sub = rq_wave_sum(sub);
         const double nrm = sqrt(acc);
         if (lane == 0) norm64[row] = nrm;
-        if (nrm == nrm && nrm <= 1.7e308) {   // (rows with non-finite elements never certify anyway)
+        // a row with a non-finite element (norm NaN or infinite) stays out of the statistics: its cosine is NaN = -inf for every
+        // query, its scan score the clamp value (row scale 0), so it is never a candidate of a finite query and holds up no
+        // certificate -- measured: as many repairs as on a twin shard with those rows zeroed
+        if (nrm == nrm && nrm <= 1.7e308) {
             mx_norm = fmax(mx_norm, nrm);
             if (sub > 0.0) { mx_abs = fmax(mx_abs, sqrt(sub)); mx_rel = fmax(mx_rel, sqrt(sub / acc)); }
         }
@@ -353,6 +356,8 @@ __global__ __launch_bounds__(256) void rq_rescore_kernel(RqRescoreArgs a) {
         if (lane == 0) {
             double s = dot;
             if (a.metric == 0) s = dot / (qn * a.rownorm64[row] + 1e-30);
+            if (qn == 0.0) s = 0.0;   // a zero-norm query scores every row 0 (include/rq.h).  For consistency of the keys only:
+                                      // rq_final_kernel answers such a query before it reads them
             out[j] = rq_make_key(rq_sanitize((float)s), (uint32_t)row);
         }
     }
@@ -368,6 +373,21 @@ __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a)
     __shared__ uint64_t list[RQ_SEL_L];
     __shared__ int cnt;
     const int q = blockIdx.x;
+    if (a.qnorm64[q] == 0.0) {
+        // a zero-norm query scores every row 0 (include/rq.h): the first rows that can be returned, as rq_final_body answers it --
+        // whichever bins were re-scored (a bin of NaN rows is never among them: its approximate maximum is the smallest value)
+        const int64_t kk = a.k < a.n_rows ? a.k : a.n_rows;
+        for (int j = threadIdx.x; j < a.k; j += RQ_SEL_THREADS) {
+            const int64_t o = (int64_t)q * a.k + j;
+            const bool v = j < kk;
+            const int64_t grow = a.row_offset + (v && a.first ? (int64_t)a.first[j] : (int64_t)j);
+            a.out_scores[o] = 0.f;
+            a.out_rows[o] = v ? grow : -1;
+            if (a.out_keys) a.out_keys[o] = v ? rq_make_key(0.f, (uint32_t)grow) : 0;
+        }
+        if (threadIdx.x == 0) a.out_status[q] = 0;
+        return;   // uniform over the workgroup
+    }
     const uint64_t* c = a.cand + (int64_t)q * a.ncand;
     const int have = rq_wg_topm([&](int64_t i) { return c[i]; }, a.ncand, a.k, list, &cnt);
     for (int j = threadIdx.x; j < a.k; j += RQ_SEL_THREADS) {
@@ -392,7 +412,7 @@ __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a)
         const int64_t kk = a.k < a.n_rows ? a.k : a.n_rows;   // rows that must be returned
         if (a.nbins <= a.nb) {
             ok = 1;   // the whole shard was re-scored
-        } else if (have < kk || (a.metric == 0 && a.qnorm64[q] != 0.0 && a.qnorm64[q] < RQ_TINY_QUERY_NORM)) {
+        } else if (have < kk || (a.metric == 0 && a.qnorm64[q] < RQ_TINY_QUERY_NORM)) {
             ok = 0;   // (tiny query: see rq_final_body.h RQ_TINY_QUERY_NORM)
         } else if (kk == 0) {
             ok = 1;
@@ -406,11 +426,7 @@ __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a)
                 const double bound = a.metric == 0 ? b + (double)a.eps
                                                    : (b + (double)a.eps * (double)a.max_row_norm) * qn * (1.0 + 1e-6);
                 const float sk = rq_key_score(list[kk - 1]);
-                ok = ((float)bound < sk) ? 1 : 0;
-                if (qn == 0.0) {
-                    // every score is 0: the answer is rows 0..k-1, present iff whole leading quads were re-scored
-                    ok = (kk <= (int64_t)a.nb * RQ_BIN_ROWS) ? 1 : 0;
-                }
+                ok = ((float)bound < sk) ? 1 : 0;   // (a zero-norm query never comes here: answered above)
             }
         }
         a.out_status[q] = ok ? 0 : 1;

@@ -35,8 +35,12 @@ def unmono32(k: np.ndarray) -> np.ndarray:
 
 
 def pack_keys(scores: np.ndarray, rows: np.ndarray) -> np.ndarray:
-    """(fp32 scores, int64 global rows, -1 = empty) -> uint64 keys."""
+    """(fp32 scores, int64 global rows, -1 = empty) -> uint64 keys, with the device's two key rules (csrc/rq_device.h rq_sanitize,
+    rq_make_key): a NaN score counts as -inf, and -0.0 ranks with +0.0."""
     rows = np.asarray(rows, dtype=np.int64)
+    scores = np.array(scores, dtype=np.float32, copy=True)
+    scores[np.isnan(scores)] = -np.inf
+    scores[scores == 0] = 0.0
     valid = rows >= 0
     if valid.any() and int(rows[valid].max()) >= 0xFFFFFFFF:
         raise ValueError("global row ids must be below 2^32 - 1")

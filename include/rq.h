@@ -25,6 +25,19 @@
  *   cosine:  s = fp32( dot64(q, x) / (||q||_64 * ||x||_64 + 1e-30) )   on the STORED fp16 row x
  *   ip:      s = fp32( dot64(q, x) )
  *   order:   s descending, then row ascending;  k_eff = min(k, N);  missing entries row = -1.
+ * Non-finite and extreme inputs, both metrics, every route (rq_search, the *_device forms, trains, multi-device indexes, filtered
+ * searches, rq_search_mmr's candidates, rq_score_rows; tests/nonfinite_oracle.py restates it):
+ *   zero-norm query: a query whose fp64 norm is 0 scores every row 0.0, whatever the row holds (a NaN or infinite row included):
+ *            its answer is rows 0 .. k_eff-1 (filtered: the first k_eff allowed rows) at 0.0.
+ *   NaN:     any other score that comes out NaN (a NaN element on either side, inf - inf, 0 x inf, inf / inf -- under cosine every
+ *            row or query with an infinite element, its norm being infinite) counts as -inf.
+ *   +-inf:   legitimate scores (inner product with an infinite element) that order like any other: +inf first, -inf last, equal
+ *            scores by row ascending.  A -inf row is still a row: k_eff = min(k, N) does not shrink, and once the better rows
+ *            are used up the answer goes on with the -inf rows in row order.
+ *   -0.0:    ranks with and is returned as +0.0.
+ *   A query below RQ_TINY_QUERY_NORM (csrc/rq_final_body.h; fp32-subnormal elements) follows the definition with its 1e-30 as it
+ *   stands.  Non-finite queries, and rows among the candidates that score -inf, are answered by the repair ladder (exact, slower);
+ *   non-finite stored rows cost finite queries nothing.
  */
 #ifndef RQ_H
 #define RQ_H
@@ -186,17 +199,20 @@ int rq_search_fixup_filtered_device(rq_index* idx, const rq_filter* f, const flo
  *     and its row is never read.  Duplicates are not checked: the candidate rows must be distinct.
  *   pair similarity: the score definition above with STORED rows on both sides: d = sum_e (double)x_i[e] * (double)x_j[e];
  *     cosine: sim(i, j) = fp32( d / (n_i * n_j + 1e-30) ), n = the stored fp64 row norm; ip: sim(i, j) = fp32(d); a NaN sim
- *     counts as -inf, as for every score.
+ *     counts as -inf, as for every score.  The zero-norm-query rule of the score definition does NOT apply to sim, which has no
+ *     query: a zero row against a row with an infinite element is 0 x inf = NaN, hence -inf, under both metrics.
  *   penalty: pen_i (fp32) = 0 before the first pick, afterwards the maximum of sim(i, j) over the selected j.
  *   value: v_i = lambda * (double)rel_i - (1.0 - lambda) * (double)pen_i in fp64: two products and one subtraction, each
- *     rounded, no fused multiply-add.  A NaN v (0 x inf) counts as -inf.
+ *     rounded, no fused multiply-add.  A term whose weight (lambda, 1.0 - lambda) is exactly 0 is 0 whatever its other factor, an
+ *     infinite one included; a NaN v (inf - inf) counts as -inf.
  *   step: among the present, unselected candidates the greatest v wins, the lowest position on equal v;
  *     k_eff = min(k, present candidates) steps.
  *   outputs, in selection order: d_rows / out_rows the global rows; d_scores / out_scores the candidate's relevance, passed through
  *     unchanged (for a search: its cosine, so everything downstream keeps working); d_mmr / out_mmr (may be NULL) fp32(v) at the
  *     moment of selection; entries beyond k_eff are (0.0, -1, 0.0).
- *   Hence lambda = 1 returns the candidates in relevance order (on a search's own candidates: that search's top k), and at lambda = 0
- *     the first pick is position 0 and every later d_mmr is -pen of the row picked.
+ *   Hence lambda = 1 returns the candidates in relevance order (on a search's own candidates: that search's top k, also where rows
+ *     are non-finite and penalties infinite), and at lambda = 0 the first pick is position 0 and every later d_mmr is -pen of the
+ *     row picked.
  * rq_mmr_select_device: asynchronous, pure selection over a caller's candidates [B][m] in device memory, any order, any relevance (a
  *   fused hybrid score as well as a cosine).  It runs in stream order after whatever produced the candidates and defers nothing.
  *   RQ_EINVAL unless 1 <= k <= m <= RQ_MAX_K, 1 <= B <= 65535, lambda finite and within [0, 1] (NaN included), a known metric and

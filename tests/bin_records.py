@@ -26,6 +26,7 @@ import numpy as np
 
 POISON = 0xFFFFFFFF
 ROUNDUP26 = 2.0 ** -17
+FLT_MAX = np.float32(3.4028234664e38)
 
 
 # ---- decoder: rq_rec_m1, rq_code16_value and the field split of rq_device.h -------------------------------------------------
@@ -77,8 +78,10 @@ def code16(f) -> np.ndarray:
 
 
 def pos_score(score, pos) -> np.ndarray:
-    """rq_pos_score: clamp to the finite range, replace the 6 low mantissa bits by the row's position."""
-    s = np.clip(np.asarray(score, dtype=np.float32), np.float32(-3.4028234664e38), np.float32(3.4028234664e38))
+    """rq_pos_score: clamp to the finite range (NaN becomes the smallest value: v_med3_f32 with a NaN operand returns the minimum
+    of the other two), replace the 6 low mantissa bits by the row's position."""
+    s = np.asarray(score, dtype=np.float32)
+    s = np.clip(np.where(np.isnan(s), -FLT_MAX, s), -FLT_MAX, FLT_MAX).astype(np.float32)
     return _f32((_bits(s) & np.uint32(0xFFFFFFC0)) | np.asarray(pos, dtype=np.uint32))
 
 
@@ -101,11 +104,12 @@ def records_from_scores(approx: np.ndarray, n: int) -> np.ndarray:
     of each bin (pad rows beyond n never win), rq_record_from_triple."""
     approx = np.asarray(approx, dtype=np.float32)
     B, nbins = approx.shape[0], (n + 63) // 64
-    a = np.full((B, nbins * 64), -np.inf, dtype=np.float32)
+    a = np.zeros((B, nbins * 64), dtype=np.float32)
     a[:, :n] = approx[:, :n]
     pos = np.broadcast_to(np.arange(64, dtype=np.uint32), (B, nbins, 64))
     ps = pos_score(a.reshape(B, nbins, 64), pos)
-    ps = np.where(np.isneginf(a.reshape(B, nbins, 64)), np.float32(-np.inf), ps)   # (a pad row stays below every row)
+    pad = (np.arange(nbins * 64) >= n).reshape(1, nbins, 64)
+    ps = np.where(pad, np.float32(-np.inf), ps)   # (a pad row stays below every row, a clamped NaN or -inf row included)
     top = -np.sort(-ps, axis=2)[:, :, :3]
     return record_from_triple(top[..., 0], top[..., 1], top[..., 2])
 
@@ -134,11 +138,11 @@ def int8_query_error(q: np.ndarray, split: bool = False) -> np.ndarray:
 
 # ---- the invariants --------------------------------------------------------------------------------------------------------
 INVARIANTS = {
-    "I1": "m1 finite for every bin with a valid row",
+    "I1": "m1 finite for every bin with a valid row (-inf allowed where every row of the bin scores -inf)",
     "I2": "max E(R_b) <= m1 + beta",
-    "I3": "m1 <= max E(R_b) + beta + 2^-17 |m1|",
+    "I3": "m1 <= max E(R_b) + beta + 2^-17 |m1| (bins with a finite maximum)",
     "I4": "64 b + p1 valid and E(64 b + p1) >= max E(R_b) - 2 beta",
-    "I5": "|R_b| >= 2: p2 != p1 and 64 b + p2 valid",
+    "I5": "|R_b| >= 2: p2 != p1 and 64 b + p2 valid (unless the second-best exact score and decode(c2) are both -inf: p2 is then never used on its own)",
     "I6": "E(r) <= decode(c2) + beta for every valid r != p1",
     "I7": "E(r) <= decode(c2 - d) + beta for every valid r not p1 / p2",
     "I8": "query slots [B, slots) still hold the poison pattern",
@@ -185,18 +189,27 @@ def check_records(rec: np.ndarray, exact: np.ndarray, n: int, beta, B: int = Non
         out[name] = {"ok": worst >= 0, "margin": worst, "first": first}
 
     with np.errstate(invalid="ignore", over="ignore"):
-        report("I1", np.where(np.isfinite(m1), 0.0, -np.inf))
-        report("I2", m1 + beta - M)
-        report("I3", M + beta + ROUNDUP26 * np.abs(m1) - m1)
+        # Exact scores may hold -inf (a NaN score counts as -inf, include/rq.h).  Every field is an upper bound, and -inf is
+        # below everything: a row at -inf constrains no field, and a bin of nothing else (`dead`) has no maximum to be tight
+        # against -- its m1 is the clamp value (positions inside the scores) or -inf (compare / select drops a NaN), then with
+        # decode(c2) = -inf, which makes the tail take the whole bin whenever it takes a second row.
+        dead = np.isneginf(M)
+        low = np.isneginf(E)
+        report("I1", np.where(np.isfinite(m1) | (dead & np.isneginf(m1)), 0.0, -np.inf))
+        report("I2", np.where(dead, np.inf, m1 + beta - M))
+        report("I3", np.where(dead, np.inf, M + beta + ROUNDUP26 * np.abs(m1) - m1))
         p1_ok = valid[np.arange(nbins)[None, :], p1]
         e_p1 = np.take_along_axis(E, p1[..., None], axis=2)[..., 0]
-        report("I4", np.where(p1_ok, e_p1 - (M - 2 * beta), -np.inf))
+        report("I4", np.where(p1_ok, np.where(dead, np.inf, e_p1 - (M - 2 * beta)), -np.inf))
         p2_ok = valid[np.arange(nbins)[None, :], p2] & (p2 != p1)
-        report("I5", np.where((nvalid[None, :] < 2) | p2_ok, 0.0, -np.inf))
+        # (waived only where the bin's second-best exact score is -inf and the field says so: decode(c2) = -inf is then honest, and
+        # the tail never uses p2 on its own, decode(c2 - d) being -inf too)
+        second = np.sort(E, axis=2)[:, :, -2]
+        report("I5", np.where((nvalid[None, :] < 2) | p2_ok | (np.isneginf(second) & np.isneginf(c2v)), 0.0, -np.inf))
         vr = valid[None, :, :]
-        m6 = np.where(vr & ~is1, c2v[..., None] + beta[..., None] - E, np.inf)
+        m6 = np.where(vr & ~is1 & ~low, c2v[..., None] + beta[..., None] - E, np.inf)
         report("I6", m6, rows=True)
-        m7 = np.where(vr & ~is1 & ~is2, c3v[..., None] + beta[..., None] - E, np.inf)
+        m7 = np.where(vr & ~is1 & ~is2 & ~low, c3v[..., None] + beta[..., None] - E, np.inf)
         report("I7", m7, rows=True)
     tail = rec[B:]
     if tail.size:

@@ -4,7 +4,7 @@ Per query: candidate positions 0..m-1, each a global row (absent: -1, outside th
 sim(i, j) is the canonical score of oracle/dense_oracle.py with the STORED row j as the query: exact_scores(x16[row_j] as
 float32, x16[candidate rows], metric) -- a NaN counts as -inf.  pen (float32) is 0 before the first pick, afterwards the maximum
 of sim over the picked rows.  v = lam * float64(rel) - (1 - lam) * float64(pen): two products and a subtraction in float64 (numpy
-never fuses), a NaN v counts as -inf.  A step takes the greatest v among the present, unselected candidates, the lowest position
+never fuses), a term whose weight is exactly 0 being 0 whatever its other factor; a NaN v counts as -inf.  A step takes the greatest v among the present, unselected candidates, the lowest position
 on equal v.  k_eff = min(k, present); the rest is (0.0, -1, 0.0)."""
 from __future__ import annotations
 
@@ -22,8 +22,11 @@ def _sims(x16, picked_local, cand_local, metric):
 
 
 def _values(rel, pen, lam):
+    lam, oml = np.float64(lam), np.float64(1.0) - np.float64(lam)
     with np.errstate(invalid="ignore"):
-        v = np.float64(lam) * rel.astype(np.float64) - (np.float64(1.0) - np.float64(lam)) * pen.astype(np.float64)
+        gain = lam * rel.astype(np.float64) if lam != 0 else np.zeros(rel.shape)      # a term whose weight is exactly 0 is 0
+        loss = oml * pen.astype(np.float64) if oml != 0 else np.zeros(pen.shape)
+        v = gain - loss
     return np.where(np.isnan(v), -np.inf, v)
 
 

@@ -57,6 +57,29 @@ int main() {
         if (a == b && r1 != r2) CHECK((k1 > k2) == (r1 < r2), "a=%g r1=%u r2=%u", a, r1, r2);
         CHECK(rq_key_index(k1) == r1 && (rq_key_score(k1) == a || a == 0.f), "a=%g r1=%u", a, r1);
     }
+    // infinite scores are legitimate (include/rq.h): the key of -inf is a key -- not 0, the empty slot -- below every finite
+    // key whatever the rows, the key of +inf is above every finite key, and both come back as they went in
+    {
+        const float inf = std::numeric_limits<float>::infinity(), fmax = std::numeric_limits<float>::max();
+        const uint32_t far = 0xfffffffeu;                             // the largest row a key can carry
+        CHECK(rq_make_key(-inf, 0u) != 0 && rq_make_key(-inf, far) != 0, "key(-inf) is the empty key");
+        CHECK(rq_make_key(-inf, 0u) < rq_make_key(-fmax, far), "key(-inf, row 0) reaches key(-FLT_MAX, last row)");
+        CHECK(rq_make_key(inf, far) > rq_make_key(fmax, 0u), "key(+inf, last row) does not reach key(FLT_MAX, row 0)");
+        for (float f : v) {
+            if (std::isinf(f)) continue;
+            const uint32_t r = (uint32_t)(rng() % 1000000);
+            CHECK(rq_make_key(-inf, 0u) < rq_make_key(f, r) && rq_make_key(f, r) < rq_make_key(inf, far), "f=%g r=%u", f, r);
+        }
+        for (uint32_t r : {0u, 1u, 4100u, far}) {
+            for (float s : {inf, -inf}) {
+                const uint64_t k = rq_make_key(s, r);
+                CHECK(rq_key_score(k) == s && rq_key_index(k) == r, "s=%g r=%u", s, r);
+            }
+            CHECK((rq_make_key(-inf, r) > rq_make_key(-inf, r + 1u)) && (rq_make_key(inf, r) > rq_make_key(inf, r + 1u)), "r=%u", r);
+        }
+        // -0.0 ranks with +0.0 and is returned as +0.0
+        CHECK(rq_make_key(-0.f, 7u) == rq_make_key(0.f, 7u) && bits(rq_key_score(rq_make_key(-0.f, 7u))) == 0u, "-0.0 key");
+    }
     std::printf("%s: %zu values, %d failures\n", fails ? "FAILED" : "ok", v.size(), fails);
     return fails ? 1 : 0;
 }
