@@ -102,7 +102,8 @@ __global__ __launch_bounds__(64 * NW) void rq_nb_attention_kernel(const _Float16
     // padded batches: len[b] = valid tokens of sequence b, whose rows start at b * L.  Packed batches (no padding rows at all): len[] is the
     // offset table, sequence b = rows [len[b], len[b + 1])
     const int nraw = packed ? len[b + 1] - len[b] : len[b];
-    const int n = nraw < L ? nraw : L;                      // valid tokens (keys) of this sequence
+    const int n = nraw < L ? (nraw > 0 ? nraw : 0) : L;     // valid tokens (keys) of this sequence: a negative length is an empty
+                                                            // sequence (unclamped, the zero fill below would start before its rows)
     const size_t row0 = packed ? (size_t)len[b] : (size_t)b * L;
     const int ld = 3 * H;
     const rq_half8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -340,7 +341,8 @@ extern "C" int rq_nb_rope_table_f32(float* d_rope, int seq, float rope_theta, vo
 static int nb_attention_common(const void* d_qkv, const int* d_len, const float* d_rope, void* d_ctx, int batch, int seq, int heads, void* stream, int packed) {
     if (!d_qkv || !d_len || !d_rope || !d_ctx) return set_err(RQ_EINVAL, "null argument");
     if (batch < 1 || batch > 65535 || heads < 1 || heads > 65535) return set_err(RQ_EINVAL, "batch %d / heads %d outside 1..65535", batch, heads);
-    if (seq < 1 || seq > NB_MAX_SEQ) return set_err(RQ_EUNSUPPORTED, "sequence length %d outside 1..%d: use the framework's attention for longer inputs", seq, NB_MAX_SEQ);
+    if (seq < 1) return set_err(RQ_EINVAL, "sequence length %d", seq);
+    if (seq > NB_MAX_SEQ) return set_err(RQ_EUNSUPPORTED, "sequence length %d outside 1..%d: use the framework's attention for longer inputs", seq, NB_MAX_SEQ);
     const int nkmax = (seq + 31) & ~31;
     // two or more 4-wave workgroups per CU while their LDS allows it, else one of 8 waves; two query groups per wave from 129 tokens on
     // (below that a sequence has too few 32-query tiles for its waves)

@@ -363,8 +363,9 @@ const char* rq_version(void);
 int rq_nb_rope_table_f32(float* d_rope, int seq, float rope_theta, void* stream);
 /* ctx[b][t][:] = softmax(rot(q) rot(k)^T / 8 + prefix mask) v per head.  d_qkv [batch * seq][3 * heads * 64] (q | k | v of the
  * fused projection), d_len[batch] = valid tokens of each sequence (the first d_len[b] positions; padded rows come out zero),
- * rotary = rotate-half over the 64 dims with d_rope (at least seq rows).  seq <= 512 (RQ_EUNSUPPORTED beyond: use the
- * framework's attention). */
+ * rotary = rotate-half over the 64 dims with d_rope (at least seq rows).  1 <= seq <= 512 (RQ_EUNSUPPORTED beyond: use the
+ * framework's attention; RQ_EINVAL below).  The lengths live in device memory, so no host check sees them: d_len[b] > seq counts as seq, and a
+ * negative d_len[b] is an empty sequence -- its seq rows of ctx come out zero and nothing else is written. */
 int rq_nb_attention_f16(const void* d_qkv, const int* d_len, const float* d_rope, void* d_ctx, int batch, int seq, int heads, void* stream);
 /* The same for a PACKED batch -- no padding rows: the tokens of sequence b are rows [d_offsets[b], d_offsets[b + 1]) of d_qkv and d_ctx
  * (d_offsets: batch + 1 ascending ints, d_offsets[0] = 0), every sequence at most max_seq <= 512 tokens long.  The GEMMs around the
@@ -376,7 +377,8 @@ int rq_nb_add_layernorm_f16(const void* d_x, const void* d_res, const void* d_ga
                             float eps, void* stream);
 /* out[t][j] = silu(gate_up[t][j]) * gate_up[t][inter + j]: d_gate_up [rows][2 * inter] (gate | up), d_out [rows][inter]. */
 int rq_nb_swiglu_f16(const void* d_gate_up, void* d_out, int64_t rows, int inter, void* stream);
-/* d_out[b][:] (fp32) = mean of d_h[b][t][:] over the first d_len[b] tokens (0 for an empty sequence). */
+/* d_out[b][:] (fp32) = mean of d_h[b][t][:] over the first d_len[b] tokens (0 for an empty sequence).  d_len[b] > seq counts
+ * as seq, and a negative d_len[b] is an empty sequence: its row of d_out is 0. */
 int rq_nb_mean_pool_f16(const void* d_h, const int* d_len, float* d_out, int batch, int seq, int width, void* stream);
 /* ... of a packed batch: d_out[b][:] = mean of the rows [d_offsets[b], d_offsets[b + 1]) of d_h. */
 int rq_nb_mean_pool_packed_f16(const void* d_h, const int* d_offsets, float* d_out, int batch, int max_seq, int width, void* stream);
