@@ -287,12 +287,17 @@ class NativeIndex:
         return row_filter._h
 
     # -- search -----------------------------------------------------------------------------
-    def search(self, queries: np.ndarray, k: int, metric: int = METRIC_COSINE, *, row_filter: Optional[RowFilter] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def _as_queries(self, queries: np.ndarray) -> np.ndarray:
+        """The queries of a host-buffer call as contiguous float32 [B][dim]; one query may come as a vector."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"expected [B][{self.dim}] float32 queries, got {q.shape}")
+        return q
+
+    def search(self, queries: np.ndarray, k: int, metric: int = METRIC_COSINE, *, row_filter: Optional[RowFilter] = None) -> Tuple[np.ndarray, np.ndarray]:
+        q = self._as_queries(queries)
         B = q.shape[0]
         scores = np.empty((B, int(k)), dtype=np.float32)
         rows = np.empty((B, int(k)), dtype=np.int64)
@@ -338,11 +343,7 @@ class NativeIndex:
         """k of the exact top fetch_k rows per query by greedy maximal marginal relevance (include/rq.h rq_search_mmr): (scores, rows)
         in selection order, the scores being the rows' own search scores; return_mmr adds the value v of every pick."""
         self._check_mmr(k, fetch_k, lambda_mult, "fetch_k")
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"expected [B][{self.dim}] float32 queries, got {q.shape}")
+        q = self._as_queries(queries)
         B = q.shape[0]
         scores = np.empty((B, int(k)), dtype=np.float32)
         rows = np.empty((B, int(k)), dtype=np.int64)
@@ -374,11 +375,7 @@ class NativeIndex:
     def score_rows(self, queries: np.ndarray, rows: np.ndarray, metric: int = METRIC_COSINE) -> np.ndarray:
         """The exact score of every (query, row) pair of one list of GLOBAL rows per query (include/rq.h rq_score_rows): float32
         [B][m], position for position; an entry outside the index (-1 included) scores 0.0."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"expected [B][{self.dim}] float32 queries, got {q.shape}")
+        q = self._as_queries(queries)
         r = np.asarray(rows)
         if r.dtype.kind not in "iu":
             raise ValueError(f"rows must be integers, got {r.dtype}")

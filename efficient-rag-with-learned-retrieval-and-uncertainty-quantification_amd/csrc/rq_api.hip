@@ -24,6 +24,7 @@ int set_err(int code, const char* fmt, ...) {
     return code;
 }
 const char* rq_err_text() { return g_err; }
+int err_no_device() { return set_err(RQ_ENODEVICE, "RQ_ENODEVICE: no HIP device visible: the gfx950 backend has no CPU fallback"); }
 
 extern "C" int rq_device_count(void) {
     int n = 0;

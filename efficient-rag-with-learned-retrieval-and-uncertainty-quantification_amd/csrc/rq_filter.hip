@@ -10,6 +10,7 @@
 // rag_uq/streaming_index.py:355-359.
 #include "rq_filter_plan.h"
 #include "rq_rowdot.h"
+#include "rq_stage.h"
 
 // ---- kernels ------------------------------------------------------------------------------------
 __device__ __forceinline__ bool rq_filter_bit(const uint32_t* bits, int64_t row) { return (bits[row >> 5] >> (row & 31)) & 1u; }
@@ -141,7 +142,7 @@ static std::vector<uint32_t> filter_rows(const rq_filter* f, int64_t limit) {
 }
 
 static rq_filter* filter_create(rq_index* idx, const uint32_t* bits, int64_t n_rows, bool on_device, hipStream_t stream) {
-    if (rq_device_count() <= 0) { set_err(RQ_ENODEVICE, "RQ_ENODEVICE: no HIP device visible: the gfx950 backend has no CPU fallback"); return nullptr; }
+    if (rq_device_count() <= 0) { err_no_device(); return nullptr; }
     if (!idx || (!bits && n_rows > 0)) { set_err(RQ_EINVAL, "null argument"); return nullptr; }
     if (!idx->shards.empty()) { set_err(RQ_EUNSUPPORTED, "RQ_EUNSUPPORTED: filters on a multi-device index: use one index per device"); return nullptr; }
     if (n_rows != idx->n) { set_err(RQ_EINVAL, "the filter covers %lld rows, the index holds %lld", (long long)n_rows, (long long)idx->n); return nullptr; }
@@ -226,28 +227,19 @@ int check_filter(const rq_index* idx, const rq_filter* f) {
     return RQ_OK;
 }
 
-static int fill_padding(int B, int k, const SearchOut& out, hipStream_t s) {
-    HIPCHK(hipMemsetAsync(out.scores, 0, (size_t)B * k * sizeof(float), s));
-    HIPCHK(hipMemsetAsync(out.rows, 0xff, (size_t)B * k * sizeof(int64_t), s));
-    if (out.keys) HIPCHK(hipMemsetAsync(out.keys, 0, (size_t)B * k * sizeof(uint64_t), s));
-    HIPCHK(hipMemsetAsync(out.status, 0, (size_t)B * sizeof(int), s));
-    return RQ_OK;
-}
-
 // The gather route: groups of queries whose candidate keys (na each) stay within 1 GiB, as the exact rung bounds its own; the
 // prepared queries and the keys live in the stream's workspace like those of any other call.
 static int gather_route(rq_index* idx, rq_filter* f, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s) {
     if (int r = ensure_filter_list(f)) return r;
     const int64_t na = f->na;
-    const int group = (int)std::max<int64_t>(1, std::min<int64_t>(B, ((int64_t)1 << 30) / (na * (int64_t)sizeof(uint64_t))));
+    const int group = queries_per_gib(B, na);
     const QuerySet* qs = nullptr;
     uint64_t* cand = nullptr;
-    if (int r = filter_workspace(idx, s, (group + 63) / 64 * 64, (size_t)group * (size_t)na, &qs, &cand)) return r;
+    if (int r = scanless_workspace(idx, s, (group + 63) / 64 * 64, (size_t)group * (size_t)na, &qs, &cand)) return r;
     for (int off = 0; off < B; off += group) {
         const int g = std::min(group, B - off);
-        RqPrepArgs pa{};
-        pa.q = d_q + (size_t)off * idx->dim; pa.dim = idx->dim; pa.B = g; pa.nslots = (g + 63) / 64 * 64;
-        pa.qh = qs->qh; pa.q32pad = qs->q32; pa.qnorm64 = qs->qn;
+        const RqPrepArgs pa = prep_args(*qs, d_q + (size_t)off * idx->dim, idx->dim, g, (g + 63) / 64 * 64, false);
+        const SearchOut o = out.from(off, k);
         RqGatherArgs ga;
         ga.x = idx->x; ga.dpad = idx->dpad; ga.rownorm64 = idx->rownorm64; ga.q32 = qs->q32; ga.qnorm64 = qs->qn;
         ga.list = f->d_list; ga.nlist = na; ga.metric = metric; ga.cand = cand; ga.cand_stride = na;
@@ -255,8 +247,7 @@ static int gather_route(rq_index* idx, rq_filter* f, const float* d_q, int B, in
         fa.cand = cand; fa.ncand = (int)na; fa.binkeys = nullptr; fa.binkeys_stride = 0; fa.nb = 1; fa.nbins = 1;   // nbins <= nb: every row in play was re-scored
         fa.qnorm64 = qs->qn; fa.metric = metric; fa.eps = 0.f; fa.max_row_norm = 0.f; fa.k = k; fa.row_offset = idx->row_offset; fa.n_rows = na;
         fa.first = f->d_first;
-        fa.out_scores = out.scores + (size_t)off * k; fa.out_rows = out.rows + (size_t)off * k;
-        fa.out_keys = out.keys ? out.keys + (size_t)off * k : nullptr; fa.out_status = out.status + off;
+        fa.out_scores = o.scores; fa.out_rows = o.rows; fa.out_keys = o.keys; fa.out_status = o.status;
         HIPCHK(rq_prep_queries_launch(pa, s));
         HIPCHK(rq_gather_score_launch(ga, g, s));
         HIPCHK(rq_final_launch(fa, g, s));
@@ -274,21 +265,16 @@ int search_filtered_device(rq_index* idx, const rq_filter* cf, const float* d_q,
     const int route = plan_filter(idx, shape, B, k, metric, idx->filter_route);
     idx->filter_route_last = route;
     if (route == FROUTE_EMPTY) {
-        const QuerySet* qs = nullptr;
-        uint64_t* cand = nullptr;
-        if (int r = filter_workspace(idx, s, 0, 0, &qs, &cand)) return r;   // (the stream's last call ran no scan: the debug hooks say so)
-        return fill_padding(B, k, out, s);
+        if (int r = mark_no_scan(idx, s)) return r;
+        return fill_empty(B, k, out, s);
     }
     if (route == FROUTE_GATHER) return gather_route(idx, f, d_q, B, k, metric, out, s);
     if (route == FROUTE_SCAN) return run_pipeline(idx, d_q, B, k, metric, nb_default(idx, k), out, s, 0, f);
     // exact: the shard's fp64 scan in groups of queries (1 GiB of candidate keys, as rq_search_fixup_device's last rung)
-    const int64_t per_q = ((idx->n + 63) / 64) * 64 * (int64_t)sizeof(uint64_t);
-    const int group = (int)std::max<int64_t>(1, std::min<int64_t>(B, ((int64_t)1 << 30) / std::max<int64_t>(per_q, 1)));
+    const int group = queries_per_gib(B, (idx->n + 63) / 64 * 64);
     for (int off = 0; off < B; off += group) {
         const int g = std::min(group, B - off);
-        if (int r = run_pipeline(idx, d_q + (size_t)off * idx->dim, g, k, metric, -1,
-                                 {out.scores + (size_t)off * k, out.rows + (size_t)off * k, out.keys ? out.keys + (size_t)off * k : nullptr, out.status + off}, s, 0, f))
-            return r;
+        if (int r = run_pipeline(idx, d_q + (size_t)off * idx->dim, g, k, metric, -1, out.from(off, k), s, 0, f)) return r;
     }
     return RQ_OK;
 }
@@ -311,28 +297,20 @@ extern "C" int rq_search_fixup_filtered_device(rq_index* idx, const rq_filter* f
     return fixup_ladder(idx, f, d_queries, B, k, metric, d_scores, d_rows, d_keys, d_status, (hipStream_t)stream);
 }
 
-// The blocking host-buffer form: staged like rq_search's large path, on the index's own stream.
+// The blocking host-buffer form, on the index's own stream (rq_stage.h).
 extern "C" int rq_search_filtered(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int metric, float* out_scores, int64_t* out_rows) {
     if (int r = check_search_args(idx, queries, B, k, metric, out_scores, out_rows)) return r;
     if (int r = check_filter(idx, f)) return r;
     RQ_ON_DEVICE(idx);
-    hipStream_t s = idx->own_stream;
-    float* d_q = nullptr; float* d_scores = nullptr; int64_t* d_rows = nullptr; int* d_status = nullptr;
-    int rc = RQ_OK;
-    do {
-        if (hipMalloc((void**)&d_q, (size_t)B * idx->dim * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_scores, (size_t)B * k * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&d_rows, (size_t)B * k * sizeof(int64_t)) != hipSuccess || hipMalloc((void**)&d_status, (size_t)B * sizeof(int)) != hipSuccess) {
-            rc = set_err(RQ_ENOMEM, "staging of a filtered search of %d queries", B);
-            break;
-        }
-        if (hipMemcpyAsync(d_q, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) { rc = set_err(RQ_EHIP, "H2D copy failed"); break; }
-        if ((rc = search_filtered_device(idx, f, d_q, B, k, metric, {d_scores, d_rows, nullptr, d_status}, s)) != RQ_OK) break;
-        const int fr = fixup_ladder(idx, f, d_q, B, k, metric, d_scores, d_rows, nullptr, d_status, s);
-        if (fr < 0) { rc = fr; break; }
-        if (hipMemcpyAsync(out_scores, d_scores, (size_t)B * k * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(out_rows, d_rows, (size_t)B * k * sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            rc = set_err(RQ_EHIP, "D2H copy failed");
-    } while (0);
-    free_dev(d_q, d_scores, d_rows, d_status);
-    return rc;
+    const SearchStaging sz = search_staging(idx->dim, B, k);
+    const size_t bytes[4] = {sz.q, sz.scores, sz.rows, sz.status};
+    Stage st(idx->own_stream);
+    if (int r = st.alloc(bytes, 4, "a filtered search")) return r;
+    float* d_q = st.at<float>(0); float* d_scores = st.at<float>(1); int64_t* d_rows = st.at<int64_t>(2); int* d_status = st.at<int>(3);
+    if (int r = st.up(d_q, queries, sz.q)) return r;
+    if (int r = search_filtered_device(idx, f, d_q, B, k, metric, {d_scores, d_rows, nullptr, d_status}, st.s)) return r;
+    if (int r = fixup_ladder(idx, f, d_q, B, k, metric, d_scores, d_rows, nullptr, d_status, st.s); r < 0) return r;
+    st.down(out_scores, d_scores, sz.scores);
+    st.down(out_rows, d_rows, sz.rows);
+    return st.finish();
 }

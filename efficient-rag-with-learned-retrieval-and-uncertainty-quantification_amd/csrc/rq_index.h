@@ -1,6 +1,7 @@
 // rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
 // rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_scan8.hip (the int8 image and its ladder) and
-// rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard.
+// rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard, the pieces
+// of a call that the routes share.  The staging of the blocking host-buffer forms is rq_stage.h's.
 // Not part of the public boundary (that is include/rq.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -249,7 +250,11 @@ enum CallFlags : unsigned {
     CALL_FORCE_GENERIC = 2,   // the generic sorted tail, whatever "fast_tail" says
     CALL_ALLOW8 = 4,          // the int8 image may be the scan operand
 };
-struct SearchOut { float* scores; int64_t* rows; uint64_t* keys; int* status; };   // a call's device outputs (keys may be null)
+struct SearchOut {   // a call's device outputs (keys may be null); from: those of its queries from `off` on, k results each
+    float* scores; int64_t* rows; uint64_t* keys; int* status;
+    SearchOut from(int off, int k) const { return {scores + (size_t)off * k, rows + (size_t)off * k, keys ? keys + (size_t)off * k : nullptr, status + off}; }
+};
+RQ_INTERNAL int err_no_device();   // rq_api.hip: RQ_ENODEVICE and its message
 // rq_search.hip
 // filt (optional): the call ranks the filter's rows only (the caller has checked that it belongs to idx and is not stale)
 RQ_INTERNAL int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags,
@@ -260,7 +265,13 @@ RQ_INTERNAL int fixup_ladder(rq_index* idx, const rq_filter* filt, const float* 
 RQ_INTERNAL int check_search_args(const rq_index* idx, const void* q, int B, int k, int metric, const void* sc, const void* rows);
 RQ_INTERNAL int flush_tails(rq_index* idx, hipStream_t s);
 RQ_INTERNAL int ensure_ones(rq_index* idx, hipStream_t s);
-RQ_INTERNAL int filter_workspace(rq_index* idx, hipStream_t s, int bpad, size_t cand_elems, const QuerySet** qs, uint64_t** cand);
+RQ_INTERNAL int fill_empty(int B, int k, const SearchOut& out, hipStream_t s);   // the outputs of a call that has no row to return: padding, status 0
+// with_int8 = false: the int8 pointers stay null and the prepare kernel skips the int8 image (the routes that only re-score rows)
+RQ_INTERNAL RqPrepArgs prep_args(const QuerySet& qs, const float* q, int dim, int B, int nslots, bool with_int8);
+// The stream's workspace for a call that runs no scan (gather route, rq_score.hip): bpad prepared-query slots, cand_elems candidate
+// keys (either may be unwanted: null); the stream's last call then has no bin records.  mark_no_scan: only that record.
+RQ_INTERNAL int scanless_workspace(rq_index* idx, hipStream_t s, int bpad, size_t cand_elems, const QuerySet** qs, uint64_t** cand);
+RQ_INTERNAL int mark_no_scan(rq_index* idx, hipStream_t s);
 // rq_filter.hip
 RQ_INTERNAL void free_filters(rq_index* idx);   // rq_index_destroy: the filters the index still owns
 RQ_INTERNAL int ensure_filter_scale(rq_index* idx, const rq_filter* f, int metric, hipStream_t s);

@@ -11,6 +11,7 @@
 // max_marginal_relevance_search over the collection.query of reference rag_uq/streaming_index.py:355-359.
 #include "rq_mmr_plan.h"
 #include "rq_rowdot.h"
+#include "rq_stage.h"
 
 // ---- kernel -------------------------------------------------------------------------------------
 // (v, position) of the better of two candidates of a step: greater v, then lower position; position -1 = none.  v is never NaN.
@@ -156,21 +157,19 @@ static int mmr_select(rq_index* idx, const int64_t* d_cand_rows, const float* d_
     return RQ_OK;
 }
 
-static int no_device() { return set_err(RQ_ENODEVICE, "RQ_ENODEVICE: no HIP device visible: the gfx950 backend has no CPU fallback"); }
-
 extern "C" int rq_mmr_select_device(rq_index* idx, const int64_t* d_cand_rows, const float* d_cand_rel, int B, int m, int k, double lambda, int metric,
                                     float* d_scores, int64_t* d_rows, float* d_mmr, void* stream) {
-    if (!idx && rq_device_count() <= 0) return no_device();
+    if (!idx && rq_device_count() <= 0) return err_no_device();
     if (int r = check_mmr_select_args(idx, d_cand_rows, d_cand_rel, B, m, k, lambda, metric, d_scores, d_rows)) return r;
     RQ_ON_DEVICE(idx);
     return mmr_select(idx, d_cand_rows, d_cand_rel, B, m, k, lambda, metric, d_scores, d_rows, d_mmr, (hipStream_t)stream);
 }
 
-// The blocking host-buffer form: the exact top m = min(fetch_k, rows in play) staged as rq_search_filtered stages its call, on the
-// index's own stream; repaired by the ladder, so the candidates are exact; then the selection and the copies back.
+// The blocking host-buffer form, on the index's own stream (rq_stage.h): the exact top m = min(fetch_k, rows in play), repaired
+// by the ladder, so the candidates are exact; then the selection and the copies back.
 extern "C" int rq_search_mmr(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int fetch_k, double lambda, int metric,
                              float* out_scores, int64_t* out_rows, float* out_mmr) {
-    if (!idx && rq_device_count() <= 0) return no_device();
+    if (!idx && rq_device_count() <= 0) return err_no_device();
     if (int r = check_mmr_search_args(idx, queries, B, k, fetch_k, lambda, metric, out_scores, out_rows)) return r;
     if (f) if (int r = check_filter(idx, f)) return r;
     RQ_ON_DEVICE(idx);
@@ -181,33 +180,24 @@ extern "C" int rq_search_mmr(rq_index* idx, const rq_filter* f, const float* que
         return RQ_OK;
     }
     const int m = mmr_fetch(k, fetch_k, f ? f->na : idx->n);
-    const MmrStaging st = mmr_staging(idx->dim, B, m, k);
-    float* d_q = nullptr; float* d_cs = nullptr; int64_t* d_cr = nullptr; int* d_status = nullptr;
-    float* d_scores = nullptr; int64_t* d_rows = nullptr; float* d_mmr = nullptr;
-    int rc = RQ_OK;
-    do {
-        if (hipMalloc((void**)&d_q, st.q) != hipSuccess || hipMalloc((void**)&d_cs, st.cand_scores) != hipSuccess || hipMalloc((void**)&d_cr, st.cand_rows) != hipSuccess ||
-            hipMalloc((void**)&d_status, st.status) != hipSuccess || hipMalloc((void**)&d_scores, st.out_scores) != hipSuccess ||
-            hipMalloc((void**)&d_rows, st.out_rows) != hipSuccess || (out_mmr && hipMalloc((void**)&d_mmr, st.out_mmr) != hipSuccess)) {
-            rc = set_err(RQ_ENOMEM, "staging of an MMR search of %d queries, %d candidates each", B, m);
-            break;
-        }
-        if (hipMemcpyAsync(d_q, queries, st.q, hipMemcpyHostToDevice, s) != hipSuccess) { rc = set_err(RQ_EHIP, "H2D copy failed"); break; }
-        if (f) {
-            if ((rc = search_filtered_device(idx, f, d_q, B, m, metric, {d_cs, d_cr, nullptr, d_status}, s)) != RQ_OK) break;
-        } else {
-            idx->t.searches++;
-            idx->t.queries += B;
-            if ((rc = run_pipeline(idx, d_q, B, m, metric, nb_default(idx, m), {d_cs, d_cr, nullptr, d_status}, s, CALL_ALLOW8)) != RQ_OK) break;
-        }
-        const int fr = fixup_ladder(idx, f, d_q, B, m, metric, d_cs, d_cr, nullptr, d_status, s);
-        if (fr < 0) { rc = fr; break; }
-        if ((rc = mmr_select(idx, d_cr, d_cs, B, m, k, lambda, metric, d_scores, d_rows, d_mmr, s)) != RQ_OK) break;
-        if (hipMemcpyAsync(out_scores, d_scores, st.out_scores, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(out_rows, d_rows, st.out_rows, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            (out_mmr && hipMemcpyAsync(out_mmr, d_mmr, st.out_mmr, hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess)
-            rc = set_err(RQ_EHIP, "D2H copy failed");
-    } while (0);
-    free_dev(d_q, d_cs, d_cr, d_status, d_scores, d_rows, d_mmr);
-    return rc;
+    const MmrStaging sz = mmr_staging(idx->dim, B, m, k);
+    const size_t bytes[7] = {sz.q, sz.cand_scores, sz.cand_rows, sz.status, sz.out_scores, sz.out_rows, sz.out_mmr};
+    Stage st(s);
+    if (int r = st.alloc(bytes, out_mmr ? 7 : 6, "an MMR search")) return r;
+    float* d_q = st.at<float>(0); float* d_cs = st.at<float>(1); int64_t* d_cr = st.at<int64_t>(2); int* d_status = st.at<int>(3);
+    float* d_scores = st.at<float>(4); int64_t* d_rows = st.at<int64_t>(5); float* d_mmr = st.at<float>(6);   // (null without out_mmr)
+    if (int r = st.up(d_q, queries, sz.q)) return r;
+    if (f) {
+        if (int r = search_filtered_device(idx, f, d_q, B, m, metric, {d_cs, d_cr, nullptr, d_status}, s)) return r;
+    } else {
+        idx->t.searches++;
+        idx->t.queries += B;
+        if (int r = run_pipeline(idx, d_q, B, m, metric, nb_default(idx, m), {d_cs, d_cr, nullptr, d_status}, s, CALL_ALLOW8)) return r;
+    }
+    if (int r = fixup_ladder(idx, f, d_q, B, m, metric, d_cs, d_cr, nullptr, d_status, s); r < 0) return r;
+    if (int r = mmr_select(idx, d_cr, d_cs, B, m, k, lambda, metric, d_scores, d_rows, d_mmr, s)) return r;
+    st.down(out_scores, d_scores, sz.out_scores);
+    st.down(out_rows, d_rows, sz.out_rows);
+    if (out_mmr) st.down(out_mmr, d_mmr, sz.out_mmr);
+    return st.finish();
 }

@@ -12,26 +12,20 @@
 static inline int check_mmr_select_args(const rq_index* idx, const void* cand_rows, const void* cand_rel, int B, int m, int k, double lambda, int metric,
                                         const void* scores, const void* rows) {
     if (!idx || !cand_rows || !cand_rel || !scores || !rows) return set_err(RQ_EINVAL, "null argument");
-    if (B < 1 || B > 65535) return set_err(RQ_EINVAL, "B %d outside 1..65535", B);
     if (m < 1 || m > RQ_MAX_K) return set_err(RQ_EINVAL, "m %d outside 1..%d", m, RQ_MAX_K);
     if (k < 1 || k > m) return set_err(RQ_EINVAL, "k %d outside 1..m = %d", k, m);
     if (!(lambda >= 0.0 && lambda <= 1.0)) return set_err(RQ_EINVAL, "lambda %g outside [0, 1]", lambda);   // (NaN fails both comparisons)
-    if (metric != RQ_METRIC_COSINE && metric != RQ_METRIC_IP) return set_err(RQ_EINVAL, "unknown metric %d", metric);
-    if (!idx->shards.empty()) return set_err(RQ_EUNSUPPORTED, "RQ_EUNSUPPORTED: MMR selection on a multi-device index: use one index per device");
-    return RQ_OK;
+    return check_batch_metric(idx, B, metric, "MMR selection");
 }
 
 // ... and rq_search_mmr (the filter's own checks are rq_filter.hip's check_filter).
 static inline int check_mmr_search_args(const rq_index* idx, const void* queries, int B, int k, int fetch_k, double lambda, int metric, const void* scores,
                                         const void* rows) {
     if (!idx || !queries || !scores || !rows) return set_err(RQ_EINVAL, "null argument");
-    if (B < 1 || B > 65535) return set_err(RQ_EINVAL, "B %d outside 1..65535", B);
     if (fetch_k < 1 || fetch_k > RQ_MAX_K) return set_err(RQ_EINVAL, "fetch_k %d outside 1..%d", fetch_k, RQ_MAX_K);
     if (k < 1 || k > fetch_k) return set_err(RQ_EINVAL, "k %d outside 1..fetch_k = %d", k, fetch_k);
     if (!(lambda >= 0.0 && lambda <= 1.0)) return set_err(RQ_EINVAL, "lambda %g outside [0, 1]", lambda);
-    if (metric != RQ_METRIC_COSINE && metric != RQ_METRIC_IP) return set_err(RQ_EINVAL, "unknown metric %d", metric);
-    if (!idx->shards.empty()) return set_err(RQ_EUNSUPPORTED, "RQ_EUNSUPPORTED: MMR searches on a multi-device index: use one index per device");
-    return RQ_OK;
+    return check_batch_metric(idx, B, metric, "MMR searches");
 }
 
 // Candidates per query that rq_search_mmr searches for and hands to the selection: min(fetch_k, rows in play), but never fewer
@@ -57,13 +51,9 @@ static inline MmrGeometry mmr_geometry(const rq_index* idx, int B, int m) {
 // Device bytes the blocking rq_search_mmr stages (64-bit throughout: B x m x 8 alone reaches 512 MiB at the limits).
 struct MmrStaging { size_t q = 0, cand_scores = 0, cand_rows = 0, status = 0, out_scores = 0, out_rows = 0, out_mmr = 0; };
 static inline MmrStaging mmr_staging(int dim, int B, int m, int k) {
+    const SearchStaging cand = search_staging(dim, B, m), out = search_staging(dim, B, k);   // the search for m candidates, the k selected
     MmrStaging s;
-    s.q = (size_t)B * (size_t)dim * sizeof(float);
-    s.cand_scores = (size_t)B * (size_t)m * sizeof(float);
-    s.cand_rows = (size_t)B * (size_t)m * sizeof(int64_t);
-    s.status = (size_t)B * sizeof(int);
-    s.out_scores = (size_t)B * (size_t)k * sizeof(float);
-    s.out_rows = (size_t)B * (size_t)k * sizeof(int64_t);
-    s.out_mmr = (size_t)B * (size_t)k * sizeof(float);
+    s.q = cand.q; s.cand_scores = cand.scores; s.cand_rows = cand.rows; s.status = cand.status;
+    s.out_scores = out.scores; s.out_rows = out.rows; s.out_mmr = out.scores;
     return s;
 }

@@ -24,6 +24,28 @@ static inline int nb_default(const rq_index* idx, int k) {
     return k + slack;
 }
 
+// What the scoring and MMR calls (`what`) refuse alike: B outside 1..65535, an unknown metric and, last, a multi-device index.
+static inline int check_batch_metric(const rq_index* idx, int B, int metric, const char* what) {
+    if (B < 1 || B > 65535) return set_err(RQ_EINVAL, "B %d outside 1..65535", B);
+    if (metric != RQ_METRIC_COSINE && metric != RQ_METRIC_IP) return set_err(RQ_EINVAL, "unknown metric %d", metric);
+    if (!idx->shards.empty()) return set_err(RQ_EUNSUPPORTED, "RQ_EUNSUPPORTED: %s on a multi-device index: use one index per device", what);
+    return RQ_OK;
+}
+
+// Queries per group of a call that holds keys_per_query candidate keys for each: as many as keep the keys within 1 GiB, at
+// least one, at most B.  The exact scans hold ceil(n / 64) * 64 keys per query, the filter's gather route its allowed rows.
+static inline int queries_per_gib(int B, int64_t keys_per_query) {
+    const int64_t per_q = std::max<int64_t>(keys_per_query * (int64_t)sizeof(uint64_t), 1);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(B, ((int64_t)1 << 30) / per_q));
+}
+
+// Device bytes a blocking search of B queries for k results stages (rq_filter.hip; 64-bit throughout).
+struct SearchStaging { size_t q = 0, scores = 0, rows = 0, status = 0; };
+static inline SearchStaging search_staging(int dim, int B, int k) {
+    const size_t b = (size_t)B, bk = b * (size_t)k;
+    return {b * (size_t)dim * sizeof(float), bk * sizeof(float), bk * sizeof(int64_t), b * sizeof(int)};
+}
+
 #define RQ_SCAN8_MIN_ROWS 100000
 // ... and k <= 128 (beyond that the candidate sets of the looser bound outweigh the bytes saved)
 #define RQ_SCAN8_AUTO_MAX_K 128

@@ -9,6 +9,7 @@
 // queries, re-read from the caches by the workgroups in flight together) every query has its own list: a random whole-row gather.
 #include "rq_score_plan.h"
 #include "rq_rowdot.h"
+#include "rq_stage.h"
 
 // ---- kernel -------------------------------------------------------------------------------------
 // grid (queries of the group, ceil(m / RQ_SCORE_TILE)), 256 threads.  The workgroup keeps its query in LDS; a wave takes 8 list
@@ -76,27 +77,22 @@ hipError_t rq_score_rows_launch(const RqScoreArgs& a, int queries, hipStream_t s
 }
 
 // ---- entry points -------------------------------------------------------------------------------
-static int no_device() { return set_err(RQ_ENODEVICE, "RQ_ENODEVICE: no HIP device visible: the gfx950 backend has no CPU fallback"); }
-
 static int score_rows_device(rq_index* idx, const float* d_q, int B, const int64_t* d_rows, int m, int metric, float* d_scores, hipStream_t s) {
     // like a "pipeline" = 0 call: whatever the stream still defers is completed first (the prepared-query slots are the stream's)
     if (int r = flush_tails(idx, s)) return r;
     idx->score_calls++;
     idx->score_pairs += (int64_t)B * m;
-    const QuerySet* qs = nullptr;
-    uint64_t* cand = nullptr;
     if (idx->n == 0) {   // every entry is absent
-        if (int r = filter_workspace(idx, s, 0, 0, &qs, &cand)) return r;   // (the stream's last call ran no scan: the debug hooks say so)
+        if (int r = mark_no_scan(idx, s)) return r;
         HIPCHK(hipMemsetAsync(d_scores, 0, (size_t)B * (size_t)m * sizeof(float), s));
         return RQ_OK;
     }
     const ScoreGroups g = score_groups(B);
-    if (int r = filter_workspace(idx, s, g.slots, 0, &qs, &cand)) return r;
+    const QuerySet* qs = nullptr;
+    if (int r = scanless_workspace(idx, s, g.slots, 0, &qs, nullptr)) return r;
     for (int i = 0; i < g.count; ++i) {
         const int off = i * g.group, nq = std::min(g.group, B - off);
-        RqPrepArgs pa{};
-        pa.q = d_q + (size_t)off * idx->dim; pa.dim = idx->dim; pa.B = nq; pa.nslots = (nq + 63) / 64 * 64;
-        pa.qh = qs->qh; pa.q32pad = qs->q32; pa.qnorm64 = qs->qn;
+        const RqPrepArgs pa = prep_args(*qs, d_q + (size_t)off * idx->dim, idx->dim, nq, (nq + 63) / 64 * 64, false);
         const ScoreGeometry geo = score_geometry(idx, nq, m);
         RqScoreArgs a;
         a.x = idx->x; a.dpad = geo.dp; a.rownorm64 = idx->rownorm64; a.n_rows = idx->n; a.row_offset = idx->row_offset;
@@ -109,36 +105,25 @@ static int score_rows_device(rq_index* idx, const float* d_q, int B, const int64
 }
 
 extern "C" int rq_score_rows_device(rq_index* idx, const float* d_queries, int B, const int64_t* d_rows, int m, int metric, float* d_scores, void* stream) {
-    if (!idx && rq_device_count() <= 0) return no_device();
+    if (!idx && rq_device_count() <= 0) return err_no_device();
     if (int r = check_score_args(idx, d_queries, B, d_rows, m, metric, d_scores)) return r;
     RQ_ON_DEVICE(idx);
     return score_rows_device(idx, d_queries, B, d_rows, m, metric, d_scores, (hipStream_t)stream);
 }
 
-// The blocking host-buffer form: staged as rq_search_filtered stages its call, on the index's own stream.
+// The blocking host-buffer form, on the index's own stream (rq_stage.h).
 extern "C" int rq_score_rows(rq_index* idx, const float* queries, int B, const int64_t* rows, int m, int metric, float* out_scores) {
-    if (!idx && rq_device_count() <= 0) return no_device();
+    if (!idx && rq_device_count() <= 0) return err_no_device();
     if (int r = check_score_args(idx, queries, B, rows, m, metric, out_scores)) return r;
     RQ_ON_DEVICE(idx);
-    hipStream_t s = idx->own_stream;
-    const ScoreStaging st = score_staging(idx->dim, B, m);
-    float* d_q = nullptr; int64_t* d_rows = nullptr; float* d_scores = nullptr;
-    int rc = RQ_OK;
-    do {
-        if (hipMalloc((void**)&d_q, st.q) != hipSuccess || hipMalloc((void**)&d_rows, st.rows) != hipSuccess || hipMalloc((void**)&d_scores, st.scores) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = set_err(RQ_ENOMEM, "staging of %zu bytes to score %d rows for each of %d queries", st.total(), m, B);
-            break;
-        }
-        if (hipMemcpyAsync(d_q, queries, st.q, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(d_rows, rows, st.rows, hipMemcpyHostToDevice, s) != hipSuccess) {
-            rc = set_err(RQ_EHIP, "H2D copy failed");
-            break;
-        }
-        if ((rc = score_rows_device(idx, d_q, B, d_rows, m, metric, d_scores, s)) != RQ_OK) break;
-        if (hipMemcpyAsync(out_scores, d_scores, st.scores, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            rc = set_err(RQ_EHIP, "D2H copy failed");
-    } while (0);
-    if (rc != RQ_OK) (void)hipStreamSynchronize(s);   // (a failed call may have copies in flight on the buffers freed below)
-    free_dev(d_q, d_rows, d_scores);
-    return rc;
+    const ScoreStaging sz = score_staging(idx->dim, B, m);
+    const size_t bytes[3] = {sz.q, sz.rows, sz.scores};
+    Stage st(idx->own_stream);
+    if (int r = st.alloc(bytes, 3, "scoring given rows")) return r;
+    float* d_q = st.at<float>(0); int64_t* d_rows = st.at<int64_t>(1); float* d_scores = st.at<float>(2);
+    st.up(d_q, queries, sz.q);
+    if (int r = st.up(d_rows, rows, sz.rows)) return r;
+    if (int r = score_rows_device(idx, d_q, B, d_rows, m, metric, d_scores, st.s)) return r;
+    st.down(out_scores, d_scores, sz.scores);
+    return st.finish();
 }

@@ -14,11 +14,8 @@
 // What both entry points refuse (RQ_EINVAL unless noted).  The pointers are only tested for null.
 static inline int check_score_args(const rq_index* idx, const void* queries, int B, const void* rows, int m, int metric, const void* scores) {
     if (!idx || !queries || !rows || !scores) return set_err(RQ_EINVAL, "null argument");
-    if (B < 1 || B > 65535) return set_err(RQ_EINVAL, "B %d outside 1..65535", B);
     if (m < 1 || m > RQ_MAX_SCORE_ROWS) return set_err(RQ_EINVAL, "m %d outside 1..%d", m, RQ_MAX_SCORE_ROWS);
-    if (metric != RQ_METRIC_COSINE && metric != RQ_METRIC_IP) return set_err(RQ_EINVAL, "unknown metric %d", metric);
-    if (!idx->shards.empty()) return set_err(RQ_EUNSUPPORTED, "RQ_EUNSUPPORTED: scoring given rows on a multi-device index: use one index per device");
-    return RQ_OK;
+    return check_batch_metric(idx, B, metric, "scoring given rows");
 }
 
 // The call's queries in groups of at most RQ_SCORE_GROUP: group i = queries [i * group, min(B, (i + 1) * group)); every group is

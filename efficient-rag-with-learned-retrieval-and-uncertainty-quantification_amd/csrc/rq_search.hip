@@ -36,11 +36,11 @@ static hipError_t alloc_queries(QuerySet& q, size_t nslots, size_t* bytes) {
 }
 
 // Preparation of B queries at q into the first nslots slots of qs (one workgroup per slot: slots >= B are written as zero).
-static RqPrepArgs prep_args(const QuerySet& qs, const float* q, int dim, int B, int nslots) {
+RqPrepArgs prep_args(const QuerySet& qs, const float* q, int dim, int B, int nslots, bool with_int8) {
     RqPrepArgs pa{};
     pa.q = q; pa.dim = dim; pa.B = B; pa.nslots = nslots;
     pa.qh = qs.qh; pa.q32pad = qs.q32; pa.qnorm64 = qs.qn;
-    pa.q8 = qs.q8; pa.qscale8 = qs.qscale8; pa.qeps8 = qs.qeps8; pa.q8lo = qs.q8lo; pa.qeps8s = qs.qeps8s;
+    if (with_int8) { pa.q8 = qs.q8; pa.qscale8 = qs.qscale8; pa.qeps8 = qs.qeps8; pa.q8lo = qs.q8lo; pa.qeps8s = qs.qeps8s; }
     return pa;
 }
 
@@ -121,7 +121,7 @@ static int next_event_pair(rq_index* idx, hipEvent_t& e0, hipEvent_t& e1) {
 }
 
 // ---- one call ------------------------------------------------------------------------------------
-static int fill_empty(int B, int k, const SearchOut& out, hipStream_t s) {
+int fill_empty(int B, int k, const SearchOut& out, hipStream_t s) {
     HIPCHK(hipMemsetAsync(out.scores, 0, (size_t)B * k * sizeof(float), s));
     HIPCHK(hipMemsetAsync(out.rows, 0xff, (size_t)B * k * sizeof(int64_t), s));
     if (out.keys) HIPCHK(hipMemsetAsync(out.keys, 0, (size_t)B * k * sizeof(uint64_t), s));
@@ -240,7 +240,7 @@ static int pair_second(rq_index* idx, StreamCtx& cx, int B, int k, const SearchO
     t1.k = k; t1.m = (int)std::min<int64_t>(k, idx->n);
     t1.out_scores = out.scores; t1.out_rows = out.rows; t1.out_keys = out.keys; t1.out_status = out.status;
     RqPrepArgs pa{};
-    if (cx.hint_q) pa = prep_args(cx.ring[(slot + 1) % 3], cx.hint_q, idx->dim, cx.hint_B, 64);
+    if (cx.hint_q) pa = prep_args(cx.ring[(slot + 1) % 3], cx.hint_q, idx->dim, cx.hint_B, 64, true);
     if (int r = poison_cand(idx, cx.pair_tail, cx.pair_B, s)) return r;
     if (int r = poison_cand(idx, t1, B, s)) return r;
     HIPCHK(rq_pair_tail_launch(cx.pair_tail, cx.pair_B, t1, B, pa, s));
@@ -477,9 +477,7 @@ static int generic_tail(rq_index* idx, const Call& c, const Workspace& w) {
     return RQ_OK;
 }
 
-// The stream's workspace for a filtered call that runs no scan (rq_filter.hip: gather route, empty filter): bpad prepared-query
-// slots and cand_elems candidate keys; the stream's last call then has no bin records.
-int filter_workspace(rq_index* idx, hipStream_t s, int bpad, size_t cand_elems, const QuerySet** qs, uint64_t** cand) {
+int scanless_workspace(rq_index* idx, hipStream_t s, int bpad, size_t cand_elems, const QuerySet** qs, uint64_t** cand) {
     if (idx->ctx.find(s) == idx->ctx.end() && idx->ctx.size() >= RQ_MAX_STREAM_CTX)
         if (int r = release_contexts(idx, nullptr)) return r;
     StreamCtx& cx = idx->ctx[s];
@@ -487,9 +485,11 @@ int filter_workspace(rq_index* idx, hipStream_t s, int bpad, size_t cand_elems, 
     if (bpad > 0)
         if (int r = ensure_ws(w, bpad, 64, 1, cand_elems)) return r;
     set_records(cx, nullptr, 0, 0, 0);
-    *qs = &w.qs; *cand = w.cand;
+    if (qs) *qs = &w.qs;
+    if (cand) *cand = w.cand;
     return RQ_OK;
 }
+int mark_no_scan(rq_index* idx, hipStream_t s) { return scanless_workspace(idx, s, 0, 0, nullptr, nullptr); }   // (the debug hooks say so)
 
 // One pass of the pipeline for B queries.  nb < 0: exact scan (every bin re-scored, no corpus scan).  flags: CallFlags (rq_index.h).
 int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags,
@@ -553,10 +553,10 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
     const bool prepared = fused && cx.prepped_q == d_q && cx.prepped_B == B && cx.prepped_slot == c.slot;
     cx.prepped_q = nullptr;
     if (prepared) idx->hints_used++;
-    else HIPCHK(rq_prep_queries_launch(prep_args(qs, d_q, idx->dim, B, p.bpad), s));
+    else HIPCHK(rq_prep_queries_launch(prep_args(qs, d_q, idx->dim, B, p.bpad, true), s));
     // the queries announced for the NEXT call are prepared by extra workgroups of this call's fused launch
     RqPrepArgs pa{};
-    if (fused && cx.hint_q) pa = prep_args(cx.ring[(c.slot + 1) % 3], cx.hint_q, idx->dim, cx.hint_B, 64);
+    if (fused && cx.hint_q) pa = prep_args(cx.ring[(c.slot + 1) % 3], cx.hint_q, idx->dim, cx.hint_B, 64, true);
     if (c.pair) {
         // the pass reads the announced batch from the next ring slot: it is prepared first, by a launch of its own; and a tail
         // still waiting for a scan (the call before this one was not paired) runs on its own, as the wide pass carries none
@@ -707,13 +707,10 @@ int fixup_ladder(rq_index* idx, const rq_filter* filt, const float* d_queries, i
         } else {
             idx->t.exact_scans += nbq;
             // bound the candidate memory: a few queries per exact pass
-            const int64_t per_q = ((idx->n + 63) / 64) * 64 * (int64_t)sizeof(uint64_t);
-            const int group = (int)std::max<int64_t>(1, std::min<int64_t>(nbq, ((int64_t)1 << 30) / std::max<int64_t>(per_q, 1)));
+            const int group = queries_per_gib(nbq, (idx->n + 63) / 64 * 64);
             for (int off = 0; off < nbq; off += group) {
                 const int g = std::min(group, nbq - off);
-                if (int r = run_pipeline(idx, w.fix_q + (size_t)off * idx->dim, g, k, metric, -1,
-                                         {w.fix_scores + (size_t)off * k, w.fix_rows + (size_t)off * k, w.fix_keys + (size_t)off * k, w.fix_status + off}, s, allow8, filt))
-                    return r;
+                if (int r = run_pipeline(idx, w.fix_q + (size_t)off * idx->dim, g, k, metric, -1, fix_out.from(off, k), s, allow8, filt)) return r;
             }
         }
         std::vector<int> st2((size_t)nbq);

@@ -161,6 +161,13 @@ int main() {
         narrow_index(nar, BIG);
         CHECK(!scan8_wanted(&nar, 64, 10, 18, DEFER8), "narrow rows have no int8 image");
     }
+    {   // ---- queries per group: as many as keep keys_per_query 8-byte keys each within 1 GiB (2^27 keys), in 1..B -------------------
+        CHECK(queries_per_gib(64, 0) == 64 && queries_per_gib(64, 1) == 64 && queries_per_gib(65535, 1) == 65535, "0 or 1 key per query: the whole batch");
+        CHECK(queries_per_gib(64, (int64_t)1 << 27) == 1 && queries_per_gib(64, ((int64_t)1 << 27) - 1) == 1 && queries_per_gib(64, (int64_t)1 << 26) == 2, "the quotient is exactly 1, then 2");
+        CHECK(queries_per_gib(1, ((int64_t)1 << 27) + 64) == 1 && queries_per_gib(64, (int64_t)1 << 31) == 1, "one query beyond 1 GiB still runs, alone");
+        CHECK(queries_per_gib(3, 1000) == 3 && queries_per_gib(1, 1) == 1, "B below the quotient");
+        CHECK(queries_per_gib(65535, 4160) == 32263 && queries_per_gib(500, (1000000 + 63) / 64 * 64) == 134, "4 101 rows padded to 4 160 keys; 1M rows");
+    }
     std::printf("%d failures\n", fails);
     return fails ? 1 : 0;
 }

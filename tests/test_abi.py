@@ -119,7 +119,9 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     record / key codecs of csrc/rq_device.h, (b) the multi-device parent of csrc/rq_multi.hip -- stripe arithmetic, row read-back,
     k-way merge incl. its threads, the poisoned / failed-search paths -- behind STUBBED shards (tests/native/multi_check.cpp),
     (c) librq_bm25's scorer (csrc/rq_bm25.cpp compiled into tests/native/bm25_check.cpp), (d) the call plan of csrc/rq_plan.h --
-    route, pass cutting, scan grids, non-temporal rule -- on a host-built rq_index (tests/native/plan_check.cpp).  Any report aborts the program."""
+    route, pass cutting, scan grids, non-temporal rule -- on a host-built rq_index (tests/native/plan_check.cpp), (e) the staging of the
+    blocking host-buffer calls, csrc/rq_stage.h, behind stand-ins for the HIP calls it makes: every allocation and every copy fails in turn
+    (tests/native/stage_check.cpp).  Any report aborts the program."""
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -131,7 +133,8 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     jobs = [([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "codec_check.cpp")], "codec"),
             ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "multi_check.cpp")], "multi"),
             ([gxx, *san, "-I", os.path.join(ROOT, "include"), os.path.join(native, "bm25_check.cpp"), os.path.join(CSRC, "rq_bm25.cpp")], "bm25"),
-            ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "plan_check.cpp")], "plan")]
+            ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "plan_check.cpp")], "plan"),
+            ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "stage_check.cpp")], "stage")]
     for cmd, name in jobs:
         exe = str(tmp_path / f"{name}_san")
         subprocess.run(cmd + ["-o", exe], check=True, timeout=600, capture_output=True)
