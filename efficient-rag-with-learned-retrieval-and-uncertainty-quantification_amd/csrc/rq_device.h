@@ -77,6 +77,23 @@ __host__ __device__ static inline float rq_code16_value(uint32_t c) {
     return rq_unmono32(k);
 }
 
+// The last step of the exactness certificate (rq_select.hip rq_final_kernel, rq_final_body.h), once.  b: an upper bound of the
+// approximate score of every row that was NOT re-scored (the (nb+1)-th bin's maximum, or the fast tail's threshold T), in
+// unit-query units; such a row's exact score is at most b + eps (cosine) or (b + eps * max_row_norm) * qn (inner product).
+// Certified iff that bound is strictly below the k-th exact score s_k.  (float)bound rounds to nearest, which is monotone and
+// leaves the fp32 value s_k where it is: (float)bound < s_k implies bound < s_k.
+// The inner product's part in a million of slack (over the fp64 roundings of the product) must RAISE the bound: a negative
+// bound is multiplied by 1 - 1e-6.  Until this function existed both copies multiplied by 1 + 1e-6 whatever the sign, which
+// lowered a negative bound: -1 became -1.000001 and certified against s_k = -1.0000005 (tests/native/cert_check.cpp).
+__host__ __device__ static inline bool rq_certified(double b, float eps, float max_row_norm, double qn, int metric, float s_k) {
+    double bound = b + (double)eps;
+    if (metric != 0) {
+        const double v = (b + (double)eps * (double)max_row_norm) * qn;
+        bound = v >= 0 ? v * (1.0 + 1e-6) : v * (1.0 - 1e-6);
+    }
+    return (float)bound < s_k;
+}
+
 #ifdef __HIPCC__
 // ---- selection with the row position inside the score (rq_scan_wide.hip, rq_scan.hip EPI = 1) ----------------------
 // A score is clamped to the finite range (an infinite score stays the largest, NaN becomes the smallest), its 6 low

@@ -175,11 +175,7 @@ __device__ __forceinline__ void rq_final_body(const RqFinalCore& a, int total, i
         else if (a.metric == 0 && qn < RQ_TINY_QUERY_NORM) good = 0;                     // the 1e-30 of the score definition is no longer negligible
         else if (T == -__builtin_huge_valf()) good = have >= kk;        // every row was a candidate
         else if (have < kk || kth == 0) good = 0;
-        else {
-            const double bound = a.metric == 0 ? (double)T + (double)a.eps
-                                               : ((double)T + (double)a.eps * (double)a.max_row_norm) * qn * (1.0 + 1e-6);
-            good = (float)bound < rq_key_score(kth);
-        }
+        else good = rq_certified((double)T, a.eps, a.max_row_norm, qn, a.metric, rq_key_score(kth));
         *a.out_status = good ? 0 : 1;
     }
 }

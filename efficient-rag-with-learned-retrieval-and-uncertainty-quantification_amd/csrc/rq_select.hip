@@ -422,11 +422,8 @@ __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a)
                 ok = 1;
             } else {
                 const double b = (double)rq_key_score(bkey);
-                const double qn = a.qnorm64[q];
-                const double bound = a.metric == 0 ? b + (double)a.eps
-                                                   : (b + (double)a.eps * (double)a.max_row_norm) * qn * (1.0 + 1e-6);
                 const float sk = rq_key_score(list[kk - 1]);
-                ok = ((float)bound < sk) ? 1 : 0;   // (a zero-norm query never comes here: answered above)
+                ok = rq_certified(b, a.eps, a.max_row_norm, a.qnorm64[q], a.metric, sk) ? 1 : 0;   // (a zero-norm query never comes here: answered above)
             }
         }
         a.out_status[q] = ok ? 0 : 1;

@@ -114,6 +114,22 @@ def test_record_codec_properties_on_the_host(tmp_path):
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
 
 
+def test_certificate_expression_is_sound_on_the_host(tmp_path):
+    """csrc/rq_device.h rq_certified, the one copy of the certificate's last step (rq_select.hip rq_final_kernel and rq_final_body.h call it),
+    compiled for the host with hipcc: over a sweep of bounds of both signs with s_k on and within a few ulps of the bound, "certified"
+    implies that the bound evaluated in long double without slack is strictly below s_k (tests/native/cert_check.cpp)."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    src = os.path.join(os.path.dirname(__file__), "native", "cert_check.cpp")
+    exe = str(tmp_path / "cert_check")
+    subprocess.run([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-I", CSRC, src, "-o", exe], check=True, timeout=600)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "0 failures" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+
+
 def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     """CPU-only sanitizer builds (the GPU boxes of this pool cannot run sanitizers): -fsanitize=address,undefined over (a) the
     record / key codecs of csrc/rq_device.h, (b) the multi-device parent of csrc/rq_multi.hip -- stripe arithmetic, row read-back,
@@ -121,7 +137,8 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     (c) librq_bm25's scorer (csrc/rq_bm25.cpp compiled into tests/native/bm25_check.cpp), (d) the call plan of csrc/rq_plan.h --
     route, pass cutting, scan grids, non-temporal rule -- on a host-built rq_index (tests/native/plan_check.cpp), (e) the staging of the
     blocking host-buffer calls, csrc/rq_stage.h, behind stand-ins for the HIP calls it makes: every allocation and every copy fails in turn
-    (tests/native/stage_check.cpp).  Any report aborts the program."""
+    (tests/native/stage_check.cpp), (f) the certificate's last step, csrc/rq_device.h rq_certified (tests/native/cert_check.cpp).  Any report
+    aborts the program."""
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -134,7 +151,8 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
             ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "multi_check.cpp")], "multi"),
             ([gxx, *san, "-I", os.path.join(ROOT, "include"), os.path.join(native, "bm25_check.cpp"), os.path.join(CSRC, "rq_bm25.cpp")], "bm25"),
             ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "plan_check.cpp")], "plan"),
-            ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "stage_check.cpp")], "stage")]
+            ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "stage_check.cpp")], "stage"),
+            ([hipcc, "--offload-host-only", *san, "-I", CSRC, os.path.join(native, "cert_check.cpp")], "cert")]
     for cmd, name in jobs:
         exe = str(tmp_path / f"{name}_san")
         subprocess.run(cmd + ["-o", exe], check=True, timeout=600, capture_output=True)
