@@ -74,6 +74,11 @@ _SIGNATURES = {
     "rq_search_mmr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_score_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rq_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "rq_search_range_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_range_fixup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int]),
     "rq_nb_rope_table_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
@@ -396,6 +401,57 @@ class NativeIndex:
         self._check_score(B, m, metric)
         _check(self._lib.rq_score_rows_device(self._h, _ptr(d_queries), int(B), _ptr(d_rows), int(m), int(metric), _ptr(d_scores), C.c_void_p(stream)),
                "rq_score_rows_device")
+
+    # -- range searches (include/rq.h "range searches") ---------------------------------------------------
+    @staticmethod
+    def _check_range(B: int, cap: int, metric: int) -> None:
+        if not 1 <= int(B) <= 65535:
+            raise ValueError(f"B {B} outside 1..65535")
+        if not 1 <= int(cap) <= MAX_K:
+            raise ValueError(f"cap {cap} outside 1..{MAX_K}")
+        if int(metric) not in (METRIC_COSINE, METRIC_IP):
+            raise ValueError(f"unknown metric {metric!r}")
+
+    def search_range(self, queries: np.ndarray, threshold, cap: int, metric: int = METRIC_COSINE, *,
+                     row_filter: Optional[RowFilter] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Every row scoring at least `threshold` (a scalar, or one value per query): (scores [B][cap], rows [B][cap], counts [B]).
+        counts is exact also beyond cap; the rows are the best min(count, cap) in the canonical order, (0.0, -1) padded
+        (include/rq.h rq_search_range)."""
+        q = self._as_queries(queries)
+        B = q.shape[0]
+        self._check_range(B, cap, metric)
+        thr = np.asarray(threshold, dtype=np.float32)
+        if thr.ndim == 0:
+            thr = np.full(B, thr, dtype=np.float32)
+        if thr.shape != (B,):
+            raise ValueError(f"threshold must be a scalar or [{B}] values, one per query, got {thr.shape}")
+        if not np.isfinite(thr).all():
+            raise ValueError("every threshold must be finite")
+        thr = np.ascontiguousarray(thr)
+        scores = np.empty((B, int(cap)), dtype=np.float32)
+        rows = np.empty((B, int(cap)), dtype=np.int64)
+        counts = np.empty(B, dtype=np.int64)
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        _check(self._lib.rq_search_range(self._h, flt, _ptr(q), B, _ptr(thr), int(cap), int(metric), _ptr(scores), _ptr(rows), _ptr(counts)),
+               "rq_search_range")
+        return scores, rows, counts
+
+    def search_range_device(self, d_queries, B: int, d_thr, cap: int, metric: int, d_scores, d_rows, d_keys, d_count, d_status, stream: int = 0, *,
+                            row_filter: Optional[RowFilter] = None) -> None:
+        """Asynchronous form over device memory (include/rq.h rq_search_range_device): d_thr [B] fp32, d_count [B] int64, d_status [B]
+        int32 (1 = repair that query with search_range_fixup_device); complete in stream order."""
+        self._check_range(B, cap, metric)
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        _check(self._lib.rq_search_range_device(self._h, flt, _ptr(d_queries), int(B), _ptr(d_thr), int(cap), int(metric), _ptr(d_scores), _ptr(d_rows),
+                                                _ptr(d_keys), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)), "rq_search_range_device")
+
+    def search_range_fixup_device(self, d_queries, B: int, d_thr, cap: int, metric: int, d_scores, d_rows, d_keys, d_count, d_status, stream: int = 0, *,
+                                  row_filter: Optional[RowFilter] = None) -> int:
+        self._check_range(B, cap, metric)
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        return _check(self._lib.rq_search_range_fixup_device(self._h, flt, _ptr(d_queries), int(B), _ptr(d_thr), int(cap), int(metric), _ptr(d_scores),
+                                                             _ptr(d_rows), _ptr(d_keys), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)),
+                      "rq_search_range_fixup_device")
 
     def search_hint_next_device(self, d_next_queries, B: int, stream: int = 0) -> None:
         """Announce the queries of the NEXT search_device call on `stream` (include/rq.h: rq_search_hint_next_device)."""

@@ -117,6 +117,7 @@ extern "C" void rq_index_destroy(rq_index* idx) {
     (void)hipDeviceSynchronize();
     for (auto& kv : idx->ctx) free_ctx(kv.second);
     free_filters(idx);   // the filters nobody destroyed (include/rq.h rq_filter_destroy)
+    free_dev(idx->range_bins);
     for (auto& ev : idx->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (idx->hs_pin) (void)hipHostFree(idx->hs_pin);
     if (idx->hs_pin_q) (void)hipHostFree(idx->hs_pin_q);
@@ -287,6 +288,8 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     else if (s == "use_hint") idx->use_hint = (int)v != 0;   // 0: rq_search_hint_next_device is ignored (A/B of the folded query preparation)
     else if (s == "scan_ahead") idx->scan_ahead = (int)v != 0;   // 0: a hinted batch is never scanned together with the call before it (A/B)
     else if (s == "filter_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "filter_route must be -1 (rule), 1 (gather), 2 (scan) or 3 (exact)"); idx->filter_route = (int)v; }   // rq_filter_plan.h
+    else if (s == "range_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "range_route must be -1 (rule), 1 (scan), 2 (gather) or 3 (exact)"); idx->range_route = (int)v; }   // rq_range_plan.h
+    else if (s == "range_cand_cap") { if (v < 0 || v > (1 << 20)) return set_err(RQ_EINVAL, "range_cand_cap must be 0 (default) .. 1048576"); idx->range_cand_cap = (int)v; }   // test hook (never below a call's cap)
     else if (s == "poison_cand") idx->poison_cand = (int)v;   // test hook: candidate lists are filled with 0xff..ff keys before every tail
     else if (s == "poison_bins") idx->poison_bins = (int)v;   // test hook: the query slots a call's passes cover are filled with 0xff bytes before its scan
     else return set_err(RQ_EINVAL, "unknown option '%s'", name);
@@ -356,6 +359,18 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
     if (s == "mmr_calls") return (double)idx->mmr_calls;   // MMR selections launched (rq_mmr_select_device, rq_search_mmr)
     if (s == "score_calls") return (double)idx->score_calls;   // scoring calls (rq_score_rows_device, rq_score_rows)
     if (s == "score_pairs") return (double)idx->score_pairs;   // ... and the (query, row) pairs they were given: B x m each
+    if (s == "range_route") return idx->range_route;
+    if (s == "range_route_last") return idx->range_route_last;   // the route the last range call took (0: no row to return; -1: none yet)
+    if (s == "range_calls") return (double)idx->range_calls;     // range calls (rq_search_range_device, rq_search_range)
+    if (s == "range_repaired") return (double)idx->range_repaired;   // queries the range fixup re-ran on the exact route
+    if (s == "range_cand_cap") return idx->range_cand_cap;
+    if (s == "range_bins_last") {   // bins the last range call's tail re-scored, all queries (-1: it did not take the scan route); waits for the device
+        if (!idx->range_bins_valid || !idx->range_bins) return -1.0;
+        DeviceGuard dg_(idx->device);
+        unsigned long long v = 0;
+        if (!dg_.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, idx->range_bins, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return NAN;
+        return (double)v;
+    }
     if (s == "repaired_queries") return (double)idx->repaired_total;   // queries rq_search_fixup_device (or the blocking rq_search) had to repair so far
     if (s == "scan8_used") return (double)idx->scan8_used;   // searches that scanned the int8 image
     if (s == "hints_used") return (double)idx->hints_used;   // searches that found their queries prepared by the launch before them

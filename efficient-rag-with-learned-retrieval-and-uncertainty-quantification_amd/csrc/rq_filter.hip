@@ -210,7 +210,7 @@ int ensure_filter_scale(rq_index* idx, const rq_filter* cf, int metric, hipStrea
     return RQ_OK;
 }
 
-static int ensure_filter_list(rq_filter* f) {
+int ensure_filter_list(rq_filter* f) {
     if (f->d_list) return RQ_OK;
     const std::vector<uint32_t> rows = filter_rows(f, f->na);
     if (hipMalloc((void**)&f->d_list, rows.size() * sizeof(uint32_t)) != hipSuccess) return set_err(RQ_ENOMEM, "hipMalloc of %zu listed rows failed", rows.size());

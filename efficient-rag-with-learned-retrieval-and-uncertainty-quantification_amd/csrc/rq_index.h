@@ -1,5 +1,5 @@
 // rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
-// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_scan8.hip (the int8 image and its ladder) and
+// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_range.hip (range searches), rq_scan8.hip (the int8 image and its ladder) and
 // rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard, the pieces
 // of a call that the routes share.  The staging of the blocking host-buffer forms is rq_stage.h's.
 // Not part of the public boundary (that is include/rq.h).
@@ -73,6 +73,12 @@ struct Workspace {
     int64_t* fix_rows = nullptr;
     uint64_t* fix_keys = nullptr;
     int* fix_status = nullptr;
+    // range searches (rq_range.hip): per query slot the candidate keys appended so far, the status rq_final_kernel writes (unused: the
+    // range kernels write the caller's), a norm of 1.0 for rq_final_kernel (the keys of a zero-norm query are already its answer)
+    int rg_bcap = 0;
+    unsigned* rg_slot = nullptr;
+    int* rg_status = nullptr;
+    double* rg_one = nullptr;
 };
 
 // Per caller stream: two workspaces (alternating calls), an internal tail stream and the events that
@@ -210,6 +216,13 @@ struct rq_index {
     int64_t filter_repaired = 0;       // queries of filtered calls that came back uncertified and were repaired
     int64_t mmr_calls = 0;             // option "mmr_calls": MMR selections launched (rq_mmr.hip)
     int64_t score_calls = 0, score_pairs = 0;   // options "score_calls" / "score_pairs": scoring calls and their B x m pairs (rq_score.hip)
+    // range searches (rq_range.hip)
+    int range_route = -1;              // option "range_route": -1 = the rule (rq_range_plan.h), 1 scan, 2 gather, 3 exact
+    int range_route_last = -1;         // the route the last range call took (0 = no row to return, -1 = none yet)
+    int range_cand_cap = 0;            // option "range_cand_cap": qualifying rows a query may hold before it overflows (0 = the plan's default)
+    int64_t range_calls = 0, range_repaired = 0;   // calls so far; queries the range fixup repaired
+    unsigned long long* range_bins = nullptr;      // device: bins the last scan-route call re-scored, all queries ("range_bins_last")
+    bool range_bins_valid = false;
 };
 
 // Derived bound on |approximate scan score - exact score| for unit queries and cosine scaling:
@@ -250,6 +263,12 @@ enum CallFlags : unsigned {
     CALL_FORCE_GENERIC = 2,   // the generic sorted tail, whatever "fast_tail" says
     CALL_ALLOW8 = 4,          // the int8 image may be the scan operand
 };
+// A call that ends after its scan passes (rq_range.hip: the range tail reads the bin records itself).  In: the candidate keys the
+// workspace must hold.  Out: where the call's records, prepared queries and candidate keys are.
+struct ScanOnly {
+    size_t cand_elems = 0;
+    Workspace* w = nullptr;
+};
 struct SearchOut {   // a call's device outputs (keys may be null); from: those of its queries from `off` on, k results each
     float* scores; int64_t* rows; uint64_t* keys; int* status;
     SearchOut from(int off, int k) const { return {scores + (size_t)off * k, rows + (size_t)off * k, keys ? keys + (size_t)off * k : nullptr, status + off}; }
@@ -258,7 +277,7 @@ RQ_INTERNAL int err_no_device();   // rq_api.hip: RQ_ENODEVICE and its message
 // rq_search.hip
 // filt (optional): the call ranks the filter's rows only (the caller has checked that it belongs to idx and is not stale)
 RQ_INTERNAL int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags,
-                             const rq_filter* filt = nullptr);
+                             const rq_filter* filt = nullptr, ScanOnly* scan_only = nullptr);
 // the repair ladder of rq_search_fixup_device; filt: of rq_search_fixup_filtered_device (no int8 rung, no int8 accounting)
 RQ_INTERNAL int fixup_ladder(rq_index* idx, const rq_filter* filt, const float* d_queries, int B, int k, int metric, float* d_scores,
                              int64_t* d_rows, uint64_t* d_keys, int* d_status, hipStream_t s);
@@ -272,10 +291,12 @@ RQ_INTERNAL RqPrepArgs prep_args(const QuerySet& qs, const float* q, int dim, in
 // keys (either may be unwanted: null); the stream's last call then has no bin records.  mark_no_scan: only that record.
 RQ_INTERNAL int scanless_workspace(rq_index* idx, hipStream_t s, int bpad, size_t cand_elems, const QuerySet** qs, uint64_t** cand);
 RQ_INTERNAL int mark_no_scan(rq_index* idx, hipStream_t s);
+RQ_INTERNAL int ensure_range_ws(Workspace& w, int bpad);   // the rg_* arrays for bpad query slots (rq_range.hip)
 // rq_filter.hip
 RQ_INTERNAL void free_filters(rq_index* idx);   // rq_index_destroy: the filters the index still owns
 RQ_INTERNAL int ensure_filter_scale(rq_index* idx, const rq_filter* f, int metric, hipStream_t s);
 RQ_INTERNAL int check_filter(const rq_index* idx, const rq_filter* f);   // null, another index's, stale, multi-device
+RQ_INTERNAL int ensure_filter_list(rq_filter* f);   // f->d_list: every allowed row, ascending (the gather routes)
 RQ_INTERNAL int search_filtered_device(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s);
 RQ_INTERNAL int flush_all(rq_index* idx);   // launches every tail still waiting for a scan ("pipeline" = 2)
 RQ_INTERNAL void free_ctx(StreamCtx& c);

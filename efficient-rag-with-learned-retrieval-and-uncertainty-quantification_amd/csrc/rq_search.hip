@@ -77,6 +77,18 @@ static int ensure_ws(Workspace& w, int bpad, int64_t stride, int64_t m, size_t c
     return RQ_OK;
 }
 
+int ensure_range_ws(Workspace& w, int bpad) {
+    if (bpad <= w.rg_bcap) return RQ_OK;
+    w.rg_bcap = 0;
+    if (int r = ensure(w.rg_slot, (size_t)bpad)) return r;
+    if (int r = ensure(w.rg_status, (size_t)bpad)) return r;
+    if (int r = ensure(w.rg_one, (size_t)bpad)) return r;
+    const std::vector<double> one((size_t)bpad, 1.0);
+    HIPCHK(hipMemcpy(w.rg_one, one.data(), one.size() * sizeof(double), hipMemcpyHostToDevice));
+    w.rg_bcap = bpad;
+    return RQ_OK;
+}
+
 int ensure_ones(rq_index* idx, hipStream_t s) {
     if (idx->ones && idx->ones_valid == idx->n) return RQ_OK;
     if (!idx->ones) HIPCHK(hipMalloc((void**)&idx->ones, (size_t)idx->cap * sizeof(float)));
@@ -90,6 +102,7 @@ int ensure_ones(rq_index* idx, hipStream_t s) {
 static void free_ws(Workspace& w) {
     free_queries(w.qs);
     free_dev(w.bins, w.binkeys, w.cand, w.wgmax, w.rowcount, w.thr, w.done, w.ovf, w.fix_q, w.fix_scores, w.fix_rows, w.fix_keys, w.fix_status);
+    free_dev(w.rg_slot, w.rg_status, w.rg_one);
     w = Workspace();
 }
 
@@ -493,7 +506,7 @@ int mark_no_scan(rq_index* idx, hipStream_t s) { return scanless_workspace(idx, 
 
 // One pass of the pipeline for B queries.  nb < 0: exact scan (every bin re-scored, no corpus scan).  flags: CallFlags (rq_index.h).
 int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int nb, const SearchOut& out, hipStream_t s, unsigned flags,
-                 const rq_filter* filt) {
+                 const rq_filter* filt, ScanOnly* scan_only) {
     if (idx->n == 0) {
         if (auto it = idx->ctx.find(s); it != idx->ctx.end()) set_records(it->second, nullptr, 0, 0, 0);
         return fill_empty(B, k, out, s);
@@ -530,7 +543,7 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
     if (int r = enter_stream(idx, cx, c)) return r;
     Workspace& w = cx.w[c.par];
     // (a pair: the announced batch's records, candidates and counters take query slots 64..127 of the same workspace)
-    if (int r = ensure_ws(w, c.pair ? 128 : p.bpad, p.exact ? 64 : p.stride, p.exact ? 1 : p.m, (size_t)(c.pair ? 128 : B) * (size_t)p.ncand)) return r;
+    if (int r = ensure_ws(w, c.pair ? 128 : p.bpad, p.exact ? 64 : p.stride, p.exact ? 1 : p.m, std::max((size_t)(c.pair ? 128 : B) * (size_t)p.ncand, scan_only ? scan_only->cand_elems : (size_t)0))) return r;
     c.scale = idx->inv_norm;
     if (metric == RQ_METRIC_IP) { if (int r = ensure_ones(idx, s)) return r; c.scale = idx->ones; }
     if (filt) {   // excluded rows get a NaN scale, like pad rows: no scan form tests a row's validity
@@ -570,6 +583,7 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
     c.grid_narrow = scan_grid(idx, p.nquads, scan_wg_per_cu(idx, c));
     c.nwg_split = c.pair ? 64 : p.nwg_split;   // both batches of a pair: the wide grid
     if (p.exact) {
+        if (scan_only) return set_err(RQ_EINVAL, "internal: a scan-only call on a shard whose plan is the exact scan");   // (rq_range_plan.h asks plan_call first)
         set_records(cx, nullptr, 0, 0, 0);
         return generic_tail(idx, c, w);
     }
@@ -577,6 +591,7 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
     set_records(cx, w.bins, w.bins_stride, c.pair ? 64 + cx.pair_qB : B, slots);
     if (int r = poison_bins(idx, w.bins, w.bins_stride, slots, s)) return r;
     if (int r = scan_passes(idx, cx, w, qs, c, pa)) return r;
+    if (scan_only) { scan_only->w = &w; return RQ_OK; }   // a range search: its own tail reads the records (rq_range.hip)
     if (!p.fast) return generic_tail(idx, c, w);
     if (idx->tail_stop) w.counters_zero = false;   // a truncated tail does not reset its counters
     const RqTailArgs ta = tail_args(idx, c, w, qs);

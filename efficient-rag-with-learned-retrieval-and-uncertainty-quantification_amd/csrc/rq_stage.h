@@ -1,4 +1,4 @@
-// rq_stage.h -- the staging buffers of ONE blocking host-buffer call on one stream (rq_search_filtered, rq_search_mmr, rq_score_rows):
+// rq_stage.h -- the staging buffers of ONE blocking host-buffer call on one stream (rq_search_filtered, rq_search_mmr, rq_score_rows, rq_search_range and its repair):
 // alloc, up, the device form, down, finish.  The first failure sticks: every later step returns it and issues nothing.  A call that
 // leaves with work enqueued that finish() has not waited for -- whichever step failed, the device form's included -- waits for the
 // stream before anything is freed: no copy is in flight on freed buffers or into the caller's memory when it returns.

@@ -924,6 +924,55 @@ class DenseIndex:
         scores = host[2 * B * k: 3 * B * k].view(np.float32).reshape(B, k)
         return scores, rows
 
+    # ---- range searches (extension: every passage at least this similar, and how many there are -- what a caller of reference
+    # :355-359's collection.query gets by fetching n_results and cutting the list; include/rq.h rq_search_range) -----------------
+    def _range_index(self):
+        if self._index is not None and (not hasattr(self._index, "search_range") or len(getattr(self._index, "devices", [0])) > 1):
+            raise _native.RqError("search_threshold / count_above need a single-device index")
+        return self._index
+
+    def _range_rows(self, vectors: np.ndarray, threshold, cap: int, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(scores [B][cap], rows [B][cap] -1 padded, counts [B]) of the passages scoring at least `threshold` (a scalar or one value
+        per query) under this index's metric.  counts is exact also beyond cap."""
+        vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
+        B = vectors.shape[0]
+        cap = max(1, min(int(cap), _native.MAX_K))
+        index = self._range_index()
+        if index is None or len(self._ids) == 0 or B == 0:
+            return np.zeros((B, cap), np.float32), np.full((B, cap), -1, np.int64), np.zeros(B, np.int64)
+        if vectors.shape[1] != self.dim:
+            raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
+        if allowed_ids is None:
+            return index.search_range(vectors, threshold, cap, self.metric)
+        own = not isinstance(allowed_ids, _native.RowFilter)
+        flt = self.make_filter(allowed_ids) if own else allowed_ids
+        try:
+            return index.search_range(vectors, threshold, cap, self.metric, row_filter=flt)
+        finally:
+            if own:
+                flt.close()
+
+    def search_threshold_vectors(self, vectors: np.ndarray, threshold, max_results: int = 100, *, allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
+        """Per query vector the passages scoring at least `threshold`, best first, at most max_results (<= 1024) of them:
+        [(doc_id, score, text)].  An empty list is the answer "nothing is similar enough"."""
+        if max_results <= 0 or self._range_index() is None or len(self._ids) == 0:
+            return [[] for _ in range(np.atleast_2d(np.asarray(vectors)).shape[0])]
+        scores, rows, _ = self._range_rows(vectors, threshold, max_results, allowed_ids)
+        return self._assemble(scores, rows)
+
+    def search_threshold_batch(self, queries: Sequence[str], threshold, max_results: int = 100, *, allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
+        if not queries:
+            return []
+        return self.search_threshold_vectors(self._embed_matrix(list(queries)), threshold, max_results, allowed_ids=allowed_ids)
+
+    def search_threshold(self, query: str, threshold: float, max_results: int = 100, *, allowed_ids=None) -> List[Tuple[str, float, str]]:
+        """List of (doc_id, score, text) of the passages whose score is at least `threshold`, best first.  `allowed_ids` as in `search`."""
+        return self.search_threshold_batch([query], threshold, max_results, allowed_ids=allowed_ids)[0]
+
+    def count_above(self, query: str, threshold: float, *, allowed_ids=None) -> int:
+        """How many passages (of `allowed_ids`, when given) score at least `threshold` for `query`: exact, whatever the number."""
+        return int(self._range_rows(self._embed_matrix([query]), threshold, 1, allowed_ids)[2][0])
+
     # ---- scoring given passages (extension: the dense score of a passage the dense search did not return; Chroma scores only what
     # its query returns, reference :355-359, so the reference's fusion writes 0.0 there, :498-499) -----------------------------------
     def _scoring_index(self):
@@ -1178,6 +1227,12 @@ class HybridRetriever:
         if self.dense_index is None:
             return []
         return [(doc_id, score) for doc_id, score, _ in self.dense_index.search_mmr(query, top_k, fetch_k, lambda_mult, allowed_ids=allowed_ids)]
+
+    def dense_search_threshold(self, query: str, threshold: float, max_results: int = 100, *, allowed_ids=None) -> List[Tuple[str, float]]:
+        """Every passage whose dense score is at least `threshold`, best first, at most max_results (DenseIndex.search_threshold)."""
+        if self.dense_index is None:
+            return []
+        return [(doc_id, score) for doc_id, score, _ in self.dense_index.search_threshold(query, threshold, max_results, allowed_ids=allowed_ids)]
 
     def dense_search_batch(self, queries: Sequence[str], top_k: int = 20) -> List[List[Tuple[str, float]]]:
         if self.dense_index is None:

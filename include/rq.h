@@ -26,7 +26,7 @@
  *   ip:      s = fp32( dot64(q, x) )
  *   order:   s descending, then row ascending;  k_eff = min(k, N);  missing entries row = -1.
  * Non-finite and extreme inputs, both metrics, every route (rq_search, the *_device forms, trains, multi-device indexes, filtered
- * searches, rq_search_mmr's candidates, rq_score_rows; tests/nonfinite_oracle.py restates it):
+ * searches, rq_search_mmr's candidates, rq_score_rows, rq_search_range; tests/nonfinite_oracle.py restates it):
  *   zero-norm query: a query whose fp64 norm is 0 scores every row 0.0, whatever the row holds (a NaN or infinite row included):
  *            its answer is rows 0 .. k_eff-1 (filtered: the first k_eff allowed rows) at 0.0.
  *   NaN:     any other score that comes out NaN (a NaN element on either side, inf - inf, 0 x inf, inf / inf -- under cosine every
@@ -261,6 +261,58 @@ int rq_search_mmr(rq_index* idx, const rq_filter* f, const float* queries, int B
 int rq_score_rows_device(rq_index* idx, const float* d_queries, int B, const int64_t* d_rows, int m, int metric,
                          float* d_scores, void* stream);
 int rq_score_rows(rq_index* idx, const float* queries, int B, const int64_t* rows, int m, int metric, float* out_scores);
+
+/* ---- range searches: every row that scores at least a threshold (what a caller of the collection.query of reference
+ * rag_uq/streaming_index.py:355-359 gets today by fetching k rows and cutting the list on the host -- abstaining when no passage is
+ * relevant enough, near-duplicate checks on ingest, "how many passages clear the bar") ------------------------------------------
+ * For query q with threshold thr[q] (fp32):
+ *   score: the score definition above on the STORED fp16 row; a NaN score counts as -inf, -0.0 is +0.0, a zero-norm query scores
+ *     every row 0.0 -- the rules of every search.
+ *   a row qualifies iff its returned fp32 score s satisfies s >= thr[q]: the comparison is on the fp32 values, after the NaN and
+ *     -0.0 rules.  With a filter f (may be NULL) only allowed rows can qualify.
+ *   count[q] (int64) = the number of qualifying rows.  It is exact, also when it exceeds cap.
+ *   outputs [B][cap]: the min(count[q], cap) best qualifying rows in the canonical order (score descending, then row ascending),
+ *     global rows = row_offset + local row; entries beyond that are (0.0, -1), with key 0 where keys are asked for.
+ *   thr[q] must be finite.  Where the host can see the thresholds (rq_search_range) a NaN or infinite threshold is RQ_EINVAL; in the
+ *     device forms a non-finite d_thr[q] makes that query return nothing, with count 0 and status 0.
+ *   Hence a zero-norm query returns rows 0 .. min(N, cap) - 1 at 0.0 with count N when thr <= 0 and nothing when thr > 0; filtered,
+ *     the first allowed rows and the allowed count.  An empty index returns count 0 and padding.
+ *   same bits as every other route: a row's score is the value rq_score_rows and rq_search return for that pair (csrc/rq_rowdot.h), so
+ *     thr = that value includes the row and nextafter(thr, +inf) excludes it.
+ * RQ_EINVAL unless 1 <= cap <= RQ_MAX_K, 1 <= B <= 65535, a known metric and non-null pointers (d_keys and f aside); the filter checks
+ *   are those of rq_search_filtered (another index's filter, a stale filter: RQ_EINVAL); RQ_EUNSUPPORTED on a multi-device index;
+ *   RQ_ENODEVICE as everywhere.
+ * rq_search_range_device: asynchronous, device pointers, no host synchronisation.  It behaves like a "pipeline" = 0 call, as
+ *   rq_search_filtered_device does: it first completes whatever `stream` still defers (a fused tail, a scanned-ahead pair, a hint) and
+ *   its results are complete in stream order.  It never touches the int8 image, and with a filter its scans keep to the forms that
+ *   honour a NaN row scale.  d_status[B]: 0 = complete, 1 = this query's outputs are not (its qualifying rows overflowed the candidate
+ *   list -- d_count[q] is exact already -- or the query is NaN / infinite): call rq_search_range_fixup_device with the SAME arguments.
+ * rq_search_range_fixup_device: synchronises `stream`, re-runs the queries whose d_status is non-zero on the exact route, patches
+ *   d_scores / d_rows / d_keys / d_count / d_status in place.  Returns the number repaired.
+ * rq_search_range: blocking, host buffers, staged on the index's own stream like rq_search_filtered (repair included):
+ *   B x (dim x 4 + cap x 12 + 16) bytes of HBM for the call (RQ_ENOMEM with a message when that fails).
+ * Routes (csrc/rq_range_plan.h); results never depend on the route.  No row to return (an empty index, a filter that allows none)
+ *   -> padding.  SCAN (1), the hot path: the call's usual fp16 scan passes, then a range tail that walks the query's bin records
+ *   (csrc/rq_device.h): a 64-row bin is skipped iff the certificate's last step, with thr in the place of the k-th score, proves
+ *   that none of its rows reaches thr; every other bin's rows are re-scored exactly.  The cost is one scan plus the bins that clear
+ *   the bar: a threshold that most bins clear re-scores most of the shard.  GATHER (2), filtered calls only: exactly the allowed
+ *   rows are re-scored, when B x allowed <= rows and 4 x allowed <= rows (the measured rule of rq_search_filtered).  EXACT (3): the
+ *   fp64 scan of the shard, keys below thr emptied -- when the scan's scores say nothing (the "eps" rule of rq_search), and for the
+ *   queries the fixup repairs.
+ * Not extended: rq_search_train_device, hints, "scan_ahead", "pipeline" 1 and 2, multi-device indexes, the int8 image.  More than
+ *   RQ_MAX_K rows per query are not returned; the count is still exact.
+ * rq_timing counts a range call as a search (searches, queries; repaired queries as exact_scans).
+ * Options: "range_route" (-1 = the rule (default), 1 = scan, 2 = gather (filtered calls), 3 = exact: forces a route, for tests and
+ *   A/B); "range_cand_cap" (test hook: qualifying rows a query of the scan route may hold before it overflows; 0 = default 4096, never
+ *   below cap); read-only "range_route_last" (the route the last range call took: 0 = no row to return, 1..3, -1 = none yet),
+ *   "range_calls" (calls so far, both entry points), "range_repaired" (queries repaired by the fixup), "range_bins_last" (bins the
+ *   last call's range tail re-scored, summed over its queries; -1 = it did not take the scan route; waits for the device). */
+int rq_search_range_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, const float* d_thr, int cap, int metric,
+                           float* d_scores, int64_t* d_rows, uint64_t* d_keys, int64_t* d_count, int* d_status, void* stream);
+int rq_search_range_fixup_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, const float* d_thr, int cap, int metric,
+                                 float* d_scores, int64_t* d_rows, uint64_t* d_keys, int64_t* d_count, int* d_status, void* stream);
+int rq_search_range(rq_index* idx, const rq_filter* f, const float* queries, int B, const float* thr, int cap, int metric,
+                    float* out_scores, int64_t* out_rows, int64_t* out_count);
 
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
