@@ -22,6 +22,7 @@ METRIC_IP = 1
 MAX_DIM = 768
 MAX_K = 1024
 MAX_SCORE_ROWS = 65536
+GROUP_NONE = -1
 
 
 class RqError(RuntimeError):
@@ -79,6 +80,15 @@ _SIGNATURES = {
     "rq_search_range_fixup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_index_set_groups": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "rq_index_get_groups": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "rq_group_collapse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_grouped_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "rq_search_grouped_fixup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int]),
     "rq_nb_rope_table_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
@@ -452,6 +462,78 @@ class NativeIndex:
         return _check(self._lib.rq_search_range_fixup_device(self._h, flt, _ptr(d_queries), int(B), _ptr(d_thr), int(cap), int(metric), _ptr(d_scores),
                                                              _ptr(d_rows), _ptr(d_keys), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)),
                       "rq_search_range_fixup_device")
+
+    # -- grouped searches (include/rq.h "grouped searches") -----------------------------------------------
+    @staticmethod
+    def _check_grouped(B: int, k: int, m: int, metric: int, what: str = "m") -> None:
+        if not 1 <= int(B) <= 65535:
+            raise ValueError(f"B {B} outside 1..65535")
+        if not 1 <= int(m) <= MAX_K:
+            raise ValueError(f"{what} {m} outside 1..{MAX_K}")
+        if not 1 <= int(k) <= int(m):
+            raise ValueError(f"k {k} outside 1..{what} = {m}")
+        if int(metric) not in (METRIC_COSINE, METRIC_IP):
+            raise ValueError(f"unknown metric {metric!r}")
+
+    def set_groups(self, groups, row_begin: int = 0) -> None:
+        """Group ids (int32; GROUP_NONE = -1: a group of its own) of the LOCAL rows [row_begin, row_begin + len(groups))
+        (include/rq.h rq_index_set_groups).  Blocking; rows appended later are GROUP_NONE."""
+        g = np.asarray(groups)
+        if g.dtype.kind not in "iu" or g.ndim != 1:
+            raise ValueError(f"groups must be a vector of integers, got {g.dtype} {g.shape}")
+        if g.size and (int(g.min()) < GROUP_NONE or int(g.max()) > 2 ** 31 - 1):
+            raise ValueError(f"group ids must lie within {GROUP_NONE}..2^31 - 1")
+        if int(row_begin) < 0:
+            raise ValueError(f"row_begin {row_begin} is negative")
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        _check(self._lib.rq_index_set_groups(self._h, int(row_begin), int(g.size), _ptr(g) if g.size else None), "rq_index_set_groups")
+
+    def get_groups(self, row_begin: int = 0, n_rows: Optional[int] = None) -> np.ndarray:
+        if int(row_begin) < 0 or (n_rows is not None and int(n_rows) < 0):
+            raise ValueError("row_begin and n_rows must not be negative")
+        n = len(self) - int(row_begin) if n_rows is None else int(n_rows)
+        out = np.empty(max(n, 0), dtype=np.int32)
+        _check(self._lib.rq_index_get_groups(self._h, int(row_begin), n, _ptr(out) if out.size else None), "rq_index_get_groups")
+        return out
+
+    def search_grouped(self, queries: np.ndarray, k: int, metric: int = METRIC_COSINE, *, row_filter: Optional[RowFilter] = None
+                       ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The best row of each of the k best groups per query (include/rq.h rq_search_grouped): (scores [B][k], rows [B][k],
+        groups [B][k]), best group first, (0.0, -1, GROUP_NONE) padded beyond the distinct groups among the rows in play."""
+        q = self._as_queries(queries)
+        B = q.shape[0]
+        self._check_grouped(B, k, MAX_K, metric, "MAX_K")
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        scores = np.empty((B, int(k)), dtype=np.float32)
+        rows = np.empty((B, int(k)), dtype=np.int64)
+        groups = np.empty((B, int(k)), dtype=np.int32)
+        _check(self._lib.rq_search_grouped(self._h, flt, _ptr(q), B, int(k), int(metric), _ptr(scores), _ptr(rows), _ptr(groups)), "rq_search_grouped")
+        return scores, rows, groups
+
+    def search_grouped_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_groups, d_keys, d_status, stream: int = 0, *,
+                              row_filter: Optional[RowFilter] = None) -> None:
+        """Asynchronous form over device memory (include/rq.h rq_search_grouped_device): d_groups [B][k] int32, d_status [B] int32
+        (1 = repair that query with search_grouped_fixup_device); complete in stream order."""
+        self._check_grouped(B, k, MAX_K, metric, "MAX_K")
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        _check(self._lib.rq_search_grouped_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(metric), _ptr(d_scores), _ptr(d_rows), _ptr(d_groups),
+                                                  _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)), "rq_search_grouped_device")
+
+    def search_grouped_fixup_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_groups, d_keys, d_status, stream: int = 0, *,
+                                    row_filter: Optional[RowFilter] = None) -> int:
+        self._check_grouped(B, k, MAX_K, metric, "MAX_K")
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        return _check(self._lib.rq_search_grouped_fixup_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(metric), _ptr(d_scores), _ptr(d_rows),
+                                                               _ptr(d_groups), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)),
+                      "rq_search_grouped_fixup_device")
+
+    def group_collapse_device(self, d_cand_rows, d_cand_scores, d_cand_groups, B: int, m: int, k: int, d_scores, d_rows, d_groups, d_keys, d_status,
+                              stream: int = 0) -> None:
+        """Asynchronous collapse of a caller's candidates [B][m] in device memory (include/rq.h rq_group_collapse_device);
+        d_cand_groups None = the groups are looked up by row in the index."""
+        self._check_grouped(B, k, m, METRIC_COSINE)
+        _check(self._lib.rq_group_collapse_device(self._h, _ptr(d_cand_rows), _ptr(d_cand_scores), _ptr(d_cand_groups), int(B), int(m), int(k), _ptr(d_scores),
+                                                  _ptr(d_rows), _ptr(d_groups), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)), "rq_group_collapse_device")
 
     def search_hint_next_device(self, d_next_queries, B: int, stream: int = 0) -> None:
         """Announce the queries of the NEXT search_device call on `stream` (include/rq.h: rq_search_hint_next_device)."""

@@ -62,7 +62,18 @@ static int grow(rq_index* idx, int64_t want_rows) {
     // row scales of the pad rows are NaN (0xffffffff): their scan scores sort last without a per-score row test
     // (rq_scan_wide.hip); rq_scan.hip masks rows >= n on its own
     HIPCHK(hipMemsetAsync(ni + keep, 0xff, (size_t)(cap - keep) * sizeof(float), idx->own_stream));
+    int32_t* ng = nullptr;   // the group ids follow the rows once a group has been set (rq_group.hip); rows beyond `keep` are RQ_GROUP_NONE (0xffffffff)
+    if (idx->d_groups) {
+        if (hipMalloc((void**)&ng, (size_t)cap * sizeof(int32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            free_dev(nx, nn, ni);
+            return set_err(RQ_ENOMEM, "hipMalloc of the group ids of %lld rows failed", (long long)cap);
+        }
+        if (keep > 0) HIPCHK(hipMemcpyAsync(ng, idx->d_groups, (size_t)keep * sizeof(int32_t), hipMemcpyDeviceToDevice, idx->own_stream));
+        HIPCHK(hipMemsetAsync(ng + keep, 0xff, (size_t)(cap - keep) * sizeof(int32_t), idx->own_stream));
+    }
     HIPCHK(hipStreamSynchronize(idx->own_stream));
+    if (ng) { (void)hipFree(idx->d_groups); idx->d_groups = ng; }
     if (idx->x) (void)hipFree(idx->x);
     if (idx->rownorm64) (void)hipFree(idx->rownorm64);
     if (idx->inv_norm) (void)hipFree(idx->inv_norm);
@@ -117,7 +128,7 @@ extern "C" void rq_index_destroy(rq_index* idx) {
     (void)hipDeviceSynchronize();
     for (auto& kv : idx->ctx) free_ctx(kv.second);
     free_filters(idx);   // the filters nobody destroyed (include/rq.h rq_filter_destroy)
-    free_dev(idx->range_bins);
+    free_dev(idx->range_bins, idx->d_groups);
     for (auto& ev : idx->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (idx->hs_pin) (void)hipHostFree(idx->hs_pin);
     if (idx->hs_pin_q) (void)hipHostFree(idx->hs_pin_q);
@@ -154,6 +165,7 @@ static int finish_add(rq_index* idx, int64_t n_new) {
     HIPCHK(hipStreamSynchronize(s));
     idx->max_row_norm = st[0]; idx->max_sub_rel = st[1]; idx->max_sub_abs = st[2];
     idx->n = e;
+    if (idx->d_groups) idx->h_groups.resize((size_t)e, RQ_GROUP_NONE);   // appended rows are groups of their own (the device side: grow)
     return RQ_OK;
 }
 
@@ -290,6 +302,8 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     else if (s == "filter_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "filter_route must be -1 (rule), 1 (gather), 2 (scan) or 3 (exact)"); idx->filter_route = (int)v; }   // rq_filter_plan.h
     else if (s == "range_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "range_route must be -1 (rule), 1 (scan), 2 (gather) or 3 (exact)"); idx->range_route = (int)v; }   // rq_range_plan.h
     else if (s == "range_cand_cap") { if (v < 0 || v > (1 << 20)) return set_err(RQ_EINVAL, "range_cand_cap must be 0 (default) .. 1048576"); idx->range_cand_cap = (int)v; }   // test hook (never below a call's cap)
+    else if (s == "group_fetch") { if (!(v >= 1 && v <= RQ_MAX_K)) return set_err(RQ_EINVAL, "group_fetch must be 1..%d", RQ_MAX_K); idx->group_fetch = (int)v; }   // rq_group_plan.h group_fetch
+    else if (s == "group_fetch_cap") { if (!(v >= 0 && v <= RQ_MAX_K)) return set_err(RQ_EINVAL, "group_fetch_cap must be 0 (default) .. %d", RQ_MAX_K); idx->group_fetch_cap = (int)v; }   // test hook (never below a call's k)
     else if (s == "poison_cand") idx->poison_cand = (int)v;   // test hook: candidate lists are filled with 0xff..ff keys before every tail
     else if (s == "poison_bins") idx->poison_bins = (int)v;   // test hook: the query slots a call's passes cover are filled with 0xff bytes before its scan
     else return set_err(RQ_EINVAL, "unknown option '%s'", name);
@@ -371,6 +385,11 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
         if (!dg_.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, idx->range_bins, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return NAN;
         return (double)v;
     }
+    if (s == "group_fetch") return idx->group_fetch;
+    if (s == "group_fetch_cap") return idx->group_fetch_cap;
+    if (s == "group_calls") return (double)idx->group_calls;         // collapses launched (rq_group_collapse_device, rq_search_grouped*)
+    if (s == "group_repaired") return (double)idx->group_repaired;   // queries the grouped fixup repaired
+    if (s == "group_rounds_last") return (double)idx->group_rounds_last;   // exclusion rounds of the last grouped fixup, all its queries
     if (s == "repaired_queries") return (double)idx->repaired_total;   // queries rq_search_fixup_device (or the blocking rq_search) had to repair so far
     if (s == "scan8_used") return (double)idx->scan8_used;   // searches that scanned the int8 image
     if (s == "hints_used") return (double)idx->hints_used;   // searches that found their queries prepared by the launch before them

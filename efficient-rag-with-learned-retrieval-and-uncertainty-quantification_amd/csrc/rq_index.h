@@ -1,5 +1,5 @@
 // rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
-// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_range.hip (range searches), rq_scan8.hip (the int8 image and its ladder) and
+// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_range.hip (range searches), rq_group.hip (grouped searches), rq_scan8.hip (the int8 image and its ladder) and
 // rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard, the pieces
 // of a call that the routes share.  The staging of the blocking host-buffer forms is rq_stage.h's.
 // Not part of the public boundary (that is include/rq.h).
@@ -117,6 +117,13 @@ struct StreamCtx {
     const uint2* rec_bins = nullptr;
     int64_t rec_stride = 0;
     int rec_B = 0, rec_slots = 0;
+    // grouped searches (rq_group.hip): the candidate rows of the stream's last rq_search_grouped_device call ([B][m1] scores and
+    // rows, grp_elems allocated of each) and its search's status ([grp_bcap])
+    float* grp_scores = nullptr;
+    int64_t* grp_rows = nullptr;
+    int* grp_status = nullptr;
+    size_t grp_elems = 0;
+    int grp_bcap = 0;
 };
 
 // A row filter (include/rq.h rq_filter): the set of local rows a filtered search may return.  It belongs to one index at one size
@@ -223,6 +230,12 @@ struct rq_index {
     int64_t range_calls = 0, range_repaired = 0;   // calls so far; queries the range fixup repaired
     unsigned long long* range_bins = nullptr;      // device: bins the last scan-route call re-scored, all queries ("range_bins_last")
     bool range_bins_valid = false;
+    // grouped searches (rq_group.hip): one int32 group id per stored row, RQ_GROUP_NONE (-1) = a group of its own
+    int32_t* d_groups = nullptr;       // [cap], allocated by the first rq_index_set_groups; null = every row is RQ_GROUP_NONE
+    std::vector<int32_t> h_groups;     // [n] host copy once d_groups exists (the exclusion loop of the fixup builds its filters from it)
+    int group_fetch = 8;               // option "group_fetch": the first rung fetches this multiple of k (rq_group_plan.h)
+    int group_fetch_cap = 0;           // option "group_fetch_cap": the largest m any rung asks for (test hook; 0 = RQ_MAX_K)
+    int64_t group_calls = 0, group_repaired = 0, group_rounds_last = 0;   // collapses launched; queries the fixup repaired; exclusion rounds of the last fixup
 };
 
 // Derived bound on |approximate scan score - exact score| for unit queries and cosine scaling:

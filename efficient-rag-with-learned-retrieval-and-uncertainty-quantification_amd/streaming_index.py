@@ -96,6 +96,25 @@ def _atomic_write(path: Path, data: bytes) -> None:
     os.replace(tmp, path)
 
 
+# ---- grouping (`distinct_by=`): the value a passage is grouped by, on both sides ------------------------------------------
+def _meta_group_value(meta: Optional[Dict[str, Any]], key: str):
+    """The value a passage is grouped by (`distinct_by=`): its metadata's `key`; None -- a group of its own -- when the key is
+    missing or holds "" / None.  Unhashable values are grouped by their repr."""
+    value = (meta or {}).get(key)
+    if value is None or value == "":
+        return None
+    try:
+        hash(value)
+    except TypeError:
+        return repr(value)
+    return value
+
+
+def _group_value(doc: "Document", key: str):
+    """... of a Document: the metadata DenseIndex.add_documents stores for it, {"title": title, **metadata}."""
+    return _meta_group_value({"title": doc.title or "", **(doc.metadata or {})}, key)
+
+
 # =============================================================================================
 # sparse side (reference :92-225).  CPU, host logic.
 # =============================================================================================
@@ -305,9 +324,34 @@ class BM25Index:
 
     SINGLE_NATIVE_AFTER: Optional[int] = 4   # one-query searches in a row over an unchanged corpus before they pay for the batch scorer's arrays (None: never)
 
-    def search(self, query: str, top_k: int = 10, *, allowed_ids=None) -> List[Tuple[str, float]]:
+    def _search_distinct(self, query: str, top_k: int, distinct_by: str, allowed_ids=None) -> List[Tuple[str, float]]:
+        """`search` with one passage per value of the documents' `distinct_by` field (extension, the sparse side of a grouped search):
+        collapsed on the host over `get_scores`, in the order of `_select_topk` -- score descending, exact ties by DESCENDING row --
+        keeping the first passage of every value.  A document without the field, or with "", is a group of its own."""
+        scores = self.get_scores(self._tokenize(query))
+        if allowed_ids is not None:
+            keep = np.zeros(len(scores), dtype=bool)
+            keep[[r for r in (self._row_of_id().get(d) for d in allowed_ids) if r is not None]] = True
+            scores = np.where(keep, scores, 0.0)
+        pos = np.flatnonzero(scores > 0)
+        out: List[Tuple[str, float]] = []
+        seen = set()
+        for i in pos[np.lexsort((-pos, -scores[pos]))].tolist():
+            if len(out) >= top_k:
+                break
+            value = _group_value(self.documents[self.doc_ids[i]], distinct_by)
+            if value is not None:
+                if value in seen:
+                    continue
+                seen.add(value)
+            out.append((self.doc_ids[i], float(scores[i])))
+        return out
+
+    def search(self, query: str, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[Tuple[str, float]]:
         if self.bm25 is None or not self.doc_ids:
             return []
+        if distinct_by is not None:
+            return self._search_distinct(query, top_k, distinct_by, allowed_ids)
         if allowed_ids is not None:
             # restricted to a set of ids (extension, the `where` of a Chroma query on the sparse side): the scores of every other
             # passage are masked to 0 before the reference's selection, which keeps positive scores only.  Unknown ids are ignored.
@@ -829,12 +873,51 @@ class DenseIndex:
             if own:
                 flt.close()
 
-    def search_vectors(self, vectors: np.ndarray, top_k: int = 10, *, allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
+    # ---- grouped searches (extension: `distinct_by=` -- one passage per value of a metadata field, e.g. "title": the best passage
+    # of each of the top_k articles of a chunked corpus; include/rq.h "grouped searches") --------------------------------------
+    def _push_groups(self, key: str) -> None:
+        """Group ids of the rows the index has not been told about yet: metadata value -> id, assigned lazily in row order; a row
+        whose metadata lacks `key`, or holds "", is a group of its own.  Another key than the last call's re-pushes every row."""
+        if self._index is None or not hasattr(self._index, "set_groups"):
+            raise _native.RqError("grouped searches need a single-device index")
+        st = self.__dict__.get("_group_state")
+        if st is None or st["key"] != key or st["pushed"] > len(self._ids):
+            st = self.__dict__["_group_state"] = {"key": key, "ids": {}, "pushed": 0}
+        first, n = st["pushed"], len(self._ids)
+        if first == n:
+            return
+        table = st["ids"]
+        groups = np.full(n - first, _native.GROUP_NONE, dtype=np.int32)
+        for j in range(first, n):
+            value = _meta_group_value(self._metas[j], key)
+            if value is not None:
+                groups[j - first] = table.setdefault(value, len(table))
+        self._index.set_groups(groups, first)
+        st["pushed"] = n
+
+    def _grouped_rows(self, vectors: np.ndarray, top_k: int, distinct_by: str, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores, rows) of the best passage of each of the top_k groups, best group first; entries beyond the distinct groups among
+        the passages in play are (0.0, -1).  The queries take the host path."""
+        self._push_groups(distinct_by)
+        k = min(int(top_k), len(self._ids), _native.MAX_K)
+        if allowed_ids is None:
+            return self._index.search_grouped(vectors, k, self.metric)[:2]
+        own = not isinstance(allowed_ids, _native.RowFilter)
+        flt = self.make_filter(allowed_ids) if own else allowed_ids
+        try:
+            return self._index.search_grouped(vectors, k, self.metric, row_filter=flt)[:2]
+        finally:
+            if own:
+                flt.close()
+
+    def search_vectors(self, vectors: np.ndarray, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[List[Tuple[str, float, str]]]:
         vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
         if self._index is None or len(self._ids) == 0 or top_k <= 0:
             return [[] for _ in range(vectors.shape[0])]
         if vectors.shape[1] != self.dim:
             raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
+        if distinct_by is not None:
+            return self._assemble(*self._grouped_rows(vectors, top_k, distinct_by, allowed_ids))
         if allowed_ids is not None:
             return self._assemble(*self._filtered_rows(vectors, top_k, allowed_ids))
         k = min(int(top_k), len(self._ids), _native.MAX_K)
@@ -1067,13 +1150,15 @@ class DenseIndex:
         rows = np.fromiter((self._row_of.get(d, -1) for d in ids), np.int64, len(ids))[None, :]
         return self.score_rows_batch([query], rows)[0].astype(np.float64).tolist()
 
-    def search_rows_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
+    def search_rows_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
         """`search_batch` without the (doc_id, score, text) tuples: (scores float32 [B][k], rows int64 [B][k], -1 padded; row r is
         `self._ids[r]`), k = min(top_k, len(self)).  What HybridRetriever's batched fusion consumes (extension).
         `allowed_ids` (ids or a `make_filter` result): only those passages are ranked; the queries then take the host path."""
         B = len(queries)
         if self._index is None or len(self._ids) == 0 or top_k <= 0 or B == 0:
             return np.zeros((B, 0), np.float32), np.zeros((B, 0), np.int64)
+        if distinct_by is not None:   # (one passage per value of that metadata field: `_grouped_rows`)
+            return self._grouped_rows(self._embed_matrix(list(queries)), top_k, distinct_by, allowed_ids)
         if allowed_ids is not None:
             return self._filtered_rows(self._embed_matrix(list(queries)), top_k, allowed_ids)
         if hasattr(self.embedder, "embed_device"):
@@ -1087,9 +1172,11 @@ class DenseIndex:
         k = min(int(top_k), len(self._ids), _native.MAX_K)
         return self._index.search(self._embed_matrix(list(queries)), k, self.metric)
 
-    def search_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
+    def search_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[List[Tuple[str, float, str]]]:
         if not queries:
             return []
+        if distinct_by is not None:   # (the device-embedder route is not extended: the queries take the host path)
+            return self.search_vectors(self._embed_matrix(list(queries)), top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)
         if allowed_ids is not None:   # (ids or a `make_filter` result: only those passages are ranked)
             return self.search_vectors(self._embed_matrix(list(queries)), top_k, allowed_ids=allowed_ids)
         # an embedder that can leave its output in HBM (embedders.NomicBertEmbedder.embed_device) feeds the search directly: no
@@ -1104,9 +1191,13 @@ class DenseIndex:
                 return self.search_device_vectors(d_q, top_k)
         return self.search_vectors(self._embed_matrix(list(queries)), top_k)
 
-    def search(self, query: str, top_k: int = 10, *, allowed_ids=None) -> List[Tuple[str, float, str]]:
+    def search(self, query: str, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[Tuple[str, float, str]]:
         """List of (doc_id, score, text), best first; score = cosine similarity (= 1 - Chroma distance).  `allowed_ids` (keyword-only
-        extension: ids, or a `make_filter` result for reuse) restricts the ranking to those passages, like a Chroma `where`."""
+        extension: ids, or a `make_filter` result for reuse) restricts the ranking to those passages, like a Chroma `where`.
+        `distinct_by` (keyword-only extension: a metadata key, e.g. "title") returns one passage per value of that field -- the best
+        passage of each of the top_k groups; a passage without the field is a group of its own.  It combines with `allowed_ids`."""
+        if distinct_by is not None:
+            return self.search_batch([query], top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)[0]
         if allowed_ids is not None:
             return self.search_batch([query], top_k, allowed_ids=allowed_ids)[0]
         return self.search_batch([query], top_k)[0]
@@ -1208,16 +1299,22 @@ class HybridRetriever:
 
     # `allowed_ids` (keyword-only extension on the per-query calls): only passages with these ids are ranked, on both sides -- the
     # `where` of a Chroma query.  The sparse side needs the ids themselves; the dense side also takes a DenseIndex.make_filter result.
-    def bm25_search(self, query: str, top_k: int = 20, *, allowed_ids=None) -> List[Tuple[str, float]]:
+    # `distinct_by` (keyword-only extension on the per-query calls, a metadata key such as "title"): one passage per value of that
+    # field on each side, and the fused list is collapsed once more by best hybrid score.  The `*_batch` fusions are not extended.
+    def bm25_search(self, query: str, top_k: int = 20, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[Tuple[str, float]]:
         if self.bm25_index is None:
             return []
+        if distinct_by is not None:
+            return self.bm25_index.search(query, top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)
         if allowed_ids is not None:
             return self.bm25_index.search(query, top_k, allowed_ids=allowed_ids)
         return self.bm25_index.search(query, top_k)
 
-    def dense_search(self, query: str, top_k: int = 20, *, allowed_ids=None) -> List[Tuple[str, float]]:
+    def dense_search(self, query: str, top_k: int = 20, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[Tuple[str, float]]:
         if self.dense_index is None:
             return []
+        if distinct_by is not None:
+            return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)]
         if allowed_ids is not None:
             return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids)]
         return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k)]
@@ -1268,8 +1365,22 @@ class HybridRetriever:
         order = sorted(range(len(ids)), key=lambda i: h[i] or 0, reverse=True)[:top_k]      # stable, like list.sort(reverse=True)
         return [ids[i] for i in order], [b[i] for i in order], [de[i] for i in order], [h[i] for i in order]
 
-    def _fuse(self, bm25_list: List[Tuple[str, float]], dense_list: List[Tuple[str, float]], top_k: int, extra=None) -> List[RetrievalResult]:
-        ids, b, de, h = self._fuse_columns(bm25_list, dense_list, top_k, extra)
+    def _fuse(self, bm25_list: List[Tuple[str, float]], dense_list: List[Tuple[str, float]], top_k: int, extra=None,
+              distinct_by: Optional[str] = None) -> List[RetrievalResult]:
+        if distinct_by is None:
+            ids, b, de, h = self._fuse_columns(bm25_list, dense_list, top_k, extra)
+        else:   # every candidate in hybrid order, then the first -- the best hybrid score -- of every value of the field
+            ids, b, de, h = self._fuse_columns(bm25_list, dense_list, len(bm25_list) + len(dense_list), extra)
+            keep, seen = [], set()
+            for i, doc_id in enumerate(ids):
+                value = _group_value(self.documents[doc_id], distinct_by)
+                if value is not None:
+                    if value in seen:
+                        continue
+                    seen.add(value)
+                keep.append(i)
+            keep = keep[:max(int(top_k), 0)]
+            ids, b, de, h = [ids[i] for i in keep], [b[i] for i in keep], [de[i] for i in keep], [h[i] for i in keep]
         out = []
         for doc_id, bs, ds, hs in zip(ids, b, de, h):
             doc = self.documents[doc_id]
@@ -1309,7 +1420,15 @@ class HybridRetriever:
                 bm25_extra = dict(zip(miss, bm.score_rows(query, [row_of[d] for d in miss]).tolist()))
         return bm25_list, dense_list, (bm25_extra, dense_extra)
 
-    def hybrid_search(self, query: str, top_k: int = 10, retrieval_pool_size: int = 50, *, allowed_ids=None, complete_scores: bool = False) -> List[RetrievalResult]:
+    def hybrid_search(self, query: str, top_k: int = 10, retrieval_pool_size: int = 50, *, allowed_ids=None, complete_scores: bool = False,
+                      distinct_by: Optional[str] = None) -> List[RetrievalResult]:
+        if distinct_by is not None:
+            if complete_scores:
+                raise ValueError("distinct_by does not combine with complete_scores")
+            if allowed_ids is not None and not isinstance(allowed_ids, _native.RowFilter):
+                allowed_ids = list(allowed_ids)      # (walked twice)
+            return self._fuse(self.bm25_search(query, retrieval_pool_size, allowed_ids=allowed_ids, distinct_by=distinct_by),
+                              self.dense_search(query, retrieval_pool_size, allowed_ids=allowed_ids, distinct_by=distinct_by), top_k, None, distinct_by)
         if complete_scores:
             bm25_list, dense_list, extra = self._pools_completed(query, retrieval_pool_size, allowed_ids)
             return self._fuse(bm25_list, dense_list, top_k, extra)

@@ -314,6 +314,68 @@ int rq_search_range_fixup_device(rq_index* idx, const rq_filter* f, const float*
 int rq_search_range(rq_index* idx, const rq_filter* f, const float* queries, int B, const float* thr, int cap, int metric,
                     float* out_scores, int64_t* out_rows, int64_t* out_count);
 
+/* ---- grouped searches: the best row of each of the k best groups (what a caller of the collection.query of reference
+ * rag_uq/streaming_index.py:355-359 does on the host for a chunked corpus -- over-fetch, keep the best passage per article, hope the
+ * over-fetch was enough; "field collapsing", "search_groups", "grouping search" elsewhere) ------------------------------------------
+ * groups: every stored row has a group id (int32).  RQ_GROUP_NONE (-1), the default, means the row is a group of its own; any value
+ *     >= 0 puts the row in the same group as every other row carrying that value.  Ids need not be dense.
+ *   ranking: the score definition and canonical order above: score descending, then row ascending; NaN counts as -inf; -0.0 is +0.0;
+ *     a zero-norm query scores every row 0.0.  With a filter f (may be NULL) only allowed rows take part: the rows in play.
+ *   winner: a group's winner is its best row in that order; groups rank by their winners.
+ *   result for k: the winners of the k best groups, best first, with their scores and group ids;
+ *     k_eff = min(k, distinct groups among the rows in play); entries beyond that are (0.0, -1, RQ_GROUP_NONE), with key 0 where keys
+ *     are asked for.
+ *   Hence: with no group set the result is rq_search's, bit for bit; with every row in one group k_eff = 1; a zero-norm query returns
+ *     the lowest row of each of the first k_eff groups in row order; a row's score has the same bits as rq_score_rows gives that pair.
+ * rq_index_set_groups: host array, LOCAL rows [row_begin, row_begin + n_rows), blocking; it waits for prior work on the device, as an
+ *   append does.  RQ_EINVAL for a range outside the stored rows or an id below RQ_GROUP_NONE.  rq_index_get_groups is the read-back
+ *   (of the device copy).  Storage: 4 B per row of HBM, allocated by the first rq_index_set_groups, which follows rq_index_reserve and
+ *   append growth, + a host copy of 4 B per row for the repair below; rows appended later are RQ_GROUP_NONE.  Groups are NOT written by
+ *   rq_save: the files stay as they are, and an index that rq_load creates has no group set.
+ * rq_group_collapse_device: asynchronous, pure selection over a caller's candidates [B][m] in device memory, any order, with
+ *   1 <= k <= m <= RQ_MAX_K.  absent candidate: as for rq_mmr_select_device -- c_i = -1 or any row outside [row_offset, row_offset +
+ *   rq_index_size), or a NaN score; it is never a winner and its group is never read.  The candidate rows must be distinct.
+ *   d_cand_groups [B][m] may be NULL: the group is looked up by row in the index (4 bytes per candidate; no stored row is read).  Given
+ *   explicitly (any negative id = RQ_GROUP_NONE) it serves fused hybrid pools and lists merged from several shards: merging per-shard
+ *   grouped top-k lists and collapsing again is exact.  d_status[q] = 0 when the present candidates hold at least k
+ *   distinct groups, else 1.  It runs in stream order after whatever produced the candidates and defers nothing.
+ * rq_search_grouped_device: asynchronous, device pointers.  It behaves like a "pipeline" = 0 call: it first completes what `stream`
+ *   defers (a fused tail, a scanned-ahead pair, a hint), as rq_search_filtered_device does.  One rung: the exact search for m1 rows
+ *   (the filtered search when f is given), then the collapse; the candidates stay in the stream's workspace (B x m1 x 12 bytes).
+ *   d_status[q]: 0 = the result is proven, 1 = not -- call rq_search_grouped_fixup_device with the SAME arguments.  Proven: the search
+ *   certified the query, and its list either holds at least k groups or already holds every row in play.
+ * rq_search_grouped_fixup_device: synchronises `stream`, repairs the flagged queries in place and returns how many it repaired.
+ *   Rung 2: m = min(rows in play, RQ_MAX_K), repaired by the usual ladder, then collapsed.  Rung 3, for queries still short of k
+ *   groups, the exclusion loop: the d winners found are the exact top d groups, because the list was the exact top m rows; the rows in
+ *   play that belong to none of them become a temporary rq_filter (built on the host from the group copy); that query is searched
+ *   filtered for up to RQ_MAX_K rows, collapsed, and the new winners are appended; until k winners are found or no row is left.  Every
+ *   round adds at least one group; no other scan kernel is involved.
+ * rq_search_grouped: blocking, host buffers ([B][dim] queries; out_scores, out_rows, out_groups [B][k], all required), staged on the
+ *   index's own stream like rq_search_mmr, repair included: B x (dim x 4 + k x 16 + 4) bytes of HBM for the call.
+ * RQ_EINVAL unless 1 <= k <= RQ_MAX_K, 1 <= B <= 65535, a known metric and non-null pointers (d_keys, d_cand_groups and f aside); the
+ *   filter checks are those of rq_search_filtered (another index's filter, a stale filter: RQ_EINVAL); RQ_EUNSUPPORTED on a multi-device
+ *   index, for every call of this section; RQ_ENODEVICE as everywhere.  One rq_index from one thread at a time, and no
+ *   rq_index_set_groups while a grouped call is in flight.
+ * Not extended: one row per group only -- group_size > 1 needs per-group member counts and a row list per group; rq_search_train_device,
+ *   hints, "pipeline" 1 and 2, "scan_ahead", multi-device indexes.
+ * rq_timing counts a grouped call as a search (searches, queries; its repairs as the ladder counts them).
+ * Options: "group_fetch" (1 .. RQ_MAX_K, default 8: the first rung asks for m1 = this multiple of k, clamped to [k, min(rows in play,
+ *   RQ_MAX_K)]; the default is the measured choice of DESIGN.md 4.16); "group_fetch_cap" (test hook, like "range_cand_cap": the largest m
+ *   any rung may ask for, never below a call's k; 0 = RQ_MAX_K; it lets small shapes reach rung 3); read-only "group_calls" (collapses
+ *   launched, every entry point and rung), "group_repaired" (queries the grouped fixup repaired), "group_rounds_last" (exclusion rounds
+ *   of the last fixup that repaired anything, summed over its queries). */
+#define RQ_GROUP_NONE (-1)
+int rq_index_set_groups(rq_index* idx, int64_t row_begin, int64_t n_rows, const int32_t* groups);
+int rq_index_get_groups(const rq_index* idx, int64_t row_begin, int64_t n_rows, int32_t* out);
+int rq_group_collapse_device(rq_index* idx, const int64_t* d_cand_rows, const float* d_cand_scores, const int32_t* d_cand_groups, int B, int m, int k,
+                             float* d_scores, int64_t* d_rows, int32_t* d_groups, uint64_t* d_keys, int* d_status, void* stream);
+int rq_search_grouped_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int metric, float* d_scores, int64_t* d_rows,
+                             int32_t* d_groups, uint64_t* d_keys, int* d_status, void* stream);
+int rq_search_grouped_fixup_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int metric, float* d_scores, int64_t* d_rows,
+                                   int32_t* d_groups, uint64_t* d_keys, int* d_status, void* stream);
+int rq_search_grouped(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int metric, float* out_scores, int64_t* out_rows,
+                      int32_t* out_groups);
+
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
  * "wg_per_cu", "nt" (non-temporal corpus loads: 0, 1, -1 = auto), "slack_bins" (extra bins beyond k, -1 = auto),
