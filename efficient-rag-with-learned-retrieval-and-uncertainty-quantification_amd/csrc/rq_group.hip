@@ -10,7 +10,7 @@
 // for both row layouts.  What a call fetches is decided by rq_group_plan.h.  Replaces the over-fetch / collapse-on-the-host loop
 // around the collection.query of reference rag_uq/streaming_index.py:355-359.
 #include "rq_group_plan.h"
-#include "rq_stage.h"
+#include "rq_repair.h"
 
 // ---- kernel -------------------------------------------------------------------------------------
 struct RqGroupArgs {
@@ -295,7 +295,7 @@ static int group_exclusion_loop(rq_index* idx, const rq_filter* f, const float* 
         {
             Stage st(s);
             rc = st.alloc(bytes, 7, "the exclusion round of a grouped search");
-            st.in_flight = rc == RQ_OK;   // (kernels write these buffers from here on: whichever step fails, the stream is waited for before they are freed)
+            st.launched();   // (kernels write these buffers from here on: whichever step fails, the stream is waited for before they are freed)
             float* cs = st.at<float>(0); int64_t* cr = st.at<int64_t>(1); int* cst = st.at<int>(2);
             const GroupOut o{st.at<float>(3), st.at<int64_t>(4), st.at<int32_t>(5), nullptr, st.at<int>(6)};
             if (rc == RQ_OK) rc = search_filtered_device(idx, rest, d_q1, 1, m, metric, {cs, cr, nullptr, cst}, s);
@@ -323,11 +323,9 @@ static int group_exclusion_loop(rq_index* idx, const rq_filter* f, const float* 
 // collapsed; rung 3 = the exclusion loop for the queries still short of k groups.  Returns how many queries it repaired.
 static int grouped_fixup(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const GroupOut& out, hipStream_t s) {
     if (int r = flush_tails(idx, s)) return r;
-    std::vector<int> st((size_t)B);
-    HIPCHK(hipMemcpyAsync(st.data(), out.status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<int> bad;
-    for (int q = 0; q < B; ++q) if (st[q] != 0) bad.push_back(q);
+    Stage fx(s);
+    RepairList bad;
+    if (int r = repair_flagged(fx, out.status, B, bad)) return r;
     if (bad.empty()) return 0;
     const int nb = (int)bad.size();
     idx->group_repaired += nb;
@@ -335,16 +333,12 @@ static int grouped_fixup(rq_index* idx, const rq_filter* f, const float* d_q, in
     const int64_t play = rows_in_play(idx, f);
     const int m2 = group_max_fetch(k, idx->group_fetch_cap, play);
     const GroupStaging sz = group_staging(idx->dim, nb, m2, k);
-    const size_t bytes_in[4] = {sz.q, sz.cand_scores, sz.cand_rows, sz.cand_status};
-    const size_t bytes_out[5] = {sz.out_scores, sz.out_rows, sz.out_groups, sz.out_keys, sz.status};
-    Stage in(s), fx(s);
-    if (int r = in.alloc(bytes_in, 4, "the repair of a grouped search")) return r;
-    if (int r = fx.alloc(bytes_out, 5, "the repair of a grouped search")) return r;
-    in.in_flight = fx.in_flight = true;   // (kernels write these buffers from here on: a failed step waits for the stream before they are freed)
-    float* fq = in.at<float>(0); float* cs = in.at<float>(1); int64_t* cr = in.at<int64_t>(2); int* cst = in.at<int>(3);
-    const GroupOut fo{fx.at<float>(0), fx.at<int64_t>(1), fx.at<int32_t>(2), fx.at<uint64_t>(3), fx.at<int>(4)};
-    for (int i = 0; i < nb; ++i)
-        if (int r = in.copy(fq + (size_t)i * idx->dim, d_q + (size_t)bad[i] * idx->dim, (size_t)idx->dim * sizeof(float), hipMemcpyDeviceToDevice, "D2D copy failed")) return r;
+    const size_t bytes[9] = {sz.q, sz.cand_scores, sz.cand_rows, sz.cand_status, sz.out_scores, sz.out_rows, sz.out_groups, sz.out_keys, sz.status};
+    if (int r = fx.alloc(bytes, 9, "the repair of a grouped search")) return r;
+    fx.launched();   // (kernels write these buffers from here on: a failed step waits for the stream before they are freed)
+    float* fq = fx.at<float>(0); float* cs = fx.at<float>(1); int64_t* cr = fx.at<int64_t>(2); int* cst = fx.at<int>(3);
+    const GroupOut fo{fx.at<float>(4), fx.at<int64_t>(5), fx.at<int32_t>(6), fx.at<uint64_t>(7), fx.at<int>(8)};
+    if (int r = repair_pack(fx, bad, {repair_col(d_q, fq, (size_t)idx->dim)})) return r;
     // rung 2
     if (int r = group_fetch_rows(idx, f, fq, nb, m2, metric, {cs, cr, nullptr, cst}, s)) return r;
     if (int r = fixup_ladder(idx, f, fq, nb, m2, metric, cs, cr, nullptr, cst, s); r < 0) return r;
@@ -360,6 +354,7 @@ static int grouped_fixup(rq_index* idx, const rq_filter* f, const float* d_q, in
     fx.down(h_status.data(), fo.status, sz.status);
     if (int r = fx.finish()) return r;
     // rung 3, query by query; the extended answers go back into the repair's buffers
+    fx.launched();   // (its searches read the packed queries)
     for (int i = 0; i < nb; ++i) {
         if (h_status[(size_t)i] == 0) continue;
         GroupAnswer ans;
@@ -379,15 +374,9 @@ static int grouped_fixup(rq_index* idx, const rq_filter* f, const float* d_q, in
         HIPCHK(hipMemcpy(fo.groups + (size_t)i * kk, ans.groups.data(), kk * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(fo.keys + (size_t)i * kk, keys.data(), kk * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
-    for (int i = 0; i < nb; ++i) {
-        const size_t q = (size_t)bad[i];
-        fx.copy(out.scores + q * kk, fo.scores + (size_t)i * kk, kk * sizeof(float), hipMemcpyDeviceToDevice, "D2D copy failed");
-        fx.copy(out.rows + q * kk, fo.rows + (size_t)i * kk, kk * sizeof(int64_t), hipMemcpyDeviceToDevice, "D2D copy failed");
-        fx.copy(out.groups + q * kk, fo.groups + (size_t)i * kk, kk * sizeof(int32_t), hipMemcpyDeviceToDevice, "D2D copy failed");
-        if (out.keys) fx.copy(out.keys + q * kk, fo.keys + (size_t)i * kk, kk * sizeof(uint64_t), hipMemcpyDeviceToDevice, "D2D copy failed");
-    }
-    if (fx.rc != RQ_OK) return fx.rc;
-    for (int i = 0; i < nb; ++i) HIPCHK(hipMemsetAsync(out.status + bad[i], 0, sizeof(int), s));
+    if (int r = repair_unpack(fx, bad, {repair_col(out.scores, fo.scores, kk), repair_col(out.rows, fo.rows, kk), repair_col(out.groups, fo.groups, kk),
+                                        repair_col(out.keys, fo.keys, kk)})) return r;
+    if (int r = repair_unpack(fx, bad, {}, out.status)) return r;   // (the status words after every copy)
     if (int r = fx.finish()) return r;
     return nb;
 }

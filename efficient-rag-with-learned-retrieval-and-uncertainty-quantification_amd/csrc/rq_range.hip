@@ -14,7 +14,7 @@
 #include "rq_range_plan.h"
 #include "rq_final_body.h"   // RQ_TINY_QUERY_NORM
 #include "rq_rowdot.h"
-#include "rq_stage.h"
+#include "rq_repair.h"
 
 // ---- kernels ------------------------------------------------------------------------------------
 struct RqRangeTailArgs {
@@ -311,11 +311,9 @@ static int search_range_device(rq_index* idx, const rq_filter* f, const float* d
 // route and patches the outputs in place.  Returns how many.
 static int range_fixup(rq_index* idx, const rq_filter* f, const float* d_q, int B, const float* d_thr, int cap, int metric, const RangeOut& out, hipStream_t s) {
     if (int r = flush_tails(idx, s)) return r;
-    std::vector<int> st((size_t)B);
-    HIPCHK(hipMemcpyAsync(st.data(), out.status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<int> bad;
-    for (int q = 0; q < B; ++q) if (st[q] != 0) bad.push_back(q);
+    Stage fx(s);
+    RepairList bad;
+    if (int r = repair_flagged(fx, out.status, B, bad)) return r;
     if (bad.empty()) return 0;
     const int nb = (int)bad.size();
     idx->range_repaired += nb;
@@ -323,23 +321,14 @@ static int range_fixup(rq_index* idx, const rq_filter* f, const float* d_q, int 
     idx->t.exact_scans += nb;
     const RangeStaging sz = range_staging(idx->dim, nb, cap);
     const size_t bytes[7] = {sz.q, sz.thr, sz.scores, sz.rows, sz.rows, sz.count, sz.status};
-    Stage fx(s);
     if (int r = fx.alloc(bytes, 7, "the repair of a range search")) return r;
     float* fq = fx.at<float>(0); float* fthr = fx.at<float>(1);
     const RangeOut fo{fx.at<float>(2), fx.at<int64_t>(3), out.keys ? fx.at<uint64_t>(4) : nullptr, fx.at<int64_t>(5), fx.at<int>(6)};
-    for (int i = 0; i < nb; ++i) {
-        fx.copy(fq + (size_t)i * idx->dim, d_q + (size_t)bad[i] * idx->dim, (size_t)idx->dim * sizeof(float), hipMemcpyDeviceToDevice, "D2D copy failed");
-        if (int r = fx.copy(fthr + i, d_thr + bad[i], sizeof(float), hipMemcpyDeviceToDevice, "D2D copy failed")) return r;
-    }
+    if (int r = repair_pack(fx, bad, {repair_col(d_q, fq, (size_t)idx->dim), repair_col(d_thr, fthr, 1)})) return r;
     if (int r = search_range_device(idx, f, fq, nb, fthr, cap, metric, fo, s, RROUTE_EXACT, false)) return r;
-    for (int i = 0; i < nb; ++i) {
-        const size_t q = (size_t)bad[i], c = (size_t)cap;
-        fx.copy(out.scores + q * c, fo.scores + (size_t)i * c, c * sizeof(float), hipMemcpyDeviceToDevice, "D2D copy failed");
-        fx.copy(out.rows + q * c, fo.rows + (size_t)i * c, c * sizeof(int64_t), hipMemcpyDeviceToDevice, "D2D copy failed");
-        if (out.keys) fx.copy(out.keys + q * c, fo.keys + (size_t)i * c, c * sizeof(uint64_t), hipMemcpyDeviceToDevice, "D2D copy failed");
-        fx.copy(out.count + q, fo.count + i, sizeof(int64_t), hipMemcpyDeviceToDevice, "D2D copy failed");
-        if (int r = fx.copy(out.status + q, fo.status + i, sizeof(int), hipMemcpyDeviceToDevice, "D2D copy failed")) return r;
-    }
+    const size_t c = (size_t)cap;   // (the re-run's status comes back as a column)
+    if (int r = repair_unpack(fx, bad, {repair_col(out.scores, fo.scores, c), repair_col(out.rows, fo.rows, c), repair_col(out.keys, fo.keys, c),
+                                        repair_col(out.count, fo.count, 1), repair_col(out.status, fo.status, 1)})) return r;
     if (int r = fx.finish()) return r;
     return nb;
 }

@@ -2,6 +2,7 @@
 // (run_pipeline: plan -> prepare -> scan passes -> tail), deferred tails and scanned-ahead pairs, the repair ladder, the
 // blocking host-buffer search.  What a call will do is decided by rq_plan.h; the kernels are rq_kernels.h's launchers.
 #include "rq_plan.h"
+#include "rq_repair.h"
 
 static const size_t RQ_MAX_STREAM_CTX = 8;
 
@@ -682,20 +683,17 @@ extern "C" int rq_search_fixup_device(rq_index* idx, const float* d_queries, int
 int fixup_ladder(rq_index* idx, const rq_filter* filt, const float* d_queries, int B, int k, int metric, float* d_scores,
                  int64_t* d_rows, uint64_t* d_keys, int* d_status, hipStream_t s) {
     if (int r = flush_tails(idx, s)) return r;
-    std::vector<int> st((size_t)B);
-    HIPCHK(hipMemcpyAsync(st.data(), d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<int> bad;
-    for (int q = 0; q < B; ++q) if (st[q] != 0) bad.push_back(q);
+    Stage fx(s);   // (owns no buffer: the workspace's grow-only fix_* are the packed ones)
+    RepairList bad;
+    if (int r = repair_flagged(fx, d_status, B, bad)) return r;
     if (!filt) scan8_account(idx, k, B, (int)bad.size());   // (filtered calls never touch the int8 image or its ladder)
     if (bad.empty()) return 0;
     const int repaired = (int)bad.size();
     idx->repaired_total += repaired;
     if (filt) idx->filter_repaired += repaired;
     Workspace& w = idx->ctx[s].w[0];
-    const int fb = (int)bad.size();
-    if (fb > w.fix_bcap || k > w.fix_k) {
-        const int nb_ = std::max(fb, w.fix_bcap), nk = std::max(k, w.fix_k);
+    if (repaired > w.fix_bcap || k > w.fix_k) {
+        const int nb_ = std::max(repaired, w.fix_bcap), nk = std::max(k, w.fix_k);
         if (int r = ensure(w.fix_q, (size_t)nb_ * RQ_MAX_DIM)) return r;
         if (int r = ensure(w.fix_scores, (size_t)nb_ * nk)) return r;
         if (int r = ensure(w.fix_rows, (size_t)nb_ * nk)) return r;
@@ -711,9 +709,7 @@ int fixup_ladder(rq_index* idx, const rq_filter* filt, const float* d_queries, i
     const SearchOut fix_out{w.fix_scores, w.fix_rows, w.fix_keys, w.fix_status};
     for (int level = from8 ? -1 : 0; level < 2 && !bad.empty(); ++level) {
         const int nbq = (int)bad.size();
-        for (int i = 0; i < nbq; ++i)
-            HIPCHK(hipMemcpyAsync(w.fix_q + (size_t)i * idx->dim, d_queries + (size_t)bad[i] * idx->dim, (size_t)idx->dim * sizeof(float),
-                                  hipMemcpyDeviceToDevice, s));
+        if (int r = repair_pack(fx, bad, {repair_col(d_queries, w.fix_q, (size_t)idx->dim)})) return r;
         if (level < 0) {
             if (int r = run_pipeline(idx, w.fix_q, nbq, k, metric, nb_default(idx, k), fix_out, s, 0, filt)) return r;
         } else if (level == 0) {
@@ -729,22 +725,16 @@ int fixup_ladder(rq_index* idx, const rq_filter* filt, const float* d_queries, i
                 if (int r = run_pipeline(idx, w.fix_q + (size_t)off * idx->dim, g, k, metric, -1, fix_out.from(off, k), s, allow8, filt)) return r;
             }
         }
-        std::vector<int> st2((size_t)nbq);
-        HIPCHK(hipMemcpyAsync(st2.data(), w.fix_status, (size_t)nbq * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        std::vector<int> still;
-        for (int i = 0; i < nbq; ++i) {
-            if (st2[i] == 0) {
-                const int q = bad[i];
-                HIPCHK(hipMemcpyAsync(d_scores + (size_t)q * k, w.fix_scores + (size_t)i * k, (size_t)k * sizeof(float), hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(d_rows + (size_t)q * k, w.fix_rows + (size_t)i * k, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-                if (d_keys) HIPCHK(hipMemcpyAsync(d_keys + (size_t)q * k, w.fix_keys + (size_t)i * k, (size_t)k * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemsetAsync(d_status + q, 0, sizeof(int), s));
-            } else {
-                still.push_back(bad[i]);
-            }
+        // the slots that certified at this rung go back, the others climb on in slots 0, 1, ...
+        std::vector<int> st2;
+        if (int r = repair_status(fx, w.fix_status, nbq, st2)) return r;
+        RepairList done, still;
+        for (const RepairPair& p : bad) {
+            if (st2[(size_t)p.slot] == 0) done.push_back(p);
+            else still.push_back({(int)still.size(), p.q});
         }
-        HIPCHK(hipStreamSynchronize(s));
+        repair_unpack(fx, done, {repair_col(d_scores, w.fix_scores, k), repair_col(d_rows, w.fix_rows, k), repair_col(d_keys, w.fix_keys, k)}, d_status);
+        if (int r = fx.finish()) return r;
         bad.swap(still);
     }
     if (!bad.empty()) return set_err(RQ_EHIP, "internal: %zu queries uncertified after the exact scan", bad.size());

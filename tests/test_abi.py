@@ -136,8 +136,8 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     k-way merge incl. its threads, the poisoned / failed-search paths -- behind STUBBED shards (tests/native/multi_check.cpp),
     (c) librq_bm25's scorer (csrc/rq_bm25.cpp compiled into tests/native/bm25_check.cpp), (d) the call plan of csrc/rq_plan.h --
     route, pass cutting, scan grids, non-temporal rule -- on a host-built rq_index (tests/native/plan_check.cpp), (e) the staging of the
-    blocking host-buffer calls, csrc/rq_stage.h, behind stand-ins for the HIP calls it makes: every allocation and every copy fails in turn
-    (tests/native/stage_check.cpp), (f) the certificate's last step, csrc/rq_device.h rq_certified (tests/native/cert_check.cpp).  Any report
+    blocking host-buffer calls, csrc/rq_stage.h, and the packing and unpacking of the three repairs, csrc/rq_repair.h, behind stand-ins for
+    the HIP calls they make: every allocation, copy, memset and wait fails in turn (tests/native/stage_check.cpp), (f) the certificate's last step, csrc/rq_device.h rq_certified (tests/native/cert_check.cpp).  Any report
     aborts the program."""
     import shutil
     import subprocess

@@ -368,6 +368,56 @@ def test_repair_takes_as_many_exclusion_rounds_as_the_groups_need():
     sh.close()
 
 
+@pytest.fixture(scope="module")
+def small():
+    sh = Shape(n=2000, seed=57)                                           # 32 bins, the last one ragged
+    yield sh
+    sh.close()
+
+
+@pytest.fixture(scope="module")
+def small_narrow():
+    sh = Shape(n=2000, dim=384, seed=58)
+    yield sh
+    sh.close()
+
+
+@pytest.mark.parametrize("B,flagged", [(5, [0, 3, 4]), (70, [0, 63, 64, 69])])
+@pytest.mark.parametrize("shape,metric", [("small", COS), ("small", IP), ("small_narrow", COS)])
+def test_the_fixup_repairs_exactly_the_queries_flagged_by_hand(request, shape, metric, B, flagged):
+    """rq_search_grouped_device without a fixup, then on the device: status 1 for a chosen subset and garbage over those queries'
+    outputs, then the fixup form.  Groups of four consecutive rows, k = 3: rung 2 alone answers (no exclusion round).  It returns the
+    size of the subset, the flagged queries equal the oracle, every other query keeps the first call's bits, every status is 0 and
+    "group_repaired" rose by the size of the subset."""
+    import torch
+    sh = request.getfixturevalue(shape)
+    k = 3
+    groups = np.arange(sh.n, dtype=np.int64) // 4
+    sh.idx.set_groups(groups)
+    want = sh.want(groups, k, metric, B=B)
+    what = f"by hand: {shape}, metric {metric}, B {B}"
+    bufs = grouped_dev(sh.idx, sh.q[:B], k, metric)
+    first = host(bufs)
+    assert not first[3].any(), f"{what}: the first call flagged {np.nonzero(first[3])[0].tolist()} itself"
+    sel = torch.tensor(flagged, device="cuda")
+    bufs["st"][sel] = 1
+    bufs["s"][sel] = float("nan")
+    bufs["r"][sel] = -7
+    bufs["g"][sel] = -7
+    bufs["k"][sel] = -1                                                   # all ones
+    before = int(sh.idx.get_option("group_repaired"))
+    n = sh.idx.search_grouped_fixup_device(bufs["q"], B, k, metric, bufs["s"], bufs["r"], bufs["g"], bufs["k"], bufs["st"])
+    after = host(bufs)
+    assert n == len(flagged), f"{what}: the fixup returned {n}"
+    assert not after[3].any(), f"{what}: status after the fixup {after[3].tolist()}"
+    agrees([a[flagged] for a in after[:3]], [w[flagged] for w in want], sh.scores(metric), f"{what}, flagged queries")
+    assert np.array_equal(after[4][flagged], host_keys(after[0][flagged], after[1][flagged])), f"{what}: keys of the flagged queries"
+    other = np.setdiff1d(np.arange(B), flagged)
+    for a, b in zip(first, after):
+        assert np.array_equal(a[other].view(np.uint8), b[other].view(np.uint8)), f"{what}: an unflagged query changed"
+    assert int(sh.idx.get_option("group_repaired")) == before + len(flagged) and int(sh.idx.get_option("group_rounds_last")) == 0, what
+
+
 # ---- 6. storage --------------------------------------------------------------------------------------------------------------------
 def test_rows_appended_after_set_groups_are_their_own_groups_and_sub_ranges_read_back():
     x16 = orc.synthetic_corpus(9101, 768, seed=41)

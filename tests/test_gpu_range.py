@@ -303,6 +303,70 @@ def test_overflow_is_reported_counted_exactly_and_repaired(wide):
     check(dev, want, "default capacity")
 
 
+@pytest.fixture(scope="module")
+def small():
+    sh = Shape(n=2000, seed=57)                                                   # 32 bins, the last one ragged
+    yield sh
+    sh.close()
+
+
+@pytest.fixture(scope="module")
+def small_narrow():
+    sh = Shape(n=2000, dim=384, seed=58)
+    yield sh
+    sh.close()
+
+
+@pytest.mark.parametrize("B,flagged", [(5, [0, 3, 4]), (70, [0, 63, 64, 69])])
+@pytest.mark.parametrize("shape,metric", [("small", COS), ("small", IP), ("small_narrow", COS)])
+def test_the_fixup_repairs_exactly_the_queries_flagged_by_hand(request, shape, metric, B, flagged):
+    """rq_search_range_device without a fixup, then on the device: status 1 for a chosen subset and garbage over those queries' outputs
+    (count included), then rq_search_range_fixup_device.  It returns the size of the subset, the flagged queries equal the oracle -- their
+    counts exactly, keys made of score and row --, every other query keeps the first call's bits, every status is 0 and "range_repaired"
+    rose by the size of the subset.  With and without d_keys."""
+    import torch
+    from rag_uq_amd import distributed as dist
+    sh = request.getfixturevalue(shape)
+    idx, cap = sh.idx, 16
+    thr = sh.mixed(B, metric)
+    want = sh.want(B, thr, cap, metric)
+    d_q = torch.from_numpy(np.ascontiguousarray(sh.q[:B], np.float32)).cuda()
+    d_t = torch.from_numpy(thr).cuda()
+    for with_keys in (True, False):
+        what = f"by hand: {shape}, metric {metric}, B {B}, keys {with_keys}"
+        sc = torch.full((B, cap), 7.0, dtype=torch.float32, device="cuda")
+        rw = torch.full((B, cap), 7, dtype=torch.int64, device="cuda")
+        ky = torch.full((B, cap), 7, dtype=torch.int64, device="cuda") if with_keys else None
+        cn = torch.full((B,), 7, dtype=torch.int64, device="cuda")
+        st = torch.full((B,), 7, dtype=torch.int32, device="cuda")
+        bufs = (sc, rw, cn, st) + ((ky,) if with_keys else ())
+        idx.search_range_device(d_q, B, d_t, cap, metric, sc, rw, ky, cn, st, 0)
+        torch.cuda.synchronize()
+        first = [t.cpu().numpy().copy() for t in bufs]
+        assert not first[3].any(), f"{what}: the first call flagged {np.nonzero(first[3])[0].tolist()} itself"
+        sel = torch.tensor(flagged, device="cuda")
+        st[sel] = 1
+        sc[sel] = float("nan")
+        rw[sel] = -7
+        cn[sel] = -1
+        if with_keys:
+            ky[sel] = -1                                                          # all ones
+        before = int(idx.get_option("range_repaired"))
+        n = idx.search_range_fixup_device(d_q, B, d_t, cap, metric, sc, rw, ky, cn, st, 0)
+        torch.cuda.synchronize()
+        after = [t.cpu().numpy() for t in bufs]
+        assert n == len(flagged), f"{what}: the fixup returned {n}"
+        assert not after[3].any(), f"{what}: status after the fixup {after[3].tolist()}"
+        check([a[flagged] for a in after[:3]], [w[flagged] for w in want], f"{what}, flagged queries")
+        if with_keys:
+            assert np.array_equal(after[4].view(np.uint64)[flagged], dist.pack_keys(after[0][flagged].reshape(-1), after[1][flagged].reshape(-1)).reshape(-1, cap)), \
+                f"{what}: keys of the flagged queries"
+        other = np.setdiff1d(np.arange(B), flagged)
+        for a, b in zip(first, after):
+            assert np.array_equal(a[other].view(np.uint8), b[other].view(np.uint8)), f"{what}: an unflagged query changed"
+        assert int(idx.get_option("range_repaired")) == before + len(flagged), what
+
+
 # ---- 5. filters ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", ["wide", "narrow", "shifted"])
 def test_filtered_calls_equal_the_oracle(request, shape):

@@ -445,3 +445,65 @@ def test_exact_scan_at_tile_and_query_group_edges(dim, row_pad):
                     assert np.array_equal(rows[0], rows[1]), f"exact scan: dim {dim}, n {n}, B {B}: the two kernels disagree on the rows"
         finally:
             sh.close()
+
+
+# ====================================================================================================================================
+# (d) the repair of queries flagged by hand: which packed slot overwrites which query's answer
+# ====================================================================================================================================
+HAND_N, HAND_K = 2000, 10                          # 32 bins, the last one ragged
+HAND_FLAGGED = [(5, [0, 3, 4]), (70, [0, 63, 64, 69])]
+
+
+@pytest.mark.parametrize("dim,row_pad,metric", [(768, None, COS), (768, None, IP), (384, 384, COS)], ids=["wide-cosine", "wide-ip", "narrow-cosine"])
+def test_the_fixup_repairs_exactly_the_queries_flagged_by_hand(dim, row_pad, metric):
+    """rq_search_device / rq_search_filtered_device without a fixup, then on the device: status 1 for a chosen subset and garbage over
+    those queries' outputs, then the fixup form.  It returns the size of the subset, the flagged queries equal the oracle (rows, scores
+    within SCORE_TOL, keys made of both), every other query keeps the first call's bits, every status is 0 and the counters rose by
+    the size of the subset.  With and without d_keys, with and without a filter that allows about half the rows."""
+    import torch
+    x = orc.synthetic_corpus(HAND_N, dim, seed=71 + dim)
+    qall = orc.synthetic_queries(70, dim, seed=72 + dim)
+    idx = nat.NativeIndex(dim, 0)
+    if row_pad:
+        idx.set_option("row_pad", row_pad)
+    idx.add_f16(x)
+    allowed = np.random.default_rng(73).random(HAND_N) < 0.5
+    flt = idx.make_filter(allowed)
+    try:
+        assert idx.row_pad == (row_pad or 768)
+        gold = {None: orc.topk_from_scores(nfo.scores(qall, x, metric), HAND_K), flt: nfo.topk(qall, x, HAND_K, metric, mask=allowed)}
+        for (B, flagged), with_keys, f in [(bf, wk, f) for bf in HAND_FLAGGED for wk in (True, False) for f in (None, flt)]:
+            what = f"by hand: dim {dim}, metric {metric}, B {B}, keys {with_keys}, filtered {f is not None}"
+            q = torch.from_numpy(np.ascontiguousarray(qall[:B])).cuda()
+            sc = torch.full((B, HAND_K), -5.5, device="cuda")
+            rw = torch.full((B, HAND_K), -9, device="cuda", dtype=torch.int64)
+            ky = torch.full((B, HAND_K), 7, device="cuda", dtype=torch.int64) if with_keys else None
+            st = torch.full((B,), -7, device="cuda", dtype=torch.int32)
+            idx.search_device(q, B, HAND_K, metric, sc, rw, ky, st, 0, row_filter=f)
+            torch.cuda.synchronize()
+            first = [t.cpu().numpy().copy() for t in (sc, rw, st) + ((ky,) if with_keys else ())]
+            assert not first[2].any(), f"{what}: the first call flagged {np.nonzero(first[2])[0].tolist()} itself"
+            sel = torch.tensor(flagged, device="cuda")
+            st[sel] = 1
+            sc[sel] = float("nan")
+            rw[sel] = -7
+            if with_keys:
+                ky[sel] = -1                        # all ones
+            before = {o: int(idx.get_option(o)) for o in ("repaired_queries", "filter_repaired")}
+            n = idx.search_fixup_device(q, B, HAND_K, metric, sc, rw, ky, st, 0, row_filter=f)
+            torch.cuda.synchronize()
+            after = [t.cpu().numpy() for t in (sc, rw, st) + ((ky,) if with_keys else ())]
+            assert n == len(flagged), f"{what}: the fixup returned {n}"
+            assert not after[2].any(), f"{what}: status after the fixup {after[2].tolist()}"
+            _same(after[0][flagged], after[1][flagged], gold[f][0][flagged], gold[f][1][flagged], f"{what}, flagged queries")
+            if with_keys:
+                assert np.array_equal(after[3].view(np.uint64)[flagged], dist.pack_keys(after[0][flagged].reshape(-1), after[1][flagged].reshape(-1)).reshape(-1, HAND_K)), \
+                    f"{what}: keys of the flagged queries"
+            other = np.setdiff1d(np.arange(B), flagged)
+            for a, b in zip(first, after):
+                assert np.array_equal(a[other].view(np.uint8), b[other].view(np.uint8)), f"{what}: an unflagged query changed"
+            assert int(idx.get_option("repaired_queries")) == before["repaired_queries"] + len(flagged), what
+            assert int(idx.get_option("filter_repaired")) == before["filter_repaired"] + (len(flagged) if f is not None else 0), what
+    finally:
+        flt.close()
+        idx.close()
