@@ -89,6 +89,14 @@ _SIGNATURES = {
     "rq_search_grouped_fixup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_group_fill_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_group_members_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_group_members_fixup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_group_members": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int]),
     "rq_nb_rope_table_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
@@ -534,6 +542,62 @@ class NativeIndex:
         self._check_grouped(B, k, m, METRIC_COSINE)
         _check(self._lib.rq_group_collapse_device(self._h, _ptr(d_cand_rows), _ptr(d_cand_scores), _ptr(d_cand_groups), int(B), int(m), int(k), _ptr(d_scores),
                                                   _ptr(d_rows), _ptr(d_groups), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)), "rq_group_collapse_device")
+
+    # -- group members (include/rq.h "group members") -----------------------------------------------------
+    @staticmethod
+    def _check_group_members(B: int, k: int, group_size: int, metric: int) -> None:
+        if not 1 <= int(B) <= 65535:
+            raise ValueError(f"B {B} outside 1..65535")
+        if int(k) < 1 or int(group_size) < 1 or int(k) * int(group_size) > MAX_K:
+            raise ValueError(f"k {k} x group_size {group_size} outside 1..{MAX_K}")
+        if int(metric) not in (METRIC_COSINE, METRIC_IP):
+            raise ValueError(f"unknown metric {metric!r}")
+
+    def search_group_members(self, queries: np.ndarray, k: int, group_size: int, metric: int = METRIC_COSINE, *, row_filter: Optional[RowFilter] = None
+                             ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The best `group_size` rows of each of the k best groups per query (include/rq.h rq_search_group_members): (scores [B][k][s],
+        rows [B][k][s], groups [B][k], counts [B][k]); members best first, (0.0, -1) padded beyond a slot's count, slots beyond the
+        distinct groups among the rows in play are (0.0, -1, GROUP_NONE, 0)."""
+        q = self._as_queries(queries)
+        B = q.shape[0]
+        self._check_group_members(B, k, group_size, metric)
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        k, s = int(k), int(group_size)
+        scores = np.empty((B, k, s), dtype=np.float32)
+        rows = np.empty((B, k, s), dtype=np.int64)
+        groups = np.empty((B, k), dtype=np.int32)
+        counts = np.empty((B, k), dtype=np.int32)
+        _check(self._lib.rq_search_group_members(self._h, flt, _ptr(q), B, k, s, int(metric), _ptr(scores), _ptr(rows), _ptr(groups), _ptr(counts)),
+               "rq_search_group_members")
+        return scores, rows, groups, counts
+
+    def search_group_members_device(self, d_queries, B: int, k: int, group_size: int, metric: int, d_scores, d_rows, d_groups, d_count, d_status,
+                                    stream: int = 0, *, row_filter: Optional[RowFilter] = None) -> None:
+        """Asynchronous form over device memory (include/rq.h rq_search_group_members_device): d_scores / d_rows [B][k][s], d_groups /
+        d_count [B][k] int32, d_status [B] int32 (1 = repair that query with search_group_members_fixup_device)."""
+        self._check_group_members(B, k, group_size, metric)
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        _check(self._lib.rq_search_group_members_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(group_size), int(metric), _ptr(d_scores),
+                                                        _ptr(d_rows), _ptr(d_groups), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)),
+               "rq_search_group_members_device")
+
+    def search_group_members_fixup_device(self, d_queries, B: int, k: int, group_size: int, metric: int, d_scores, d_rows, d_groups, d_count, d_status,
+                                          stream: int = 0, *, row_filter: Optional[RowFilter] = None) -> int:
+        self._check_group_members(B, k, group_size, metric)
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        return _check(self._lib.rq_search_group_members_fixup_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(group_size), int(metric),
+                                                                     _ptr(d_scores), _ptr(d_rows), _ptr(d_groups), _ptr(d_count), _ptr(d_status),
+                                                                     C.c_void_p(stream)), "rq_search_group_members_fixup_device")
+
+    def group_fill_device(self, d_queries, B: int, k: int, group_size: int, metric: int, d_win_rows, d_win_groups, d_scores, d_rows, d_count, d_status,
+                          stream: int = 0, *, row_filter: Optional[RowFilter] = None) -> None:
+        """Asynchronous fill over a caller's group slots (include/rq.h rq_group_fill_device): d_win_rows [B][k] int64 global rows,
+        d_win_groups [B][k] int32 ids; the best `group_size` members of every slot's group."""
+        self._check_group_members(B, k, group_size, metric)
+        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        _check(self._lib.rq_group_fill_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(group_size), int(metric), _ptr(d_win_rows),
+                                              _ptr(d_win_groups), _ptr(d_scores), _ptr(d_rows), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)),
+               "rq_group_fill_device")
 
     def search_hint_next_device(self, d_next_queries, B: int, stream: int = 0) -> None:
         """Announce the queries of the NEXT search_device call on `stream` (include/rq.h: rq_search_hint_next_device)."""

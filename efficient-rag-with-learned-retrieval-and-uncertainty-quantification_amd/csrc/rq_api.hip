@@ -8,7 +8,7 @@
 // plus one workspace per stream (query fragments, per-bin scan records, bin keys, candidate keys).
 // Internal definitions: rq_index.h; searches: rq_search.hip (what a call does: rq_plan.h); the int8 image: rq_scan8.hip; filtered
 // searches: rq_filter.hip; the multi-device parent (n_devices > 1): rq_multi.hip.
-#include "rq_plan.h"
+#include "rq_group_members_plan.h"
 
 hipError_t rq_rowscale_launch(const double* norm64, int64_t row_begin, int64_t row_end, float* inv_norm, hipStream_t stream);
 
@@ -128,7 +128,8 @@ extern "C" void rq_index_destroy(rq_index* idx) {
     (void)hipDeviceSynchronize();
     for (auto& kv : idx->ctx) free_ctx(kv.second);
     free_filters(idx);   // the filters nobody destroyed (include/rq.h rq_filter_destroy)
-    free_dev(idx->range_bins, idx->d_groups);
+    free_dev(idx->range_bins, idx->d_groups, idx->gm_scored);
+    drop_group_table(idx);
     for (auto& ev : idx->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (idx->hs_pin) (void)hipHostFree(idx->hs_pin);
     if (idx->hs_pin_q) (void)hipHostFree(idx->hs_pin_q);
@@ -303,6 +304,7 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     else if (s == "range_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "range_route must be -1 (rule), 1 (scan), 2 (gather) or 3 (exact)"); idx->range_route = (int)v; }   // rq_range_plan.h
     else if (s == "range_cand_cap") { if (v < 0 || v > (1 << 20)) return set_err(RQ_EINVAL, "range_cand_cap must be 0 (default) .. 1048576"); idx->range_cand_cap = (int)v; }   // test hook (never below a call's cap)
     else if (s == "group_fetch") { if (!(v >= 1 && v <= RQ_MAX_K)) return set_err(RQ_EINVAL, "group_fetch must be 1..%d", RQ_MAX_K); idx->group_fetch = (int)v; }   // rq_group_plan.h group_fetch
+    else if (s == "group_fill_cap") { if (!(v >= 0 && v <= RQ_GROUP_FILL_MAX)) return set_err(RQ_EINVAL, "group_fill_cap must be 0 (default) .. %d", RQ_GROUP_FILL_MAX); idx->group_fill_cap = (int)v; }   // test hook (rq_group_members_plan.h group_fill_cap)
     else if (s == "group_fetch_cap") { if (!(v >= 0 && v <= RQ_MAX_K)) return set_err(RQ_EINVAL, "group_fetch_cap must be 0 (default) .. %d", RQ_MAX_K); idx->group_fetch_cap = (int)v; }   // test hook (never below a call's k)
     else if (s == "poison_cand") idx->poison_cand = (int)v;   // test hook: candidate lists are filled with 0xff..ff keys before every tail
     else if (s == "poison_bins") idx->poison_bins = (int)v;   // test hook: the query slots a call's passes cover are filled with 0xff bytes before its scan
@@ -390,6 +392,19 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
     if (s == "group_calls") return (double)idx->group_calls;         // collapses launched (rq_group_collapse_device, rq_search_grouped*)
     if (s == "group_repaired") return (double)idx->group_repaired;   // queries the grouped fixup repaired
     if (s == "group_rounds_last") return (double)idx->group_rounds_last;   // exclusion rounds of the last grouped fixup, all its queries
+    if (s == "group_fill_cap") return idx->group_fill_cap;
+    if (s == "group_table_builds") return (double)idx->group_table_builds;   // member tables built (rq_group_members.hip)
+    if (s == "group_fill_calls") return (double)idx->group_fill_calls;       // fill launches (every entry point, the repair's included)
+    if (s == "group_fill_repaired") return (double)idx->group_fill_repaired; // queries the member fixup filled by the exact route
+    if (s == "group_fill_rows_last") {   // members the last fill scored, all its slots (-1: no fill yet); waits for the device
+        if (!idx->gm_scored || idx->gm_scored_slots <= 0) return idx->group_fill_calls > 0 ? 0.0 : -1.0;
+        DeviceGuard dg_(idx->device);
+        std::vector<int> h((size_t)idx->gm_scored_slots);
+        if (!dg_.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(h.data(), idx->gm_scored, h.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return NAN;
+        double v = 0;
+        for (int x : h) v += x;
+        return v;
+    }
     if (s == "repaired_queries") return (double)idx->repaired_total;   // queries rq_search_fixup_device (or the blocking rq_search) had to repair so far
     if (s == "scan8_used") return (double)idx->scan8_used;   // searches that scanned the int8 image
     if (s == "hints_used") return (double)idx->hints_used;   // searches that found their queries prepared by the launch before them

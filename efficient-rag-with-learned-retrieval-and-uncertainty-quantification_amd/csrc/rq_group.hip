@@ -141,6 +141,7 @@ extern "C" int rq_index_set_groups(rq_index* idx, int64_t row_begin, int64_t n_r
     // as an append: searches in flight on any stream may still read the ids
     if (int r = flush_all(idx)) return r;
     HIPCHK(hipDeviceSynchronize());
+    drop_group_table(idx);   // the member table follows the ids: the next fill builds it again (rq_group_members.hip)
     if (!idx->d_groups) {
         int32_t* fresh = nullptr;
         if (hipMalloc((void**)&fresh, (size_t)idx->cap * sizeof(int32_t)) != hipSuccess) {
@@ -173,10 +174,6 @@ extern "C" int rq_index_get_groups(const rq_index* idx, int64_t row_begin, int64
 }
 
 // ---- the collapse -----------------------------------------------------------------------------------
-struct GroupOut {   // a call's device outputs (keys may be null)
-    float* scores; int64_t* rows; int32_t* groups; uint64_t* keys; int* status;
-};
-
 static int group_collapse(rq_index* idx, const int64_t* d_cand_rows, const float* d_cand_scores, const int32_t* d_cand_groups, const int* d_search_status,
                           int B, int m, int k, bool complete, const GroupOut& out, hipStream_t s) {
     const GroupGeometry g = group_geometry(B, m);
@@ -219,7 +216,7 @@ static int group_fill_empty(int B, int k, const GroupOut& out, hipStream_t s) {
 }
 
 // Rung 1: the exact search for m1 = "group_fetch" x k rows into the stream's candidate buffers, then the collapse.  Nothing waits.
-static int search_grouped_device(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const GroupOut& out, hipStream_t s) {
+int search_grouped_device(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const GroupOut& out, hipStream_t s) {
     // like a "pipeline" = 0 call: whatever the stream still defers (fused tail, scanned-ahead pair, hint) is completed first
     if (int r = flush_tails(idx, s)) return r;
     const int64_t play = rows_in_play(idx, f);
@@ -321,7 +318,7 @@ static int group_exclusion_loop(rq_index* idx, const rq_filter* f, const float* 
 
 // Synchronises `s`, repairs the flagged queries: rung 2 = the widest list a rung may ask for, repaired by the usual ladder and
 // collapsed; rung 3 = the exclusion loop for the queries still short of k groups.  Returns how many queries it repaired.
-static int grouped_fixup(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const GroupOut& out, hipStream_t s) {
+int grouped_fixup(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const GroupOut& out, hipStream_t s) {
     if (int r = flush_tails(idx, s)) return r;
     Stage fx(s);
     RepairList bad;

@@ -1,5 +1,5 @@
 // rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
-// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_range.hip (range searches), rq_group.hip (grouped searches), rq_scan8.hip (the int8 image and its ladder) and
+// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_range.hip (range searches), rq_group.hip (grouped searches), rq_group_members.hip (the members of the top groups), rq_scan8.hip (the int8 image and its ladder) and
 // rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard, the pieces
 // of a call that the routes share.  The staging of the blocking host-buffer forms is rq_stage.h's.
 // Not part of the public boundary (that is include/rq.h).
@@ -124,6 +124,11 @@ struct StreamCtx {
     int* grp_status = nullptr;
     size_t grp_elems = 0;
     int grp_bcap = 0;
+    // group members (rq_group_members.hip): the winners of the stream's last rq_search_group_members_device call ([B][k] scores and
+    // rows, gm_elems allocated of each); the fill reads the rows
+    float* gm_scores = nullptr;
+    int64_t* gm_rows = nullptr;
+    size_t gm_elems = 0;
 };
 
 // A row filter (include/rq.h rq_filter): the set of local rows a filtered search may return.  It belongs to one index at one size
@@ -236,6 +241,17 @@ struct rq_index {
     int group_fetch = 8;               // option "group_fetch": the first rung fetches this multiple of k (rq_group_plan.h)
     int group_fetch_cap = 0;           // option "group_fetch_cap": the largest m any rung asks for (test hook; 0 = RQ_MAX_K)
     int64_t group_calls = 0, group_repaired = 0, group_rounds_last = 0;   // collapses launched; queries the fixup repaired; exclusion rounds of the last fixup
+    // group members (rq_group_members.hip): the member table (rq_group_members_plan.h GroupTable) on the device, built from h_groups by
+    // the first fill that needs it and dropped by rq_index_set_groups; appended rows are RQ_GROUP_NONE and belong to no list
+    int32_t* gt_ids = nullptr;         // [gt_groups] distinct ids, ascending
+    uint32_t* gt_off = nullptr;        // [gt_groups + 1]
+    uint32_t* gt_rows = nullptr;       // [grouped rows] local rows by (id, row)
+    int64_t gt_groups = 0, gt_largest = 0;
+    bool gt_valid = false;
+    int group_fill_cap = 0;            // option "group_fill_cap": rows of a group the fill kernel takes (test hook; 0 = RQ_GROUP_FILL_MAX, can only lower it)
+    int64_t group_table_builds = 0, group_fill_calls = 0, group_fill_repaired = 0;   // table builds; fill launches; queries the member fixup filled by the exact route
+    int* gm_scored = nullptr;          // device: members scored by the last fill, one word per (query, slot) ("group_fill_rows_last")
+    int64_t gm_scored_slots = 0, gm_scored_cap = 0;
 };
 
 // Derived bound on |approximate scan score - exact score| for unit queries and cosine scaling:
@@ -312,6 +328,14 @@ RQ_INTERNAL int check_filter(const rq_index* idx, const rq_filter* f);   // null
 RQ_INTERNAL int ensure_filter_list(rq_filter* f);   // f->d_list: every allowed row, ascending (the gather routes)
 RQ_INTERNAL int search_filtered_device(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s);
 RQ_INTERNAL int flush_all(rq_index* idx);   // launches every tail still waiting for a scan ("pipeline" = 2)
+// rq_group.hip
+struct GroupOut {   // a grouped call's device outputs (keys may be null)
+    float* scores; int64_t* rows; int32_t* groups; uint64_t* keys; int* status;
+};
+RQ_INTERNAL int search_grouped_device(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const GroupOut& out, hipStream_t s);   // rung 1, nothing waits
+RQ_INTERNAL int grouped_fixup(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const GroupOut& out, hipStream_t s);   // rungs 2 and 3; queries repaired
+// rq_group_members.hip
+RQ_INTERNAL void drop_group_table(rq_index* idx);   // rq_index_set_groups, rq_index_destroy (the device is idle)
 RQ_INTERNAL void free_ctx(StreamCtx& c);
 // rq_scan8.hip
 RQ_INTERNAL void drop_x8(rq_index* idx);

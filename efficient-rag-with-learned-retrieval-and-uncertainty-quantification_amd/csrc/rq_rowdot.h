@@ -1,6 +1,7 @@
 // rq_rowdot.h -- the fp64 dot product of stored fp16 rows with an fp32 vector in LDS, 16 lanes per row: the arithmetic shared by
 // rq_gather_score_kernel (rq_filter.hip: a query against the listed rows), rq_mmr_kernel (rq_mmr.hip: the row just selected
-// against the remaining candidates) and rq_score_rows_kernel (rq_score.hip: a query against its own list).  Lane sub = lane & 15
+// against the remaining candidates), rq_score_rows_kernel (rq_score.hip: a query against its own list) and rq_group_members_kernel
+// (rq_group_members.hip: a query against the rows of a group).  Lane sub = lane & 15
 // of a row's 16 lanes owns elements pp * 128 + 8 * sub + e (one 16-byte load per pp), the products are formed in fp64 and added
 // in element order, then an xor butterfly over the 16 lanes.  The tail does NOT call this: rq_tail_body.h phase C keeps its own
 // copy of the same summation order (a call changes the tail kernels' registers) -- one order, hence the same bits everywhere.

@@ -111,7 +111,7 @@ void free_ctx(StreamCtx& c) {
     free_ws(c.w[0]);
     free_ws(c.w[1]);
     for (QuerySet& r : c.ring) free_queries(r);
-    free_dev(c.grp_scores, c.grp_rows, c.grp_status);
+    free_dev(c.grp_scores, c.grp_rows, c.grp_status, c.gm_scores, c.gm_rows);
     if (c.tail) (void)hipStreamDestroy(c.tail);
     for (int p = 0; p < 2; ++p) {
         if (c.ev_scan[p]) (void)hipEventDestroy(c.ev_scan[p]);

@@ -110,6 +110,23 @@ def _meta_group_value(meta: Optional[Dict[str, Any]], key: str):
     return value
 
 
+def _per_group_size(distinct_by: Optional[str], per_group: Optional[int]) -> int:
+    """`per_group=` (how many passages of each group a `distinct_by=` search returns) as a checked int; absent = 1."""
+    if per_group is None:
+        return 1
+    if distinct_by is None:
+        raise ValueError("per_group needs distinct_by")
+    if isinstance(per_group, bool) or not isinstance(per_group, (int, np.integer)) or int(per_group) < 1:
+        raise ValueError(f"per_group must be an integer >= 1, got {per_group!r}")
+    return int(per_group)
+
+
+def _refuse_per_group(per_group: Optional[int], what: str) -> None:
+    """The calls that return one passage per group only (the sparse side, the fused lists, the row forms)."""
+    if per_group is not None and (isinstance(per_group, bool) or not isinstance(per_group, (int, np.integer)) or int(per_group) != 1):
+        raise ValueError(f"{what} returns one passage per group: per_group={per_group!r} is not supported (use DenseIndex.search)")
+
+
 def _group_value(doc: "Document", key: str):
     """... of a Document: the metadata DenseIndex.add_documents stores for it, {"title": title, **metadata}."""
     return _meta_group_value({"title": doc.title or "", **(doc.metadata or {})}, key)
@@ -347,9 +364,10 @@ class BM25Index:
             out.append((self.doc_ids[i], float(scores[i])))
         return out
 
-    def search(self, query: str, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[Tuple[str, float]]:
+    def search(self, query: str, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[Tuple[str, float]]:
         if self.bm25 is None or not self.doc_ids:
             return []
+        _refuse_per_group(per_group, "BM25Index.search")
         if distinct_by is not None:
             return self._search_distinct(query, top_k, distinct_by, allowed_ids)
         if allowed_ids is not None:
@@ -910,12 +928,36 @@ class DenseIndex:
             if own:
                 flt.close()
 
-    def search_vectors(self, vectors: np.ndarray, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[List[Tuple[str, float, str]]]:
+    def _group_member_rows(self, vectors: np.ndarray, top_k: int, distinct_by: str, per_group: int, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores, rows), each [B][k x per_group]: the best per_group passages of each of the top_k groups, group by group, members
+        best first; entries a group does not fill, and groups beyond those in play, are (0.0, -1) (include/rq.h "group members").
+        top_k is clamped so that k x per_group <= MAX_K."""
+        if per_group > _native.MAX_K:
+            raise ValueError(f"per_group {per_group} beyond {_native.MAX_K}")
+        if not hasattr(self._index, "search_group_members"):
+            raise _native.RqError("grouped searches need a single-device index")
+        self._push_groups(distinct_by)
+        k = min(int(top_k), len(self._ids), _native.MAX_K // per_group)
+        own = allowed_ids is not None and not isinstance(allowed_ids, _native.RowFilter)
+        flt = self.make_filter(allowed_ids) if own else allowed_ids
+        try:
+            scores, rows = self._index.search_group_members(vectors, k, per_group, self.metric, row_filter=flt)[:2]
+        finally:
+            if own:
+                flt.close()
+        B = rows.shape[0]
+        return scores.reshape(B, k * per_group), rows.reshape(B, k * per_group)
+
+    def search_vectors(self, vectors: np.ndarray, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
+                       per_group: Optional[int] = None) -> List[List[Tuple[str, float, str]]]:
+        per = _per_group_size(distinct_by, per_group)
         vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
         if self._index is None or len(self._ids) == 0 or top_k <= 0:
             return [[] for _ in range(vectors.shape[0])]
         if vectors.shape[1] != self.dim:
             raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
+        if per > 1:   # (the best `per` passages of each of the top_k groups, group by group: up to top_k x per entries, no padding)
+            return self._assemble(*self._group_member_rows(vectors, top_k, distinct_by, per, allowed_ids))
         if distinct_by is not None:
             return self._assemble(*self._grouped_rows(vectors, top_k, distinct_by, allowed_ids))
         if allowed_ids is not None:
@@ -1150,10 +1192,12 @@ class DenseIndex:
         rows = np.fromiter((self._row_of.get(d, -1) for d in ids), np.int64, len(ids))[None, :]
         return self.score_rows_batch([query], rows)[0].astype(np.float64).tolist()
 
-    def search_rows_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def search_rows_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
+                          per_group: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """`search_batch` without the (doc_id, score, text) tuples: (scores float32 [B][k], rows int64 [B][k], -1 padded; row r is
         `self._ids[r]`), k = min(top_k, len(self)).  What HybridRetriever's batched fusion consumes (extension).
         `allowed_ids` (ids or a `make_filter` result): only those passages are ranked; the queries then take the host path."""
+        _refuse_per_group(per_group, "search_rows_batch")
         B = len(queries)
         if self._index is None or len(self._ids) == 0 or top_k <= 0 or B == 0:
             return np.zeros((B, 0), np.float32), np.zeros((B, 0), np.int64)
@@ -1172,9 +1216,13 @@ class DenseIndex:
         k = min(int(top_k), len(self._ids), _native.MAX_K)
         return self._index.search(self._embed_matrix(list(queries)), k, self.metric)
 
-    def search_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[List[Tuple[str, float, str]]]:
+    def search_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
+                     per_group: Optional[int] = None) -> List[List[Tuple[str, float, str]]]:
+        per = _per_group_size(distinct_by, per_group)
         if not queries:
             return []
+        if per > 1:
+            return self.search_vectors(self._embed_matrix(list(queries)), top_k, allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per)
         if distinct_by is not None:   # (the device-embedder route is not extended: the queries take the host path)
             return self.search_vectors(self._embed_matrix(list(queries)), top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)
         if allowed_ids is not None:   # (ids or a `make_filter` result: only those passages are ranked)
@@ -1191,11 +1239,16 @@ class DenseIndex:
                 return self.search_device_vectors(d_q, top_k)
         return self.search_vectors(self._embed_matrix(list(queries)), top_k)
 
-    def search(self, query: str, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[Tuple[str, float, str]]:
+    def search(self, query: str, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
+               per_group: Optional[int] = None) -> List[Tuple[str, float, str]]:
         """List of (doc_id, score, text), best first; score = cosine similarity (= 1 - Chroma distance).  `allowed_ids` (keyword-only
         extension: ids, or a `make_filter` result for reuse) restricts the ranking to those passages, like a Chroma `where`.
         `distinct_by` (keyword-only extension: a metadata key, e.g. "title") returns one passage per value of that field -- the best
-        passage of each of the top_k groups; a passage without the field is a group of its own.  It combines with `allowed_ids`."""
+        passage of each of the top_k groups; a passage without the field is a group of its own.  It combines with `allowed_ids`.
+        `per_group` (with `distinct_by`; default 1): the best per_group passages of each of the top_k groups, group by group, members
+        best first -- up to top_k x per_group entries."""
+        if _per_group_size(distinct_by, per_group) > 1:
+            return self.search_batch([query], top_k, allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per_group)[0]
         if distinct_by is not None:
             return self.search_batch([query], top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)[0]
         if allowed_ids is not None:
@@ -1301,7 +1354,10 @@ class HybridRetriever:
     # `where` of a Chroma query.  The sparse side needs the ids themselves; the dense side also takes a DenseIndex.make_filter result.
     # `distinct_by` (keyword-only extension on the per-query calls, a metadata key such as "title"): one passage per value of that
     # field on each side, and the fused list is collapsed once more by best hybrid score.  The `*_batch` fusions are not extended.
-    def bm25_search(self, query: str, top_k: int = 20, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[Tuple[str, float]]:
+    # `per_group` (with `distinct_by`): `dense_search` alone passes it on (DenseIndex.search); the sparse side and the fused list
+    # return one passage per group, and refuse any other value.
+    def bm25_search(self, query: str, top_k: int = 20, *, allowed_ids=None, distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[Tuple[str, float]]:
+        _refuse_per_group(per_group, "bm25_search")
         if self.bm25_index is None:
             return []
         if distinct_by is not None:
@@ -1310,9 +1366,12 @@ class HybridRetriever:
             return self.bm25_index.search(query, top_k, allowed_ids=allowed_ids)
         return self.bm25_index.search(query, top_k)
 
-    def dense_search(self, query: str, top_k: int = 20, *, allowed_ids=None, distinct_by: Optional[str] = None) -> List[Tuple[str, float]]:
+    def dense_search(self, query: str, top_k: int = 20, *, allowed_ids=None, distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[Tuple[str, float]]:
+        per = _per_group_size(distinct_by, per_group)
         if self.dense_index is None:
             return []
+        if per > 1:   # (the best `per` passages of each of the top_k groups: DenseIndex.search)
+            return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per)]
         if distinct_by is not None:
             return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)]
         if allowed_ids is not None:
@@ -1421,7 +1480,8 @@ class HybridRetriever:
         return bm25_list, dense_list, (bm25_extra, dense_extra)
 
     def hybrid_search(self, query: str, top_k: int = 10, retrieval_pool_size: int = 50, *, allowed_ids=None, complete_scores: bool = False,
-                      distinct_by: Optional[str] = None) -> List[RetrievalResult]:
+                      distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[RetrievalResult]:
+        _refuse_per_group(per_group, "hybrid_search")
         if distinct_by is not None:
             if complete_scores:
                 raise ValueError("distinct_by does not combine with complete_scores")

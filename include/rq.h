@@ -356,8 +356,9 @@ int rq_search_range(rq_index* idx, const rq_filter* f, const float* queries, int
  *   filter checks are those of rq_search_filtered (another index's filter, a stale filter: RQ_EINVAL); RQ_EUNSUPPORTED on a multi-device
  *   index, for every call of this section; RQ_ENODEVICE as everywhere.  One rq_index from one thread at a time, and no
  *   rq_index_set_groups while a grouped call is in flight.
- * Not extended: one row per group only -- group_size > 1 needs per-group member counts and a row list per group; rq_search_train_device,
- *   hints, "pipeline" 1 and 2, "scan_ahead", multi-device indexes.
+ * Not extended: these calls return one row per group only -- group_size > 1 needs per-group member counts and a row list per group, and
+ *   is served by rq_search_group_members* ("group members", below); rq_search_train_device, hints, "pipeline" 1 and 2, "scan_ahead",
+ *   multi-device indexes.
  * rq_timing counts a grouped call as a search (searches, queries; its repairs as the ladder counts them).
  * Options: "group_fetch" (1 .. RQ_MAX_K, default 8: the first rung asks for m1 = this multiple of k, clamped to [k, min(rows in play,
  *   RQ_MAX_K)]; the default is the measured choice of DESIGN.md 4.16); "group_fetch_cap" (test hook, like "range_cand_cap": the largest m
@@ -375,6 +376,67 @@ int rq_search_grouped_fixup_device(rq_index* idx, const rq_filter* f, const floa
                                    int32_t* d_groups, uint64_t* d_keys, int* d_status, void* stream);
 int rq_search_grouped(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int metric, float* out_scores, int64_t* out_rows,
                       int32_t* out_groups);
+
+/* ---- group members: the best s rows of each of the k best groups ("the top k articles, each with its two or three best passages":
+ * inner_hits / group_size elsewhere) -------------------------------------------------------------------------------------------------
+ * For a query, a group size s >= 1 and k >= 1 with k x s <= RQ_MAX_K:
+ *   groups and their rank: exactly as rq_search_grouped defines them -- rows in play, winner, groups rank by their winners,
+ *     k_eff = min(k, distinct groups among the rows in play).
+ *   members of a group: its rows in play, in the canonical order (score descending, then row ascending).  NaN counts as -inf; -0.0 is
+ *     +0.0; a zero-norm query scores every row 0.0; a -inf row is still a row; a row with RQ_GROUP_NONE is a group of one.
+ *   result: for group slot j < k_eff, count[q][j] = min(s, rows in play of that group); rows[q][j][0 .. count) and scores[q][j][0 .. count)
+ *     are the best members, best first; entries beyond count are (0.0, -1); slots beyond k_eff are (0.0, -1, RQ_GROUP_NONE, count 0).
+ *   Hence: s = 1 is rq_search_grouped's answer bit for bit; member 0 of every slot is that slot's winner, same row and same score bits;
+ *     every member's score has the bits rq_score_rows returns for that pair (the dot product of csrc/rq_rowdot.h over queries prepared
+ *     as rq_score_rows_device prepares them); with no group set every slot has count 1 and the result is rq_search's; a zero-norm query
+ *     returns the lowest s rows in play of each of the first k_eff groups.
+ * The members are fetched through the group, not through the ranking (a group's third-best row may rank anywhere): the library keeps a
+ *   group member table -- the rows with id >= 0 sorted by (id, row), the sorted distinct ids and their offsets; ids need not be dense,
+ *   the kernel finds a group's range by binary search.  It is built from the host copy of the ids by the FIRST call of this section that
+ *   needs it (blocking: a host sort and three uploads; rq_search_grouped users pay nothing) and dropped by rq_index_set_groups; an
+ *   append does not invalidate it (appended rows are RQ_GROUP_NONE and belong to no list), growth and rq_index_reserve leave it alone,
+ *   rq_index_destroy frees it, rq_save stays as it is.  Storage: 4 B per grouped row + 8 B per distinct group of HBM, and as much host
+ *   memory while it is built (the host copy of the ids, 4 B per row, is rq_index_set_groups's).
+ * The fill kernel (csrc/rq_group_members.hip): one workgroup per (query, group slot) scores every row of the slot's group that is in
+ *   play and sorts the keys in LDS; at most RQ_GROUP_FILL_MAX = 4096 rows (32 KiB of keys: a structural limit).  A group with more rows
+ *   in the table than option "group_fill_cap" is not filled: its slot gets count = -1 and (0.0, -1) entries, and the query's status
+ *   becomes 1.
+ * rq_group_fill_device: asynchronous, pure fill over a caller's groups (the articles of a fused hybrid pool, a grouped call's own
+ *   outputs): d_win_rows, d_win_groups [B][k] name the slots.  An absent slot (row -1 or outside [row_offset, row_offset +
+ *   rq_index_size)) gets count 0; a slot whose id is negative is its row alone (count 1 when the row is in play); otherwise the members
+ *   are the rows in play carrying the id (none: count 0); the same group may stand in two slots.  d_scores, d_rows [B][k][s], d_count
+ *   [B][k] (int32), d_status [B] (0, or 1 when a slot overflowed).  It behaves like rq_score_rows_device towards the stream: it completes
+ *   what `stream` defers, runs in stream order, defers nothing, and leaves no bin records.
+ * rq_search_group_members_device: asynchronous; the grouped search (rq_search_grouped_device's one rung, winners in the stream's
+ *   workspace: B x k x 12 bytes) then the fill.  d_groups [B][k].  d_status[q] = 0 iff the grouped stage proved the query and every
+ *   slot was filled; else call rq_search_group_members_fixup_device with the SAME arguments.
+ * rq_search_group_members_fixup_device: synchronises `stream`, repairs the flagged queries in place and returns how many it repaired:
+ *   their winners are searched again and repaired (Rung 2 and Rung 3 of rq_search_grouped_fixup_device), the fill runs again, and a slot
+ *   that still overflows takes the exact route -- the group's rows in play become a temporary rq_filter (built on the host from the
+ *   group copy and the caller's filter), the query is searched filtered for s rows and repaired by the usual ladder.
+ * rq_search_group_members: blocking, host buffers (out_scores, out_rows [B][k][s]; out_groups, out_count [B][k]; all required), staged
+ *   on the index's own stream like rq_search_grouped, repair included: B x (dim x 4 + k x s x 12 + k x 8 + 4) bytes of HBM for the call.
+ * RQ_EINVAL unless k >= 1, s >= 1, k x s <= RQ_MAX_K, 1 <= B <= 65535, a known metric and non-null pointers (f aside); the filter checks
+ *   are those of rq_search_filtered (another index's filter, a stale filter: RQ_EINVAL); RQ_EUNSUPPORTED on a multi-device index;
+ *   RQ_ENODEVICE as everywhere.  One rq_index from one thread at a time, and no rq_index_set_groups while such a call is in flight.
+ * Not extended: keys (d_keys) and merging members across shards -- a group's members in a shard where the group is not among that
+ *   shard's top k are not in that shard's lists, so the merge argument of DESIGN.md 4.16 does not carry over; rq_search_train_device;
+ *   hints; "pipeline" 1 and 2; "scan_ahead".
+ * rq_timing counts the call as a search, as a grouped call does.
+ * Options: "group_fill_cap" (test hook: rows of a group the fill kernel takes; it can only lower the maximum, 0 = default =
+ *   RQ_GROUP_FILL_MAX); read-only "group_table_builds" (member tables built), "group_fill_calls" (fills launched, every entry point and
+ *   the repair's), "group_fill_repaired" (queries the fixup filled by the exact route: those that held an overflowed slot; a query that
+ *   only its grouped stage flagged is counted by "group_repaired"), "group_fill_rows_last" (members scored by the last fill, summed over
+ *   its slots; -1 = none yet; waits for the device). */
+#define RQ_GROUP_FILL_MAX 4096
+int rq_group_fill_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int s, int metric, const int64_t* d_win_rows,
+                         const int32_t* d_win_groups, float* d_scores, int64_t* d_rows, int32_t* d_count, int* d_status, void* stream);
+int rq_search_group_members_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int s, int metric, float* d_scores,
+                                   int64_t* d_rows, int32_t* d_groups, int32_t* d_count, int* d_status, void* stream);
+int rq_search_group_members_fixup_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int s, int metric, float* d_scores,
+                                         int64_t* d_rows, int32_t* d_groups, int32_t* d_count, int* d_status, void* stream);
+int rq_search_group_members(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int s, int metric, float* out_scores, int64_t* out_rows,
+                            int32_t* out_groups, int32_t* out_count);
 
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
