@@ -26,7 +26,8 @@
  *   ip:      s = fp32( dot64(q, x) )
  *   order:   s descending, then row ascending;  k_eff = min(k, N);  missing entries row = -1.
  * Non-finite and extreme inputs, both metrics, every route (rq_search, the *_device forms, trains, multi-device indexes, filtered
- * searches, rq_search_mmr's candidates, rq_score_rows, rq_search_range; tests/nonfinite_oracle.py restates it):
+ * searches, rq_search_mmr's candidates, rq_score_rows, rq_search_range, the grouped calls rq_search_grouped* and rq_group_collapse_device,
+ * the group-member calls rq_search_group_members* and rq_group_fill_device; tests/nonfinite_oracle.py restates it):
  *   zero-norm query: a query whose fp64 norm is 0 scores every row 0.0, whatever the row holds (a NaN or infinite row included):
  *            its answer is rows 0 .. k_eff-1 (filtered: the first k_eff allowed rows) at 0.0.
  *   NaN:     any other score that comes out NaN (a NaN element on either side, inf - inf, 0 x inf, inf / inf -- under cosine every
@@ -37,7 +38,9 @@
  *   -0.0:    ranks with and is returned as +0.0.
  *   A query below RQ_TINY_QUERY_NORM (csrc/rq_final_body.h; fp32-subnormal elements) follows the definition with its 1e-30 as it
  *   stands.  Non-finite queries, and rows among the candidates that score -inf, are answered by the repair ladder (exact, slower);
- *   non-finite stored rows cost finite queries nothing.
+ *   non-finite stored rows cost finite queries nothing.  The grouped and group-member calls leave such queries
+ *   uncertified like any other search; they are answered by those calls' own fixups (rq_search_grouped_fixup_device: rung 2 and the
+ *   exclusion loop over all -inf and all +inf tie runs; rq_search_group_members_fixup_device: the same, then the fill again).
  */
 #ifndef RQ_H
 #define RQ_H
