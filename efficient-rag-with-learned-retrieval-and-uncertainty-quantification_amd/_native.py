@@ -70,6 +70,11 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_fixup_filtered_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_filtered_each": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rq_search_filtered_each_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_search_fixup_filtered_each_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_mmr_select_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rq_search_mmr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -350,6 +355,35 @@ class NativeIndex:
         return _check(self._lib.rq_search_fixup_device(self._h, _ptr(d_queries), int(B), int(k), int(metric), _ptr(d_scores),
                                                        _ptr(d_rows), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)),
                       "rq_search_fixup_device")
+
+    # -- per-query filters (include/rq.h "per-query filters") ------------------------------------------
+    def _filter_array(self, filters, B: int):
+        """The host array of B rq_filter pointers of an each-call: one open RowFilter or None (unrestricted) per query."""
+        filters = list(filters)
+        if len(filters) != int(B):
+            raise ValueError(f"expected one filter (or None) per query: {B} queries, {len(filters)} filters")
+        return (C.c_void_p * int(B))(*[None if f is None else self._filter_handle(f).value for f in filters])
+
+    def search_filtered_each(self, queries: np.ndarray, k: int, filters, metric: int = METRIC_COSINE) -> Tuple[np.ndarray, np.ndarray]:
+        """Query q over the rows of filters[q] only (a RowFilter, or None for every row), all in one call
+        (include/rq.h rq_search_filtered_each): blocking, host buffers, repair included."""
+        q = self._as_queries(queries)
+        B = q.shape[0]
+        arr = self._filter_array(filters, B)
+        scores = np.empty((B, int(k)), dtype=np.float32)
+        rows = np.empty((B, int(k)), dtype=np.int64)
+        _check(self._lib.rq_search_filtered_each(self._h, arr, _ptr(q), B, int(k), int(metric), _ptr(scores), _ptr(rows)), "rq_search_filtered_each")
+        return scores, rows
+
+    def search_filtered_each_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_keys, d_status, filters, stream: int = 0) -> None:
+        _check(self._lib.rq_search_filtered_each_device(self._h, self._filter_array(filters, B), _ptr(d_queries), int(B), int(k), int(metric),
+                                                        _ptr(d_scores), _ptr(d_rows), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)),
+               "rq_search_filtered_each_device")
+
+    def search_filtered_each_fixup_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_keys, d_status, filters, stream: int = 0) -> int:
+        return _check(self._lib.rq_search_fixup_filtered_each_device(self._h, self._filter_array(filters, B), _ptr(d_queries), int(B), int(k),
+                                                                     int(metric), _ptr(d_scores), _ptr(d_rows), _ptr(d_keys), _ptr(d_status),
+                                                                     C.c_void_p(stream)), "rq_search_fixup_filtered_each_device")
 
     # -- diversified search (include/rq.h "diversified search") --------------------------------------
     @staticmethod

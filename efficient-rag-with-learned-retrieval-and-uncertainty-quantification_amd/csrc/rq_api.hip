@@ -301,6 +301,7 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     else if (s == "use_hint") idx->use_hint = (int)v != 0;   // 0: rq_search_hint_next_device is ignored (A/B of the folded query preparation)
     else if (s == "scan_ahead") idx->scan_ahead = (int)v != 0;   // 0: a hinted batch is never scanned together with the call before it (A/B)
     else if (s == "filter_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "filter_route must be -1 (rule), 1 (gather), 2 (scan) or 3 (exact)"); idx->filter_route = (int)v; }   // rq_filter_plan.h
+    else if (s == "filter_each_key_cap") { if (!(v >= 0 && v <= (double)((int64_t)1 << 40))) return set_err(RQ_EINVAL, "filter_each_key_cap must be 0 (default) .. 2^40"); idx->each_key_cap = (int64_t)v; }   // test hook (rq_filter_each_plan.h: keys per ragged round)
     else if (s == "range_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "range_route must be -1 (rule), 1 (scan), 2 (gather) or 3 (exact)"); idx->range_route = (int)v; }   // rq_range_plan.h
     else if (s == "range_cand_cap") { if (v < 0 || v > (1 << 20)) return set_err(RQ_EINVAL, "range_cand_cap must be 0 (default) .. 1048576"); idx->range_cand_cap = (int)v; }   // test hook (never below a call's cap)
     else if (s == "group_fetch") { if (!(v >= 1 && v <= RQ_MAX_K)) return set_err(RQ_EINVAL, "group_fetch must be 1..%d", RQ_MAX_K); idx->group_fetch = (int)v; }   // rq_group_plan.h group_fetch
@@ -372,7 +373,14 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
     if (s == "filter_route") return idx->filter_route;
     if (s == "filter_route_last") return idx->filter_route_last;   // the route the last filtered call took (0: no row allowed; -1: none yet)
     if (s == "filter_repaired") return (double)idx->filter_repaired;   // queries of filtered calls that were repaired
-    if (s == "mmr_calls") return (double)idx->mmr_calls;   // MMR selections launched (rq_mmr_select_device, rq_search_mmr)
+    if (s == "filter_each_calls") return (double)idx->each_calls;               // searches with one filter per query so far (rq_filter_each.hip)
+    if (s == "filter_each_groups_last") return (double)idx->each_groups_last;   // distinct filters of the last one (NULL counts as one)
+    if (s == "filter_each_ragged_last") return (double)idx->each_ragged_last;   // queries its ragged launches answered
+    if (s == "filter_each_rounds_last") return (double)idx->each_rounds_last;   // ragged rounds it ran
+    if (s == "filter_each_shared_exact_last") return (double)idx->each_shared_last;   // queries its shared exact route answered
+    if (s == "filter_each_routes_last") return (double)idx->each_routes_last;   // bit r: some group took route r (4: the unrestricted group)
+    if (s == "filter_each_key_cap") return (double)idx->each_key_cap;
+    if (s == "mmr_calls") return (double)idx->mmr_calls;  // MMR selections launched (rq_mmr_select_device, rq_search_mmr)
     if (s == "score_calls") return (double)idx->score_calls;   // scoring calls (rq_score_rows_device, rq_score_rows)
     if (s == "score_pairs") return (double)idx->score_pairs;   // ... and the (query, row) pairs they were given: B x m each
     if (s == "range_route") return idx->range_route;

@@ -9,7 +9,7 @@
 // excluded rows' keys emptied.  Replaces the `where` restriction of the collection.query of reference
 // rag_uq/streaming_index.py:355-359.
 #include "rq_filter_plan.h"
-#include "rq_rowdot.h"
+#include "rq_gather_body.h"
 #include "rq_stage.h"
 
 // ---- kernels ------------------------------------------------------------------------------------
@@ -45,52 +45,13 @@ hipError_t rq_mask_keys_launch(uint64_t* cand, int64_t n, const uint32_t* bits, 
 // different queries (the rows come from the caches after their first reader); 256 threads.  The arithmetic of one row is
 // rq_tail_body.h phase C's: 16 lanes per row (sub = lane & 15 owns elements pp * 128 + 8 * sub + e), a wave takes 8 rows per
 // round, fp64 products in element order, xor butterfly over the 16 lanes -- the same summation order, hence the same bits
-// (rq_rowdot.h, shared with rq_mmr.hip).
+// (rq_rowdot.h, shared with rq_mmr.hip).  The body is rq_gather_body.h's, shared with the ragged gather of rq_filter_each.hip.
 template <int DP>
 __global__ __launch_bounds__(256) void rq_gather_score_kernel(RqGatherArgs a) {
-    static_assert(DP == 384 || DP == RQ_DPAD, "stored row length");
-    constexpr int NP = DP / 128;   // 16-byte loads per lane and row
     __shared__ __attribute__((aligned(16))) float qs[RQ_DPAD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = (int)blockIdx.x;
-#pragma unroll
-    for (int pp = 0; pp < 3; ++pp) qs[pp * 256 + tid] = a.q32[(size_t)q * RQ_DPAD + pp * 256 + tid];
-    __syncthreads();
-    const double qn = a.qnorm64[q];
-    const int sub = lane & 15, rloc = lane >> 4;
-    const char* xb = (const char*)a.x;
-    const int64_t base = (int64_t)blockIdx.y * 256;
-    uint64_t* out = a.cand + (int64_t)q * a.cand_stride;
-    for (int j0 = wave * 8; j0 < 256; j0 += 32) {
-        if (base + j0 >= a.nlist) break;   // uniform over the wave
-        rq_half8 xv[2][NP];
-        int64_t rows[2], slot[2];
-        double rn[2];
-        bool lv[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            slot[u] = base + j0 + u * 4 + rloc;
-            lv[u] = slot[u] < a.nlist;
-            rows[u] = (int64_t)a.list[lv[u] ? slot[u] : 0];   // (nlist >= 1; every listed row is below the shard's end)
-            rn[u] = a.rownorm64[rows[u]];
-            const char* r = xb + rows[u] * (DP * 2) + sub * 16;
-#pragma unroll
-            for (int pp = 0; pp < NP; ++pp) xv[u][pp] = *(const rq_half8*)(r + pp * 256);
-        }
-        double dot[2];
-        rq_rowdot16<NP, 2>(xv, qs, sub, dot);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const double d = dot[u];
-            if (sub == 0 && lv[u]) {
-                double sc = d;
-                if (a.metric == 0) sc = d / (qn * rn[u] + 1e-30);
-                if (qn == 0.0) sc = 0.0;   // a zero-norm query scores every row 0 (include/rq.h).  For consistency of the keys only:
-                                           // rq_final_kernel answers such a query (RqFinalArgs::first) before it reads them
-                out[slot[u]] = rq_make_key(rq_sanitize((float)sc), (uint32_t)rows[u]);
-            }
-        }
-    }
+    rq_gather_chunk<DP>(a.x, a.rownorm64, a.q32 + (size_t)q * RQ_DPAD, a.qnorm64[q], a.list, a.nlist, (int64_t)blockIdx.y * 256, a.metric,
+                        a.cand + (int64_t)q * a.cand_stride, qs);
 }
 hipError_t rq_gather_score_launch(const RqGatherArgs& a, int B, hipStream_t stream) {
     if (B < 1 || a.nlist < 1 || a.cand_stride < a.nlist || (a.dpad != 384 && a.dpad != RQ_DPAD)) return hipErrorInvalidValue;
@@ -264,6 +225,11 @@ int search_filtered_device(rq_index* idx, const rq_filter* cf, const float* d_q,
     const FilterShape shape{f->n, f->na, f->occ_prefix.data()};
     const int route = plan_filter(idx, shape, B, k, metric, idx->filter_route);
     idx->filter_route_last = route;
+    return run_filter_route(idx, f, route, d_q, B, k, metric, out, s);
+}
+
+// One filter's queries down the route the plan chose (search_filtered_device; the pass groups of rq_filter_each.hip).
+int run_filter_route(rq_index* idx, rq_filter* f, int route, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s) {
     if (route == FROUTE_EMPTY) {
         if (int r = mark_no_scan(idx, s)) return r;
         return fill_empty(B, k, out, s);

@@ -1,5 +1,5 @@
 // rq_index.h -- internal definitions shared by the host translation units: rq_api.hip (storage, options, the C ABI),
-// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_range.hip (range searches), rq_group.hip (grouped searches), rq_group_members.hip (the members of the top groups), rq_scan8.hip (the int8 image and its ladder) and
+// rq_search.hip (search orchestration), rq_filter.hip (filtered searches), rq_filter_each.hip (one filter per query), rq_mmr.hip (MMR selection), rq_score.hip (scoring given rows), rq_range.hip (range searches), rq_group.hip (grouped searches), rq_group_members.hip (the members of the top groups), rq_scan8.hip (the int8 image and its ladder) and
 // rq_multi.hip (the multi-device parent): error channel, the index object, the per-stream workspaces, the device guard, the pieces
 // of a call that the routes share.  The staging of the blocking host-buffer forms is rq_stage.h's.
 // Not part of the public boundary (that is include/rq.h).
@@ -129,6 +129,21 @@ struct StreamCtx {
     float* gm_scores = nullptr;
     int64_t* gm_rows = nullptr;
     size_t gm_elems = 0;
+    // one filter per query (rq_filter_each.hip).  The tables of a call (per-query descriptors, runs, batch positions) are written into
+    // pinned host memory and copied to each_tab on the stream; each_ev marks the end of that copy (the next call waits for it before
+    // it writes the pinned block again).  each_q .. each_status: the staging sub-batch of a group whose queries are not one
+    // contiguous run, [each_bcap] queries and [each_bcap][each_k] results.
+    char* each_pin = nullptr;
+    char* each_tab = nullptr;
+    size_t each_tab_bytes = 0;
+    hipEvent_t each_ev = nullptr;
+    bool each_ev_pending = false;
+    float* each_q = nullptr;
+    float* each_scores = nullptr;
+    int64_t* each_rows = nullptr;
+    uint64_t* each_keys = nullptr;
+    int* each_status = nullptr;
+    int each_bcap = 0, each_k = 0;
 };
 
 // A row filter (include/rq.h rq_filter): the set of local rows a filtered search may return.  It belongs to one index at one size
@@ -226,6 +241,10 @@ struct rq_index {
     int filter_route = -1;             // option "filter_route": -1 = the rule (rq_filter_plan.h), 1 gather, 2 scan, 3 exact
     int filter_route_last = -1;        // the route the last filtered call took (0 = empty filter)
     int64_t filter_repaired = 0;       // queries of filtered calls that came back uncertified and were repaired
+    // one filter per query (rq_filter_each.hip, rq_filter_each_plan.h): read-only options "filter_each_calls", "filter_each_groups_last",
+    // "filter_each_ragged_last", "filter_each_rounds_last", "filter_each_shared_exact_last", "filter_each_routes_last"
+    int64_t each_calls = 0, each_groups_last = 0, each_ragged_last = 0, each_rounds_last = 0, each_shared_last = 0, each_routes_last = 0;
+    int64_t each_key_cap = 0;          // option "filter_each_key_cap": keys per ragged round (test hook; 0 = 1 GiB / 8)
     int64_t mmr_calls = 0;             // option "mmr_calls": MMR selections launched (rq_mmr.hip)
     int64_t score_calls = 0, score_pairs = 0;   // options "score_calls" / "score_pairs": scoring calls and their B x m pairs (rq_score.hip)
     // range searches (rq_range.hip)
@@ -327,6 +346,8 @@ RQ_INTERNAL int ensure_filter_scale(rq_index* idx, const rq_filter* f, int metri
 RQ_INTERNAL int check_filter(const rq_index* idx, const rq_filter* f);   // null, another index's, stale, multi-device
 RQ_INTERNAL int ensure_filter_list(rq_filter* f);   // f->d_list: every allowed row, ascending (the gather routes)
 RQ_INTERNAL int search_filtered_device(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s);
+// one filter's queries down `route` (rq_filter_plan.h FilterRoute): what search_filtered_device does after its plan
+RQ_INTERNAL int run_filter_route(rq_index* idx, rq_filter* f, int route, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s);
 RQ_INTERNAL int flush_all(rq_index* idx);   // launches every tail still waiting for a scan ("pipeline" = 2)
 // rq_group.hip
 struct GroupOut {   // a grouped call's device outputs (keys may be null)

@@ -99,6 +99,19 @@ hipError_t rq_rescore_launch(const RqRescoreArgs& a, int B, hipStream_t stream);
 // (v_mfma_f64_16x16x4_f64, rq_exact.hip): a 16-row tile is read once for 64 queries instead of once per query.
 hipError_t rq_exact_scan_launch(const RqRescoreArgs& a, int B, int cu_count, hipStream_t stream);
 
+// One query of a launch whose queries each bring their own filter (rq_filter_each.hip, include/rq.h rq_search_filtered_each): where
+// its candidate keys are and how many, its filter's arrays, which prepared query it is and where its outputs go.
+struct RqEachDesc {
+    const uint32_t* list;      // ragged gather: the filter's listed rows [na], ascending
+    const uint32_t* first;     // the filter's first allowed rows (RqFilterArgs::first)
+    const uint32_t* bits;      // per-query key mask: the filter's bitmap
+    int64_t key_off;           // the query's candidate keys start at cand + key_off
+    int64_t ncand;             // ... and are this many (<= INT32_MAX)
+    int64_t na;                // allowed rows: the rows that can be returned
+    int q;                     // slot among the prepared queries (q32, qnorm64)
+    int out;                   // query of the call: row of the outputs
+};
+
 // Pass 4: top-k of the candidates, certificate, outputs.
 struct RqFinalArgs {
     const uint64_t* cand;      // [B][ncand]
@@ -119,6 +132,9 @@ struct RqFinalArgs {
     int64_t* out_rows;         // [B][k], -1 padded
     uint64_t* out_keys;        // [B][k] optional (global-row keys for cross-shard merging), may be null
     int* out_status;           // [B] 0 = certified exact, 1 = not certified
+    // Per-query bookkeeping (null = the uniform layout above).  With it workgroup b serves each[b]: keys cand + key_off, ncand of
+    // them, n_rows = na, first = that filter's, qnorm64[q], outputs of query `out`; ncand, n_rows and first above are not read.
+    const RqEachDesc* each = nullptr;
 };
 hipError_t rq_final_launch(const RqFinalArgs& a, int B, hipStream_t stream);
 
@@ -196,6 +212,43 @@ struct RqGatherArgs {
 };
 #define RQ_GATHER_MAX_CHUNKS 65535   // chunks of 256 listed rows per launch (grid y); rq_gather_score_launch loops beyond
 hipError_t rq_gather_score_launch(const RqGatherArgs& a, int B, hipStream_t stream);
+
+// ---- one filter per query (rq_filter_each.hip, include/rq.h rq_search_filtered_each) ----
+// The ragged gather: rq_gather_score_kernel with a list per query.  The queries of a launch come as runs that share a list
+// (RqEachRun: the queries of one filter); a work item is (run, 256-row chunk of its list, query of the run), the query running
+// fastest, so that the workgroups in flight together re-score the SAME 256 rows for the queries that share them -- the reason
+// rq_gather_score_kernel puts the query on blockIdx.x.  Item i of the launch belongs to the run with item_base <= i < the next
+// run's (found by bisection, uniform over the workgroup).  Keys: cand[each[j].key_off + position in the list], 64-bit offsets.
+struct RqEachRun {
+    int64_t item_base;         // work items of the runs before this one
+    int64_t na;                // rows of the run's list, >= 1
+    int first, count;          // the run's queries: each[first .. first + count)
+};
+struct RqRaggedArgs {
+    const void* x; int dpad;   // stored rows and their length in elements (768 or 384)
+    const double* rownorm64;
+    const float* q32;          // [prepared queries][768] raw fp32 queries, zero padded (rq_prep_body); addressed by each[j].q
+    const double* qnorm64;
+    const RqEachDesc* each;    // the launch's queries
+    const RqEachRun* runs; int nruns;   // nruns >= 1; runs[nruns] is a sentinel whose item_base is the number of items
+    int metric;
+    uint64_t* cand;
+};
+#define RQ_RAGGED_MAX_ITEMS 2147483647LL   // work items per launch (grid x); rq_gather_ragged_launch loops beyond
+hipError_t rq_gather_ragged_launch(const RqRaggedArgs& a, int64_t items, hipStream_t stream);
+// rq_mask_keys_launch with a bitmap per query: key j of query i (cand[each[i].key_off + j], j < each[i].ncand) becomes 0 unless
+// its row's bit is set in each[i].bits.  nq <= 65535.
+hipError_t rq_mask_keys_each_launch(uint64_t* cand, const RqEachDesc* each, int nq, int64_t max_ncand, hipStream_t stream);
+// Rows of [n][dim] floats gathered (dst[i] = src[pos[i]]) and a sub-batch's results scattered back to the queries pos[i] of the call
+// (scores / rows / keys [n][k], status [n]; keys may be null on both sides together); src null: the queries pos[i] get padding
+// (0.0, -1, key 0) and status 0.
+hipError_t rq_each_gather_rows_launch(const float* src, const int* pos, int n, int dim, float* dst, hipStream_t stream);
+struct RqEachScatterArgs {
+    const int* pos; int n, k;
+    const float* src_scores; const int64_t* src_rows; const uint64_t* src_keys; const int* src_status;   // src_scores null: padding
+    float* scores; int64_t* rows; uint64_t* keys; int* status;
+};
+hipError_t rq_each_scatter_launch(const RqEachScatterArgs& a, hipStream_t stream);
 
 // ---- MMR selection (rq_mmr.hip, include/rq.h rq_mmr_select_device): k of m candidate rows per query, greedily by
 // v = lambda rel - (1 - lambda) max similarity to the rows already picked; one workgroup per query ----

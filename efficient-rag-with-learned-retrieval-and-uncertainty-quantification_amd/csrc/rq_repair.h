@@ -1,5 +1,6 @@
 // rq_repair.h -- what the repairs of the device forms share (fixup_ladder in rq_search.hip, range_fixup in rq_range.hip, grouped_fixup
-// in rq_group.hip, group_members_fixup in rq_group_members.hip).  A repair reads the call's d_status and waits, lists the flagged queries, PACKS their inputs into the first slots of
+// in rq_group.hip, group_members_fixup in rq_group_members.hip; fixup_filtered_each in rq_filter_each.hip packs the flagged queries of a scattered group the same way
+// before it hands them to fixup_ladder).  A repair reads the call's d_status and waits, lists the flagged queries, PACKS their inputs into the first slots of
 // buffers of its own, runs them again, and UNPACKS the packed outputs over the flagged queries' outputs; the other queries' outputs are
 // not touched.  A column is one array of the call ("full", one entry per query) with its packed twin (one entry per slot) and the bytes
 // of an entry; a null column (the optional keys) is skipped.  Every copy is one D2D copy on the Stage's stream (rq_stage.h), in the

@@ -112,6 +112,9 @@ void free_ctx(StreamCtx& c) {
     free_ws(c.w[1]);
     for (QuerySet& r : c.ring) free_queries(r);
     free_dev(c.grp_scores, c.grp_rows, c.grp_status, c.gm_scores, c.gm_rows);
+    free_dev(c.each_tab, c.each_q, c.each_scores, c.each_rows, c.each_keys, c.each_status);
+    if (c.each_pin) (void)hipHostFree(c.each_pin);
+    if (c.each_ev) (void)hipEventDestroy(c.each_ev);
     if (c.tail) (void)hipStreamDestroy(c.tail);
     for (int p = 0; p < 2; ++p) {
         if (c.ev_scan[p]) (void)hipEventDestroy(c.ev_scan[p]);

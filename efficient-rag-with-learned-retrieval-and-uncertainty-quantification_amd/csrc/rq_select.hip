@@ -372,15 +372,24 @@ hipError_t rq_rescore_launch(const RqRescoreArgs& a, int B, hipStream_t stream) 
 __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a) {
     __shared__ uint64_t list[RQ_SEL_L];
     __shared__ int cnt;
-    const int q = blockIdx.x;
-    if (a.qnorm64[q] == 0.0) {
+    // per-query bookkeeping (RqFinalArgs::each): the workgroup's query brings its own keys, allowed rows and first rows
+    int q = blockIdx.x, ncand = a.ncand;
+    int64_t n_rows = a.n_rows, key_off = (int64_t)q * a.ncand;
+    const uint32_t* first = a.first;
+    double qn = 0.0;
+    if (a.each) {
+        const RqEachDesc d = a.each[blockIdx.x];
+        q = d.out; ncand = (int)d.ncand; n_rows = d.na; key_off = d.key_off; first = d.first;
+        qn = a.qnorm64[d.q];
+    } else qn = a.qnorm64[q];
+    if (qn == 0.0) {
         // a zero-norm query scores every row 0 (include/rq.h): the first rows that can be returned, as rq_final_body answers it --
         // whichever bins were re-scored (a bin of NaN rows is never among them: its approximate maximum is the smallest value)
-        const int64_t kk = a.k < a.n_rows ? a.k : a.n_rows;
+        const int64_t kk = a.k < n_rows ? a.k : n_rows;
         for (int j = threadIdx.x; j < a.k; j += RQ_SEL_THREADS) {
             const int64_t o = (int64_t)q * a.k + j;
             const bool v = j < kk;
-            const int64_t grow = a.row_offset + (v && a.first ? (int64_t)a.first[j] : (int64_t)j);
+            const int64_t grow = a.row_offset + (v && first ? (int64_t)first[j] : (int64_t)j);
             a.out_scores[o] = 0.f;
             a.out_rows[o] = v ? grow : -1;
             if (a.out_keys) a.out_keys[o] = v ? rq_make_key(0.f, (uint32_t)grow) : 0;
@@ -388,8 +397,8 @@ __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a)
         if (threadIdx.x == 0) a.out_status[q] = 0;
         return;   // uniform over the workgroup
     }
-    const uint64_t* c = a.cand + (int64_t)q * a.ncand;
-    const int have = rq_wg_topm([&](int64_t i) { return c[i]; }, a.ncand, a.k, list, &cnt);
+    const uint64_t* c = a.cand + key_off;
+    const int have = rq_wg_topm([&](int64_t i) { return c[i]; }, ncand, a.k, list, &cnt);
     for (int j = threadIdx.x; j < a.k; j += RQ_SEL_THREADS) {
         const int64_t o = (int64_t)q * a.k + j;
         if (j < have) {
@@ -409,10 +418,10 @@ __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a)
         // Certificate: every row outside the re-scored bins has approximate score <= b, hence exact
         // score <= b + eps (unit-query units). Exact iff that is strictly below the k-th exact score.
         int ok;
-        const int64_t kk = a.k < a.n_rows ? a.k : a.n_rows;   // rows that must be returned
+        const int64_t kk = a.k < n_rows ? a.k : n_rows;   // rows that must be returned
         if (a.nbins <= a.nb) {
             ok = 1;   // the whole shard was re-scored
-        } else if (have < kk || (a.metric == 0 && a.qnorm64[q] < RQ_TINY_QUERY_NORM)) {
+        } else if (have < kk || (a.metric == 0 && qn < RQ_TINY_QUERY_NORM)) {
             ok = 0;   // (tiny query: see rq_final_body.h RQ_TINY_QUERY_NORM)
         } else if (kk == 0) {
             ok = 1;
@@ -423,7 +432,7 @@ __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a)
             } else {
                 const double b = (double)rq_key_score(bkey);
                 const float sk = rq_key_score(list[kk - 1]);
-                ok = rq_certified(b, a.eps, a.max_row_norm, a.qnorm64[q], a.metric, sk) ? 1 : 0;   // (a zero-norm query never comes here: answered above)
+                ok = rq_certified(b, a.eps, a.max_row_norm, qn, a.metric, sk) ? 1 : 0;   // (a zero-norm query never comes here: answered above)
             }
         }
         a.out_status[q] = ok ? 0 : 1;
@@ -431,6 +440,7 @@ __global__ __launch_bounds__(RQ_SEL_THREADS) void rq_final_kernel(RqFinalArgs a)
 }
 hipError_t rq_final_launch(const RqFinalArgs& a, int B, hipStream_t stream) {
     if (a.k < 1 || a.k > RQ_SEL_L - RQ_SEL_THREADS) return hipErrorInvalidValue;
+    if (a.each && a.nbins > a.nb) return hipErrorInvalidValue;   // (per-query bookkeeping: for candidate sets that hold every row in play)
     hipLaunchKernelGGL(rq_final_kernel, dim3(B), dim3(RQ_SEL_THREADS), 0, stream, a);
     return hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// rq_stage.h -- the staging of ONE blocking call on one stream: the host-buffer forms (rq_search_filtered, rq_search_mmr, rq_score_rows,
+// rq_stage.h -- the staging of ONE blocking call on one stream: the host-buffer forms (rq_search_filtered, rq_search_filtered_each, rq_search_mmr, rq_score_rows,
 // rq_search_range, rq_search_grouped, rq_search_group_members: alloc, up, the device form, down, finish) and the repairs (fixup_ladder,
 // range_fixup, grouped_fixup and its exclusion rounds, group_members_fixup, through rq_repair.h: d2d, zero, launched).  The first failure sticks: every later step
 // returns it and issues nothing.  A call that leaves with work enqueued that finish() has not waited for -- whichever step failed, the

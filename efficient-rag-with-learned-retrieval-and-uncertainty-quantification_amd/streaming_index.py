@@ -891,6 +891,37 @@ class DenseIndex:
             if own:
                 flt.close()
 
+    @staticmethod
+    def _each_entries(allowed_ids_each, n_queries: int, allowed_ids=None, distinct_by=None, per_group=None) -> list:
+        """`allowed_ids_each=` as a checked list: one entry per query (a `make_filter` result, an iterable of ids, or None for an
+        unrestricted query); it does not combine with `allowed_ids`, `distinct_by` or `per_group`."""
+        if allowed_ids is not None or distinct_by is not None or per_group is not None:
+            raise ValueError("allowed_ids_each does not combine with allowed_ids, distinct_by or per_group")
+        entries = list(allowed_ids_each)
+        if len(entries) != int(n_queries):
+            raise ValueError(f"allowed_ids_each needs one entry per query: {n_queries} queries, {len(entries)} entries")
+        return entries
+
+    def _filtered_each_rows(self, vectors: np.ndarray, top_k: int, entries: list) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores, rows) with query q ranked over the passages of entries[q] only, all queries in ONE native call (include/rq.h
+        "per-query filters").  Id lists become filters for the call and are closed afterwards; the same object given for several
+        queries becomes one filter."""
+        k = min(int(top_k), len(self._ids), _native.MAX_K)
+        made = {}
+        try:
+            filters = []
+            for e in entries:
+                if e is None or isinstance(e, _native.RowFilter):
+                    filters.append(e)
+                    continue
+                if id(e) not in made:
+                    made[id(e)] = self.make_filter(e)
+                filters.append(made[id(e)])
+            return self._index.search_filtered_each(vectors, k, filters, self.metric)
+        finally:
+            for flt in made.values():
+                flt.close()
+
     # ---- grouped searches (extension: `distinct_by=` -- one passage per value of a metadata field, e.g. "title": the best passage
     # of each of the top_k articles of a chunked corpus; include/rq.h "grouped searches") --------------------------------------
     def _push_groups(self, key: str) -> None:
@@ -949,13 +980,18 @@ class DenseIndex:
         return scores.reshape(B, k * per_group), rows.reshape(B, k * per_group)
 
     def search_vectors(self, vectors: np.ndarray, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
-                       per_group: Optional[int] = None) -> List[List[Tuple[str, float, str]]]:
+                       per_group: Optional[int] = None, allowed_ids_each=None) -> List[List[Tuple[str, float, str]]]:
+        """`allowed_ids_each` (keyword-only): one entry per query -- a `make_filter` result, an iterable of ids, or None -- each
+        query ranked over its own passages, the whole batch in one native call."""
         per = _per_group_size(distinct_by, per_group)
         vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
+        each = None if allowed_ids_each is None else self._each_entries(allowed_ids_each, vectors.shape[0], allowed_ids, distinct_by, per_group)
         if self._index is None or len(self._ids) == 0 or top_k <= 0:
             return [[] for _ in range(vectors.shape[0])]
         if vectors.shape[1] != self.dim:
             raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
+        if each is not None:
+            return self._assemble(*self._filtered_each_rows(vectors, top_k, each))
         if per > 1:   # (the best `per` passages of each of the top_k groups, group by group: up to top_k x per entries, no padding)
             return self._assemble(*self._group_member_rows(vectors, top_k, distinct_by, per, allowed_ids))
         if distinct_by is not None:
@@ -1193,14 +1229,18 @@ class DenseIndex:
         return self.score_rows_batch([query], rows)[0].astype(np.float64).tolist()
 
     def search_rows_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
-                          per_group: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+                          per_group: Optional[int] = None, allowed_ids_each=None) -> Tuple[np.ndarray, np.ndarray]:
         """`search_batch` without the (doc_id, score, text) tuples: (scores float32 [B][k], rows int64 [B][k], -1 padded; row r is
         `self._ids[r]`), k = min(top_k, len(self)).  What HybridRetriever's batched fusion consumes (extension).
-        `allowed_ids` (ids or a `make_filter` result): only those passages are ranked; the queries then take the host path."""
+        `allowed_ids` (ids or a `make_filter` result): only those passages are ranked; the queries then take the host path.
+        `allowed_ids_each`: one such entry (or None) per query, as in `search_vectors`."""
         _refuse_per_group(per_group, "search_rows_batch")
         B = len(queries)
+        each = None if allowed_ids_each is None else self._each_entries(allowed_ids_each, B, allowed_ids, distinct_by, per_group)
         if self._index is None or len(self._ids) == 0 or top_k <= 0 or B == 0:
             return np.zeros((B, 0), np.float32), np.zeros((B, 0), np.int64)
+        if each is not None:
+            return self._filtered_each_rows(self._embed_matrix(list(queries)), top_k, each)
         if distinct_by is not None:   # (one passage per value of that metadata field: `_grouped_rows`)
             return self._grouped_rows(self._embed_matrix(list(queries)), top_k, distinct_by, allowed_ids)
         if allowed_ids is not None:
@@ -1217,8 +1257,13 @@ class DenseIndex:
         return self._index.search(self._embed_matrix(list(queries)), k, self.metric)
 
     def search_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
-                     per_group: Optional[int] = None) -> List[List[Tuple[str, float, str]]]:
+                     per_group: Optional[int] = None, allowed_ids_each=None) -> List[List[Tuple[str, float, str]]]:
+        """`allowed_ids_each` (keyword-only): one allowed set per query -- a batch of questions from different tenants, sources or
+        users in one native call; see `search_vectors`."""
         per = _per_group_size(distinct_by, per_group)
+        if allowed_ids_each is not None:   # (checked by search_vectors; the queries take the host path)
+            return self.search_vectors(self._embed_matrix(list(queries)) if queries else np.zeros((0, self.dim), np.float32), top_k,
+                                       allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per_group, allowed_ids_each=allowed_ids_each)
         if not queries:
             return []
         if per > 1:

@@ -194,6 +194,51 @@ int rq_search_filtered_device(rq_index* idx, const rq_filter* f, const float* d_
 int rq_search_fixup_filtered_device(rq_index* idx, const rq_filter* f, const float* d_queries, int B, int k, int metric, float* d_scores,
                                     int64_t* d_rows, uint64_t* d_keys, int* d_status, void* stream);
 
+/* ---- per-query filters: one allowed set per query in one call (a batch of questions from different tenants, sources or users) ----
+ * `filters` is a HOST array of B pointers, read during the call only and never kept: filters[q] restricts query q, a NULL entry
+ * leaves that query unrestricted, entries may repeat in any arrangement.
+ * Answer: query q's answer is, by definition, that of rq_search_filtered(idx, filters[q], ...) for that query alone (of rq_search for
+ *   a NULL entry): the same score definition, canonical order, NaN, -0.0 and +-inf rules; k_eff = min(k, allowed rows of THAT query's
+ *   filter), missing entries (0.0, -1) with key 0; a zero-norm query returns the first k_eff allowed rows of its own filter at 0.0;
+ *   row_offset is added; keys as elsewhere (rq_merge_keys_device).  Results are exact and never depend on the plan.
+ * Stream: the call behaves like a "pipeline" = 0 call.  It first completes whatever `stream` still defers (a fused tail, a
+ *   scanned-ahead pair, a hint), its results are complete in stream order, and it defers nothing.  It never touches the int8 image.
+ *   Not extended: rq_search_train_device, hints, "scan_ahead", "pipeline" 1 and 2; the MMR, range, grouped and member calls keep
+ *   their one filter per call.
+ * Refusals: every non-null entry gets the checks of rq_search_filtered: a filter of another index, or a stale filter, ANYWHERE in the
+ *   array refuses the whole call before anything is enqueued (RQ_EINVAL).  RQ_EUNSUPPORTED on a multi-device index.  RQ_EINVAL for
+ *   filters == NULL, B outside 1 .. 65535, k outside 1 .. RQ_MAX_K, an unknown metric, a null pointer; d_status is required in
+ *   the device forms.
+ * Status and repair: d_status[q] is 0 when query q is certified and 1 otherwise.  rq_search_fixup_filtered_each_device (the SAME
+ *   arguments) waits for the stream, reads the statuses, repairs every flagged query with the repair ladder of
+ *   rq_search_fixup_filtered_device under that query's OWN filter, patches the outputs in place and returns the number repaired.
+ *   rq_search_filtered_each: blocking, host buffers, staged on the index's own stream like rq_search_filtered, repair included.
+ * Plan (csrc/rq_filter_each_plan.h): the queries are grouped by filter pointer and every group is routed by the rule of
+ *   rq_search_filtered with its own number of queries.  The groups of the GATHER route together are the ragged set: the batch is
+ *   prepared once, one ragged gather launch re-scores each query's own allowed rows (the bits of the gather route) and one final
+ *   launch ranks them -- three launches whatever the number of filters; beyond 1 GiB of candidate keys the set is cut into rounds.
+ *   Groups of the SCAN and EXACT routes and the NULL entries run the existing call of their route, through pointer offsets when
+ *   their queries are one contiguous run of the batch and through a staging copy otherwise (arrange a batch by filter to avoid the
+ *   copy).  When more than 12 such filtered groups share 64 queries, ONE exact fp64 scan of the shard answers all of them, each query's keys
+ *   masked by its own bitmap (the shared exact route).  A batch whose entries are all the same filter is exactly the
+ *   rq_search_filtered_device call; a batch of NULL entries is the unfiltered search.
+ * Timing: rq_timing counts one search and B queries per call, not one per group.
+ * Memory: per stream, the staging of the largest scattered group (B_g x (4 dim + 20 k + 4) bytes) and the call's tables (about 64 bytes per
+ *   query) beside the workspace every search keeps.
+ * Options: "filter_route" forces the route of every group (1: every group with a row to return joins the ragged set; 2: one pass per
+ *   group; 3: all of them take the shared exact route); "filter_route_last" reports the last group's route (-1: it was a NULL entry);
+ *   "filter_repaired" counts the repairs of rq_search_fixup_filtered_each_device too.  Read-only: "filter_each_calls" (calls so
+ *   far), "filter_each_groups_last" (distinct filters of the last call, NULL counting as one), "filter_each_ragged_last" (queries the
+ *   ragged launches answered), "filter_each_rounds_last" (ragged rounds), "filter_each_shared_exact_last" (queries the shared exact
+ *   route answered), "filter_each_routes_last" (bit r set = some group took route r: 0 no row allowed, 1 gather, 2 scan, 3 exact,
+ *   4 a NULL entry).  Test hook "filter_each_key_cap": candidate keys per ragged round (0 = the default, 1 GiB / 8). */
+int rq_search_filtered_each_device(rq_index* idx, const rq_filter* const* filters, const float* d_queries, int B, int k, int metric,
+                                   float* d_scores, int64_t* d_rows, uint64_t* d_keys, int* d_status, void* stream);
+int rq_search_fixup_filtered_each_device(rq_index* idx, const rq_filter* const* filters, const float* d_queries, int B, int k, int metric,
+                                         float* d_scores, int64_t* d_rows, uint64_t* d_keys, int* d_status, void* stream);
+int rq_search_filtered_each(rq_index* idx, const rq_filter* const* filters, const float* queries, int B, int k, int metric,
+                            float* out_scores, int64_t* out_rows);
+
 /* ---- diversified search: MMR selection over candidate rows (what a max_marginal_relevance_search(query, k, fetch_k, lambda_mult)
  * does on the host with the fetch_k embeddings of the collection.query of reference rag_uq/streaming_index.py:355-359) ----------
  * Greedy maximal marginal relevance: k of m candidates per query, each step taking the candidate that is most relevant and least
