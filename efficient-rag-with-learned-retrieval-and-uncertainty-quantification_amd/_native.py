@@ -314,6 +314,25 @@ class NativeIndex:
             raise ValueError("row_filter must be an open RowFilter (NativeIndex.make_filter)")
         return row_filter._h
 
+    def _opt_filter(self, row_filter: Optional[RowFilter]) -> Optional[C.c_void_p]:
+        """The rq_filter argument of a call that takes one or NULL (no restriction)."""
+        return None if row_filter is None else self._filter_handle(row_filter)
+
+    # -- checks and outputs the calls below share --------------------------------------------------
+    @staticmethod
+    def _check_call(B: int, metric: int, *own: Tuple[bool, str]) -> None:
+        """B and metric as every call below takes them; `own`: (holds, what to say if not) for the call's own arguments, checked
+        between the two."""
+        for holds, message in ((1 <= int(B) <= 65535, f"B {B} outside 1..65535"), *own,
+                               (int(metric) in (METRIC_COSINE, METRIC_IP), f"unknown metric {metric!r}")):
+            if not holds:
+                raise ValueError(message)
+
+    @staticmethod
+    def _out(*shape: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores float32, rows int64) of a blocking call, for the library to fill"""
+        return np.empty(shape, dtype=np.float32), np.empty(shape, dtype=np.int64)
+
     # -- search -----------------------------------------------------------------------------
     def _as_queries(self, queries: np.ndarray) -> np.ndarray:
         """The queries of a host-buffer call as contiguous float32 [B][dim]; one query may come as a vector."""
@@ -327,8 +346,7 @@ class NativeIndex:
     def search(self, queries: np.ndarray, k: int, metric: int = METRIC_COSINE, *, row_filter: Optional[RowFilter] = None) -> Tuple[np.ndarray, np.ndarray]:
         q = self._as_queries(queries)
         B = q.shape[0]
-        scores = np.empty((B, int(k)), dtype=np.float32)
-        rows = np.empty((B, int(k)), dtype=np.int64)
+        scores, rows = self._out(B, int(k))
         if row_filter is not None:
             _check(self._lib.rq_search_filtered(self._h, self._filter_handle(row_filter), _ptr(q), B, int(k), int(metric), _ptr(scores), _ptr(rows)),
                    "rq_search_filtered")
@@ -370,8 +388,7 @@ class NativeIndex:
         q = self._as_queries(queries)
         B = q.shape[0]
         arr = self._filter_array(filters, B)
-        scores = np.empty((B, int(k)), dtype=np.float32)
-        rows = np.empty((B, int(k)), dtype=np.int64)
+        scores, rows = self._out(B, int(k))
         _check(self._lib.rq_search_filtered_each(self._h, arr, _ptr(q), B, int(k), int(metric), _ptr(scores), _ptr(rows)), "rq_search_filtered_each")
         return scores, rows
 
@@ -402,10 +419,9 @@ class NativeIndex:
         self._check_mmr(k, fetch_k, lambda_mult, "fetch_k")
         q = self._as_queries(queries)
         B = q.shape[0]
-        scores = np.empty((B, int(k)), dtype=np.float32)
-        rows = np.empty((B, int(k)), dtype=np.int64)
+        scores, rows = self._out(B, int(k))
         mmr = np.empty((B, int(k)), dtype=np.float32) if return_mmr else None
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         _check(self._lib.rq_search_mmr(self._h, flt, _ptr(q), B, int(k), int(fetch_k), float(lambda_mult), int(metric), _ptr(scores), _ptr(rows),
                                        _ptr(mmr)), "rq_search_mmr")
         return (scores, rows, mmr) if return_mmr else (scores, rows)
@@ -420,14 +436,9 @@ class NativeIndex:
                                               _ptr(d_scores), _ptr(d_rows), _ptr(d_mmr), C.c_void_p(stream)), "rq_mmr_select_device")
 
     # -- scoring given rows (include/rq.h "scoring given rows") ------------------------------------------
-    @staticmethod
-    def _check_score(B: int, m: int, metric: int) -> None:
-        if not 1 <= int(B) <= 65535:
-            raise ValueError(f"B {B} outside 1..65535")
-        if not 1 <= int(m) <= MAX_SCORE_ROWS:
-            raise ValueError(f"m {m} outside 1..{MAX_SCORE_ROWS}")
-        if int(metric) not in (METRIC_COSINE, METRIC_IP):
-            raise ValueError(f"unknown metric {metric!r}")
+    @classmethod
+    def _check_score(cls, B: int, m: int, metric: int) -> None:
+        cls._check_call(B, metric, (1 <= int(m) <= MAX_SCORE_ROWS, f"m {m} outside 1..{MAX_SCORE_ROWS}"))
 
     def score_rows(self, queries: np.ndarray, rows: np.ndarray, metric: int = METRIC_COSINE) -> np.ndarray:
         """The exact score of every (query, row) pair of one list of GLOBAL rows per query (include/rq.h rq_score_rows): float32
@@ -455,14 +466,9 @@ class NativeIndex:
                "rq_score_rows_device")
 
     # -- range searches (include/rq.h "range searches") ---------------------------------------------------
-    @staticmethod
-    def _check_range(B: int, cap: int, metric: int) -> None:
-        if not 1 <= int(B) <= 65535:
-            raise ValueError(f"B {B} outside 1..65535")
-        if not 1 <= int(cap) <= MAX_K:
-            raise ValueError(f"cap {cap} outside 1..{MAX_K}")
-        if int(metric) not in (METRIC_COSINE, METRIC_IP):
-            raise ValueError(f"unknown metric {metric!r}")
+    @classmethod
+    def _check_range(cls, B: int, cap: int, metric: int) -> None:
+        cls._check_call(B, metric, (1 <= int(cap) <= MAX_K, f"cap {cap} outside 1..{MAX_K}"))
 
     def search_range(self, queries: np.ndarray, threshold, cap: int, metric: int = METRIC_COSINE, *,
                      row_filter: Optional[RowFilter] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -480,10 +486,9 @@ class NativeIndex:
         if not np.isfinite(thr).all():
             raise ValueError("every threshold must be finite")
         thr = np.ascontiguousarray(thr)
-        scores = np.empty((B, int(cap)), dtype=np.float32)
-        rows = np.empty((B, int(cap)), dtype=np.int64)
+        scores, rows = self._out(B, int(cap))
         counts = np.empty(B, dtype=np.int64)
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         _check(self._lib.rq_search_range(self._h, flt, _ptr(q), B, _ptr(thr), int(cap), int(metric), _ptr(scores), _ptr(rows), _ptr(counts)),
                "rq_search_range")
         return scores, rows, counts
@@ -493,29 +498,22 @@ class NativeIndex:
         """Asynchronous form over device memory (include/rq.h rq_search_range_device): d_thr [B] fp32, d_count [B] int64, d_status [B]
         int32 (1 = repair that query with search_range_fixup_device); complete in stream order."""
         self._check_range(B, cap, metric)
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         _check(self._lib.rq_search_range_device(self._h, flt, _ptr(d_queries), int(B), _ptr(d_thr), int(cap), int(metric), _ptr(d_scores), _ptr(d_rows),
                                                 _ptr(d_keys), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)), "rq_search_range_device")
 
     def search_range_fixup_device(self, d_queries, B: int, d_thr, cap: int, metric: int, d_scores, d_rows, d_keys, d_count, d_status, stream: int = 0, *,
                                   row_filter: Optional[RowFilter] = None) -> int:
         self._check_range(B, cap, metric)
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         return _check(self._lib.rq_search_range_fixup_device(self._h, flt, _ptr(d_queries), int(B), _ptr(d_thr), int(cap), int(metric), _ptr(d_scores),
                                                              _ptr(d_rows), _ptr(d_keys), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)),
                       "rq_search_range_fixup_device")
 
     # -- grouped searches (include/rq.h "grouped searches") -----------------------------------------------
-    @staticmethod
-    def _check_grouped(B: int, k: int, m: int, metric: int, what: str = "m") -> None:
-        if not 1 <= int(B) <= 65535:
-            raise ValueError(f"B {B} outside 1..65535")
-        if not 1 <= int(m) <= MAX_K:
-            raise ValueError(f"{what} {m} outside 1..{MAX_K}")
-        if not 1 <= int(k) <= int(m):
-            raise ValueError(f"k {k} outside 1..{what} = {m}")
-        if int(metric) not in (METRIC_COSINE, METRIC_IP):
-            raise ValueError(f"unknown metric {metric!r}")
+    @classmethod
+    def _check_grouped(cls, B: int, k: int, m: int, metric: int, what: str = "m") -> None:
+        cls._check_call(B, metric, (1 <= int(m) <= MAX_K, f"{what} {m} outside 1..{MAX_K}"), (1 <= int(k) <= int(m), f"k {k} outside 1..{what} = {m}"))
 
     def set_groups(self, groups, row_begin: int = 0) -> None:
         """Group ids (int32; GROUP_NONE = -1: a group of its own) of the LOCAL rows [row_begin, row_begin + len(groups))
@@ -545,9 +543,8 @@ class NativeIndex:
         q = self._as_queries(queries)
         B = q.shape[0]
         self._check_grouped(B, k, MAX_K, metric, "MAX_K")
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
-        scores = np.empty((B, int(k)), dtype=np.float32)
-        rows = np.empty((B, int(k)), dtype=np.int64)
+        flt = self._opt_filter(row_filter)
+        scores, rows = self._out(B, int(k))
         groups = np.empty((B, int(k)), dtype=np.int32)
         _check(self._lib.rq_search_grouped(self._h, flt, _ptr(q), B, int(k), int(metric), _ptr(scores), _ptr(rows), _ptr(groups)), "rq_search_grouped")
         return scores, rows, groups
@@ -557,14 +554,14 @@ class NativeIndex:
         """Asynchronous form over device memory (include/rq.h rq_search_grouped_device): d_groups [B][k] int32, d_status [B] int32
         (1 = repair that query with search_grouped_fixup_device); complete in stream order."""
         self._check_grouped(B, k, MAX_K, metric, "MAX_K")
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         _check(self._lib.rq_search_grouped_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(metric), _ptr(d_scores), _ptr(d_rows), _ptr(d_groups),
                                                   _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)), "rq_search_grouped_device")
 
     def search_grouped_fixup_device(self, d_queries, B: int, k: int, metric: int, d_scores, d_rows, d_groups, d_keys, d_status, stream: int = 0, *,
                                     row_filter: Optional[RowFilter] = None) -> int:
         self._check_grouped(B, k, MAX_K, metric, "MAX_K")
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         return _check(self._lib.rq_search_grouped_fixup_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(metric), _ptr(d_scores), _ptr(d_rows),
                                                                _ptr(d_groups), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)),
                       "rq_search_grouped_fixup_device")
@@ -578,14 +575,10 @@ class NativeIndex:
                                                   _ptr(d_rows), _ptr(d_groups), _ptr(d_keys), _ptr(d_status), C.c_void_p(stream)), "rq_group_collapse_device")
 
     # -- group members (include/rq.h "group members") -----------------------------------------------------
-    @staticmethod
-    def _check_group_members(B: int, k: int, group_size: int, metric: int) -> None:
-        if not 1 <= int(B) <= 65535:
-            raise ValueError(f"B {B} outside 1..65535")
-        if int(k) < 1 or int(group_size) < 1 or int(k) * int(group_size) > MAX_K:
-            raise ValueError(f"k {k} x group_size {group_size} outside 1..{MAX_K}")
-        if int(metric) not in (METRIC_COSINE, METRIC_IP):
-            raise ValueError(f"unknown metric {metric!r}")
+    @classmethod
+    def _check_group_members(cls, B: int, k: int, group_size: int, metric: int) -> None:
+        fits = int(k) >= 1 and int(group_size) >= 1 and int(k) * int(group_size) <= MAX_K
+        cls._check_call(B, metric, (fits, f"k {k} x group_size {group_size} outside 1..{MAX_K}"))
 
     def search_group_members(self, queries: np.ndarray, k: int, group_size: int, metric: int = METRIC_COSINE, *, row_filter: Optional[RowFilter] = None
                              ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
@@ -595,10 +588,9 @@ class NativeIndex:
         q = self._as_queries(queries)
         B = q.shape[0]
         self._check_group_members(B, k, group_size, metric)
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         k, s = int(k), int(group_size)
-        scores = np.empty((B, k, s), dtype=np.float32)
-        rows = np.empty((B, k, s), dtype=np.int64)
+        scores, rows = self._out(B, k, s)
         groups = np.empty((B, k), dtype=np.int32)
         counts = np.empty((B, k), dtype=np.int32)
         _check(self._lib.rq_search_group_members(self._h, flt, _ptr(q), B, k, s, int(metric), _ptr(scores), _ptr(rows), _ptr(groups), _ptr(counts)),
@@ -610,7 +602,7 @@ class NativeIndex:
         """Asynchronous form over device memory (include/rq.h rq_search_group_members_device): d_scores / d_rows [B][k][s], d_groups /
         d_count [B][k] int32, d_status [B] int32 (1 = repair that query with search_group_members_fixup_device)."""
         self._check_group_members(B, k, group_size, metric)
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         _check(self._lib.rq_search_group_members_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(group_size), int(metric), _ptr(d_scores),
                                                         _ptr(d_rows), _ptr(d_groups), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)),
                "rq_search_group_members_device")
@@ -618,7 +610,7 @@ class NativeIndex:
     def search_group_members_fixup_device(self, d_queries, B: int, k: int, group_size: int, metric: int, d_scores, d_rows, d_groups, d_count, d_status,
                                           stream: int = 0, *, row_filter: Optional[RowFilter] = None) -> int:
         self._check_group_members(B, k, group_size, metric)
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         return _check(self._lib.rq_search_group_members_fixup_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(group_size), int(metric),
                                                                      _ptr(d_scores), _ptr(d_rows), _ptr(d_groups), _ptr(d_count), _ptr(d_status),
                                                                      C.c_void_p(stream)), "rq_search_group_members_fixup_device")
@@ -628,7 +620,7 @@ class NativeIndex:
         """Asynchronous fill over a caller's group slots (include/rq.h rq_group_fill_device): d_win_rows [B][k] int64 global rows,
         d_win_groups [B][k] int32 ids; the best `group_size` members of every slot's group."""
         self._check_group_members(B, k, group_size, metric)
-        flt = self._filter_handle(row_filter) if row_filter is not None else None
+        flt = self._opt_filter(row_filter)
         _check(self._lib.rq_group_fill_device(self._h, flt, _ptr(d_queries), int(B), int(k), int(group_size), int(metric), _ptr(d_win_rows),
                                               _ptr(d_win_groups), _ptr(d_scores), _ptr(d_rows), _ptr(d_count), _ptr(d_status), C.c_void_p(stream)),
                "rq_group_fill_device")

@@ -127,6 +127,12 @@ def _refuse_per_group(per_group: Optional[int], what: str) -> None:
         raise ValueError(f"{what} returns one passage per group: per_group={per_group!r} is not supported (use DenseIndex.search)")
 
 
+def _given(**keywords) -> Dict[str, Any]:
+    """Only the keywords that were given (not None): an index of someone else's, whose `search(query, top_k)` knows none of the
+    extensions, is never handed one its caller did not use."""
+    return {name: value for name, value in keywords.items() if value is not None}
+
+
 def _group_value(doc: "Document", key: str):
     """... of a Document: the metadata DenseIndex.add_documents stores for it, {"title": title, **metadata}."""
     return _meta_group_value({"title": doc.title or "", **(doc.metadata or {})}, key)
@@ -869,27 +875,99 @@ class DenseIndex:
             if gc_was_on:
                 gc.enable()
 
+    # ---- the parts every request below is put together from ----------------------------------------------------------------
+    # What a call needs of the index: (the method, whether an index over several devices is refused here too, the refusal).  Two
+    # idioms, kept apart on purpose.  The first four probe the method alone, and an index that does not exist yet is refused as well:
+    # an index over several devices has every method, and it is the library that refuses it.  Range and scoring also refuse
+    # several devices, and let a missing index pass (they answer "nothing" for it).  "device" refuses nobody: the host route answers.
+    _NEEDS = {
+        "filter": ("make_filter", False, "filtered searches need a single-device index that holds rows"),
+        "groups": ("set_groups", False, "grouped searches need a single-device index"),
+        "members": ("search_group_members", False, "grouped searches need a single-device index"),
+        "mmr": ("search_mmr", False, "MMR searches need a single-device index"),
+        "range": ("search_range", True, "search_threshold / count_above need a single-device index"),
+        "scoring": ("score_rows", True, "score_vectors / score_rows_batch / score_ids need a single-device index"),
+        "device": ("search_device", True, None),
+    }
+
+    def _can(self, what: str) -> bool:
+        method, one_device, _ = self._NEEDS[what]
+        return hasattr(self._index, method) and not (one_device and len(getattr(self._index, "devices", [0])) > 1)
+
+    def _require(self, what: str):
+        """The index, after refusing the call if the index cannot serve it (`_NEEDS`)."""
+        if not self._can(what) and not (self._index is None and self._NEEDS[what][1]):
+            raise _native.RqError(self._NEEDS[what][2])
+        return self._index
+
+    def _k(self, top_k, limit: int = _native.MAX_K) -> int:
+        """top_k as the k of a native call: no more than the index holds, nor than the library takes"""
+        return min(int(top_k), len(self._ids), limit)
+
+    def _nothing_to_search(self, top_k=1, n_queries: int = 1) -> bool:
+        return self._index is None or len(self._ids) == 0 or top_k <= 0 or n_queries == 0
+
+    @staticmethod
+    def _no_passages(n_queries: int) -> List[List[Tuple[str, float, str]]]:
+        return [[] for _ in range(n_queries)]
+
+    @staticmethod
+    def _no_rows(n_queries: int) -> Tuple[np.ndarray, np.ndarray]:
+        return np.zeros((n_queries, 0), np.float32), np.zeros((n_queries, 0), np.int64)
+
+    @staticmethod
+    def _query_matrix(vectors) -> np.ndarray:
+        """Query vectors as a float32 matrix [B][dim] (one query may come as a vector); a float32 matrix is passed through as it is."""
+        v = np.asarray(vectors, dtype=np.float32)
+        return v if v.ndim == 2 else np.atleast_2d(v)
+
+    def _check_dim(self, dim: int) -> None:
+        if dim != self.dim:
+            raise ValueError(f"query dimension {dim} does not match the index ({self.dim})")
+
+    def _embed_device(self, queries: Sequence[str]):
+        """The queries as a tensor in HBM -- from an embedder that can leave them there, for an index that holds rows -- or None:
+        the host path (`_embed_matrix`) then embeds them, after the reason was logged if the embedder failed."""
+        if not hasattr(self.embedder, "embed_device") or self._index is None or not len(self._ids):
+            return None
+        try:
+            return self.embedder.embed_device(list(queries))
+        except Exception as e:     # reference :281-284 semantics live in _embed_matrix (per-text retry, zero vector)
+            logger.error(f"Device embedding failed ({e}); falling back to the host path")
+            return None
+
     # ---- filtered searches (extension: the `where` of reference :355-359's collection.query) -------------------------
     def make_filter(self, ids) -> "_native.RowFilter":
         """A reusable filter that restricts searches to the passages with these ids (`allowed_ids=` accepts it as well as the ids
         themselves).  Unknown ids are ignored.  It describes the collection as it is now: adding documents makes it stale."""
-        if self._index is None or not hasattr(self._index, "make_filter"):
-            raise _native.RqError("filtered searches need a single-device index that holds rows")
+        index = self._require("filter")
         rows = [r for r in (self._row_of.get(d) for d in ids) if r is not None]
-        return self._index.make_filter(np.asarray(rows, dtype=np.int64))
+        return index.make_filter(np.asarray(rows, dtype=np.int64))
 
-    def _filtered_rows(self, vectors: np.ndarray, top_k: int, allowed_ids) -> Tuple[np.ndarray, np.ndarray]:
-        """(scores, rows) of the top_k over the allowed passages only: k = min(top_k, rows of the index); entries beyond the allowed
-        count are (0.0, -1).  Ids (rather than a `make_filter` result) cost a filter's whole set-up and tear-down per call: O(rows) on the
-        host, two device allocations, the masked scale, a device synchronisation -- reuse a filter for repeated questions."""
-        k = min(int(top_k), len(self._ids), _native.MAX_K)
-        own = not isinstance(allowed_ids, _native.RowFilter)
-        flt = self.make_filter(allowed_ids) if own else allowed_ids
+    def _with_filters(self, entries, call):
+        """`call(filters)` with every entry as the native calls take it: None (unrestricted) and a caller's own filter pass through
+        untouched; ids become a filter made now -- one per distinct OBJECT -- and closed once the call has returned or raised.  Ids
+        cost a filter's whole set-up and tear-down per call (O(rows) on the host, two device allocations, the masked scale, a device
+        synchronisation): reuse a `make_filter` result for repeated questions."""
+        made = {}
         try:
-            return self._index.search(vectors, k, self.metric, row_filter=flt)
+            filters = []
+            for e in entries:
+                if e is not None and not isinstance(e, _native.RowFilter):
+                    if id(e) not in made:
+                        made[id(e)] = self.make_filter(e)
+                    e = made[id(e)]
+                filters.append(e)
+            return call(filters)
         finally:
-            if own:
+            for flt in made.values():
                 flt.close()
+
+    def _with_filter(self, allowed_ids, call):
+        """`call(row_filter)` for one `allowed_ids`; free when there is no filter to make."""
+        if allowed_ids is None or isinstance(allowed_ids, _native.RowFilter):
+            return call(allowed_ids)
+        return self._with_filters([allowed_ids], lambda filters: call(filters[0]))
 
     @staticmethod
     def _each_entries(allowed_ids_each, n_queries: int, allowed_ids=None, distinct_by=None, per_group=None) -> list:
@@ -902,33 +980,12 @@ class DenseIndex:
             raise ValueError(f"allowed_ids_each needs one entry per query: {n_queries} queries, {len(entries)} entries")
         return entries
 
-    def _filtered_each_rows(self, vectors: np.ndarray, top_k: int, entries: list) -> Tuple[np.ndarray, np.ndarray]:
-        """(scores, rows) with query q ranked over the passages of entries[q] only, all queries in ONE native call (include/rq.h
-        "per-query filters").  Id lists become filters for the call and are closed afterwards; the same object given for several
-        queries becomes one filter."""
-        k = min(int(top_k), len(self._ids), _native.MAX_K)
-        made = {}
-        try:
-            filters = []
-            for e in entries:
-                if e is None or isinstance(e, _native.RowFilter):
-                    filters.append(e)
-                    continue
-                if id(e) not in made:
-                    made[id(e)] = self.make_filter(e)
-                filters.append(made[id(e)])
-            return self._index.search_filtered_each(vectors, k, filters, self.metric)
-        finally:
-            for flt in made.values():
-                flt.close()
-
     # ---- grouped searches (extension: `distinct_by=` -- one passage per value of a metadata field, e.g. "title": the best passage
     # of each of the top_k articles of a chunked corpus; include/rq.h "grouped searches") --------------------------------------
     def _push_groups(self, key: str) -> None:
         """Group ids of the rows the index has not been told about yet: metadata value -> id, assigned lazily in row order; a row
         whose metadata lacks `key`, or holds "", is a group of its own.  Another key than the last call's re-pushes every row."""
-        if self._index is None or not hasattr(self._index, "set_groups"):
-            raise _native.RqError("grouped searches need a single-device index")
+        index = self._require("groups")
         st = self.__dict__.get("_group_state")
         if st is None or st["key"] != key or st["pushed"] > len(self._ids):
             st = self.__dict__["_group_state"] = {"key": key, "ids": {}, "pushed": 0}
@@ -941,23 +998,8 @@ class DenseIndex:
             value = _meta_group_value(self._metas[j], key)
             if value is not None:
                 groups[j - first] = table.setdefault(value, len(table))
-        self._index.set_groups(groups, first)
+        index.set_groups(groups, first)
         st["pushed"] = n
-
-    def _grouped_rows(self, vectors: np.ndarray, top_k: int, distinct_by: str, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
-        """(scores, rows) of the best passage of each of the top_k groups, best group first; entries beyond the distinct groups among
-        the passages in play are (0.0, -1).  The queries take the host path."""
-        self._push_groups(distinct_by)
-        k = min(int(top_k), len(self._ids), _native.MAX_K)
-        if allowed_ids is None:
-            return self._index.search_grouped(vectors, k, self.metric)[:2]
-        own = not isinstance(allowed_ids, _native.RowFilter)
-        flt = self.make_filter(allowed_ids) if own else allowed_ids
-        try:
-            return self._index.search_grouped(vectors, k, self.metric, row_filter=flt)[:2]
-        finally:
-            if own:
-                flt.close()
 
     def _group_member_rows(self, vectors: np.ndarray, top_k: int, distinct_by: str, per_group: int, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
         """(scores, rows), each [B][k x per_group]: the best per_group passages of each of the top_k groups, group by group, members
@@ -965,42 +1007,49 @@ class DenseIndex:
         top_k is clamped so that k x per_group <= MAX_K."""
         if per_group > _native.MAX_K:
             raise ValueError(f"per_group {per_group} beyond {_native.MAX_K}")
-        if not hasattr(self._index, "search_group_members"):
-            raise _native.RqError("grouped searches need a single-device index")
+        index = self._require("members")
         self._push_groups(distinct_by)
-        k = min(int(top_k), len(self._ids), _native.MAX_K // per_group)
-        own = allowed_ids is not None and not isinstance(allowed_ids, _native.RowFilter)
-        flt = self.make_filter(allowed_ids) if own else allowed_ids
-        try:
-            scores, rows = self._index.search_group_members(vectors, k, per_group, self.metric, row_filter=flt)[:2]
-        finally:
-            if own:
-                flt.close()
+        k = self._k(top_k, _native.MAX_K // per_group)
+        scores, rows = self._with_filter(allowed_ids, lambda flt: index.search_group_members(vectors, k, per_group, self.metric, row_filter=flt)[:2])
         B = rows.shape[0]
         return scores.reshape(B, k * per_group), rows.reshape(B, k * per_group)
+
+    # ---- the one choice of route: every search that ranks passages ends here -------------------------------------------------
+    def _search_rows(self, vectors, top_k: int, allowed_ids=None, distinct_by: Optional[str] = None, per: int = 1, each: Optional[list] = None, *,
+                     on_device: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores float32, rows int64, (0.0, -1) padded) of one batch of query vectors by the first route that applies:
+          each         query q over the passages of each[q] only, all in ONE native call (include/rq.h "per-query filters")
+          per > 1      the best `per` passages of each of the top_k groups: [B][k x per] (`_group_member_rows`)
+          distinct_by  the best passage of each of the top_k groups, best group first
+          allowed_ids  the top_k of the allowed passages only
+          on_device    `vectors` is a tensor in HBM and is searched there (`_search_device_rows`); no restricted route takes one
+          otherwise    the plain search: host matrix in, k = min(top_k, rows of the index, MAX_K).
+        The caller has answered "nothing to search" and validated its keywords (`_per_group_size`, `_each_entries`)."""
+        index, metric = self._index, self.metric
+        if each is not None:
+            return self._with_filters(each, lambda filters: index.search_filtered_each(vectors, self._k(top_k), filters, metric))
+        if per > 1:
+            return self._group_member_rows(vectors, top_k, distinct_by, per, allowed_ids)
+        if distinct_by is not None:
+            self._push_groups(distinct_by)
+            return self._with_filter(allowed_ids, lambda flt: index.search_grouped(vectors, self._k(top_k), metric, row_filter=flt)[:2])
+        if allowed_ids is not None:
+            return self._with_filter(allowed_ids, lambda flt: index.search(vectors, self._k(top_k), metric, row_filter=flt))
+        if on_device:
+            return self._search_device_rows(vectors, top_k)
+        return index.search(vectors, self._k(top_k), metric)
 
     def search_vectors(self, vectors: np.ndarray, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
                        per_group: Optional[int] = None, allowed_ids_each=None) -> List[List[Tuple[str, float, str]]]:
         """`allowed_ids_each` (keyword-only): one entry per query -- a `make_filter` result, an iterable of ids, or None -- each
         query ranked over its own passages, the whole batch in one native call."""
         per = _per_group_size(distinct_by, per_group)
-        vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
+        vectors = self._query_matrix(vectors)
         each = None if allowed_ids_each is None else self._each_entries(allowed_ids_each, vectors.shape[0], allowed_ids, distinct_by, per_group)
-        if self._index is None or len(self._ids) == 0 or top_k <= 0:
-            return [[] for _ in range(vectors.shape[0])]
-        if vectors.shape[1] != self.dim:
-            raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
-        if each is not None:
-            return self._assemble(*self._filtered_each_rows(vectors, top_k, each))
-        if per > 1:   # (the best `per` passages of each of the top_k groups, group by group: up to top_k x per entries, no padding)
-            return self._assemble(*self._group_member_rows(vectors, top_k, distinct_by, per, allowed_ids))
-        if distinct_by is not None:
-            return self._assemble(*self._grouped_rows(vectors, top_k, distinct_by, allowed_ids))
-        if allowed_ids is not None:
-            return self._assemble(*self._filtered_rows(vectors, top_k, allowed_ids))
-        k = min(int(top_k), len(self._ids), _native.MAX_K)
-        scores, rows = self._index.search(vectors, k, self.metric)
-        return self._assemble(scores, rows)
+        if self._nothing_to_search(top_k):
+            return self._no_passages(vectors.shape[0])
+        self._check_dim(vectors.shape[1])
+        return self._assemble(*self._search_rows(vectors, top_k, allowed_ids, distinct_by, per, each))
 
     # ---- diversified searches (extension: what LangChain's max_marginal_relevance_search does on the host with the fetch_k
     # embeddings of reference :355-359's collection.query) -----------------------------------------------------------------
@@ -1009,27 +1058,16 @@ class DenseIndex:
         """`search_vectors` with the top_k chosen among the exact top fetch_k by greedy maximal marginal relevance (include/rq.h
         rq_search_mmr): (doc_id, score, text) in SELECTION order, the score still the cosine.  lambda_mult = 1 is the plain search,
         0 looks at diversity alone.  fetch_k is clamped to [top_k, min(len(self), MAX_K)].  The queries take the host path."""
-        vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
+        vectors = self._query_matrix(vectors)
         if not 0.0 <= float(lambda_mult) <= 1.0:
             raise ValueError(f"lambda_mult must lie within [0, 1], got {lambda_mult!r}")
-        if self._index is None or len(self._ids) == 0 or top_k <= 0:
-            return [[] for _ in range(vectors.shape[0])]
-        if vectors.shape[1] != self.dim:
-            raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
-        if not hasattr(self._index, "search_mmr"):
-            raise _native.RqError("MMR searches need a single-device index")
-        limit = min(len(self._ids), _native.MAX_K)
-        k = min(int(top_k), limit)
-        fetch = min(max(int(fetch_k), k), limit)
-        if allowed_ids is None:
-            return self._assemble(*self._index.search_mmr(vectors, k, fetch, float(lambda_mult), self.metric))
-        own = not isinstance(allowed_ids, _native.RowFilter)
-        flt = self.make_filter(allowed_ids) if own else allowed_ids
-        try:
-            return self._assemble(*self._index.search_mmr(vectors, k, fetch, float(lambda_mult), self.metric, row_filter=flt))
-        finally:
-            if own:
-                flt.close()
+        if self._nothing_to_search(top_k):
+            return self._no_passages(vectors.shape[0])
+        self._check_dim(vectors.shape[1])
+        index = self._require("mmr")
+        k = self._k(top_k)
+        fetch = self._k(max(int(fetch_k), k))
+        return self._assemble(*self._with_filter(allowed_ids, lambda flt: index.search_mmr(vectors, k, fetch, float(lambda_mult), self.metric, row_filter=flt)))
 
     def search_mmr_batch(self, queries: Sequence[str], top_k: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, *,
                          allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
@@ -1045,18 +1083,17 @@ class DenseIndex:
         """Queries that are already in HBM (a CUDA tensor [B][dim] fp32, e.g. `NomicBertEmbedder.embed_device`): searched where they
         are (rq_search_device on torch's current stream), repaired if a certificate failed, ONE device-to-host copy of rows + scores."""
         B = int(d_vectors.shape[0])
-        if self._index is None or len(self._ids) == 0 or top_k <= 0 or B == 0:
-            return [[] for _ in range(B)]
-        return self._assemble(*self._search_device_rows(d_vectors, top_k))
+        if self._nothing_to_search(top_k, B):
+            return self._no_passages(B)
+        return self._assemble(*self._search_rows(d_vectors, top_k, on_device=True))
 
     def _search_device_rows(self, d_vectors, top_k: int) -> Tuple[np.ndarray, np.ndarray]:
         """(scores float32 [B][k], rows int64 [B][k], -1 padded), k = min(top_k, rows of the index)"""
         import torch
         B = int(d_vectors.shape[0])
-        if int(d_vectors.shape[1]) != self.dim:
-            raise ValueError(f"query dimension {int(d_vectors.shape[1])} does not match the index ({self.dim})")
-        k = min(int(top_k), len(self._ids), _native.MAX_K)
-        if not hasattr(self._index, "search_device") or len(getattr(self._index, "devices", [0])) > 1:
+        self._check_dim(int(d_vectors.shape[1]))
+        k = self._k(top_k)
+        if not self._can("device"):
             return self._index.search(d_vectors.float().cpu().numpy(), k, self.metric)       # multi-device parent: host-buffer calls only
         dev = d_vectors.device
         q = d_vectors.to(torch.float32).contiguous()
@@ -1087,37 +1124,23 @@ class DenseIndex:
 
     # ---- range searches (extension: every passage at least this similar, and how many there are -- what a caller of reference
     # :355-359's collection.query gets by fetching n_results and cutting the list; include/rq.h rq_search_range) -----------------
-    def _range_index(self):
-        if self._index is not None and (not hasattr(self._index, "search_range") or len(getattr(self._index, "devices", [0])) > 1):
-            raise _native.RqError("search_threshold / count_above need a single-device index")
-        return self._index
-
     def _range_rows(self, vectors: np.ndarray, threshold, cap: int, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(scores [B][cap], rows [B][cap] -1 padded, counts [B]) of the passages scoring at least `threshold` (a scalar or one value
         per query) under this index's metric.  counts is exact also beyond cap."""
-        vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
+        vectors = self._query_matrix(vectors)
         B = vectors.shape[0]
         cap = max(1, min(int(cap), _native.MAX_K))
-        index = self._range_index()
-        if index is None or len(self._ids) == 0 or B == 0:
+        index = self._require("range")
+        if self._nothing_to_search(n_queries=B):
             return np.zeros((B, cap), np.float32), np.full((B, cap), -1, np.int64), np.zeros(B, np.int64)
-        if vectors.shape[1] != self.dim:
-            raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
-        if allowed_ids is None:
-            return index.search_range(vectors, threshold, cap, self.metric)
-        own = not isinstance(allowed_ids, _native.RowFilter)
-        flt = self.make_filter(allowed_ids) if own else allowed_ids
-        try:
-            return index.search_range(vectors, threshold, cap, self.metric, row_filter=flt)
-        finally:
-            if own:
-                flt.close()
+        self._check_dim(vectors.shape[1])
+        return self._with_filter(allowed_ids, lambda flt: index.search_range(vectors, threshold, cap, self.metric, row_filter=flt))
 
     def search_threshold_vectors(self, vectors: np.ndarray, threshold, max_results: int = 100, *, allowed_ids=None) -> List[List[Tuple[str, float, str]]]:
         """Per query vector the passages scoring at least `threshold`, best first, at most max_results (<= 1024) of them:
         [(doc_id, score, text)].  An empty list is the answer "nothing is similar enough"."""
-        if max_results <= 0 or self._range_index() is None or len(self._ids) == 0:
-            return [[] for _ in range(np.atleast_2d(np.asarray(vectors)).shape[0])]
+        if max_results <= 0 or self._require("range") is None or len(self._ids) == 0:
+            return self._no_passages(np.atleast_2d(np.asarray(vectors)).shape[0])
         scores, rows, _ = self._range_rows(vectors, threshold, max_results, allowed_ids)
         return self._assemble(scores, rows)
 
@@ -1136,25 +1159,27 @@ class DenseIndex:
 
     # ---- scoring given passages (extension: the dense score of a passage the dense search did not return; Chroma scores only what
     # its query returns, reference :355-359, so the reference's fusion writes 0.0 there, :498-499) -----------------------------------
-    def _scoring_index(self):
-        if self._index is not None and (not hasattr(self._index, "score_rows") or len(getattr(self._index, "devices", [0])) > 1):
-            raise _native.RqError("score_vectors / score_rows_batch / score_ids need a single-device index")
-        return self._index
+    def _nothing_to_score(self, n_rows: int) -> bool:
+        """... asked once an index that cannot score is refused (`_NEEDS`); the answer is then 0.0 for every row"""
+        return self._require("scoring") is None or len(self._ids) == 0 or n_rows == 0
+
+    @staticmethod
+    def _row_lists(rows, n_queries: int) -> np.ndarray:
+        rows = np.atleast_2d(np.asarray(rows, dtype=np.int64))
+        if rows.ndim != 2 or rows.shape[0] != n_queries:
+            raise ValueError(f"expected [{n_queries}][m] rows, one list per query, got {rows.shape}")
+        return rows
 
     def score_vectors(self, vectors: np.ndarray, rows) -> np.ndarray:
         """The exact score (this index's metric) of every given query vector against its own list of rows: vectors [B][dim], rows
         [B][m] (row r is `self._ids[r]`; -1 or any row the index does not hold scores 0.0) -> float32 [B][m], the values a search
         returns for those pairs (include/rq.h rq_score_rows)."""
-        vectors = np.atleast_2d(np.asarray(vectors, dtype=np.float32))
-        rows = np.atleast_2d(np.asarray(rows, dtype=np.int64))
-        if rows.ndim != 2 or rows.shape[0] != vectors.shape[0]:
-            raise ValueError(f"expected [{vectors.shape[0]}][m] rows, one list per query, got {rows.shape}")
-        index = self._scoring_index()
-        if index is None or len(self._ids) == 0 or rows.size == 0:
+        vectors = self._query_matrix(vectors)
+        rows = self._row_lists(rows, vectors.shape[0])
+        if self._nothing_to_score(rows.size):
             return np.zeros(rows.shape, np.float32)
-        if vectors.shape[1] != self.dim:
-            raise ValueError(f"query dimension {vectors.shape[1]} does not match the index ({self.dim})")
-        return index.score_rows(vectors, rows, self.metric)
+        self._check_dim(vectors.shape[1])
+        return self._index.score_rows(vectors, rows, self.metric)
 
     def _score_device_rows(self, d_vectors, rows: np.ndarray) -> np.ndarray:
         """`score_vectors` for queries that are already in HBM (rq_score_rows_device on torch's current stream)."""
@@ -1172,35 +1197,21 @@ class DenseIndex:
     def _embed_queries(self, queries: Sequence[str], *, host_only: bool = False):
         """The query vectors of one call, embedded ONCE: ("device", tensor in HBM) from an embedder that can leave them there and an
         index that searches them there, else ("host", float32 matrix).  What searched is what scores."""
-        single = self._index is not None and hasattr(self._index, "search_device") and len(getattr(self._index, "devices", [0])) == 1
-        if not host_only and single and len(self._ids) and hasattr(self.embedder, "embed_device"):
-            try:
-                d_q = self.embedder.embed_device(list(queries))
-            except Exception as e:
-                logger.error(f"Device embedding failed ({e}); falling back to the host path")
-                d_q = None
-            if d_q is not None:
-                return "device", d_q
-        return "host", self._embed_matrix(list(queries))
+        d_q = None if host_only or not self._can("device") else self._embed_device(queries)
+        return ("host", self._embed_matrix(list(queries))) if d_q is None else ("device", d_q)
 
     def _search_embedded(self, qv, top_k: int, allowed_ids=None) -> Tuple[np.ndarray, np.ndarray]:
         """`search_rows_batch` over vectors from `_embed_queries`."""
         kind, vecs = qv
         B = int(vecs.shape[0])
-        if self._index is None or len(self._ids) == 0 or top_k <= 0 or B == 0:
-            return np.zeros((B, 0), np.float32), np.zeros((B, 0), np.int64)
-        if allowed_ids is not None:
-            return self._filtered_rows(vecs, top_k, allowed_ids)
-        if kind == "device":
-            return self._search_device_rows(vecs, top_k)
-        k = min(int(top_k), len(self._ids), _native.MAX_K)
-        return self._index.search(vecs, k, self.metric)
+        if self._nothing_to_search(top_k, B):
+            return self._no_rows(B)
+        return self._search_rows(vecs, top_k, allowed_ids, on_device=kind == "device")
 
     def _score_embedded(self, qv, rows: np.ndarray) -> np.ndarray:
         kind, vecs = qv
         rows = np.asarray(rows, dtype=np.int64)
-        index = self._scoring_index()
-        if index is None or len(self._ids) == 0 or rows.size == 0 or not (rows >= 0).any():
+        if self._nothing_to_score(rows.size) or not (rows >= 0).any():
             return np.zeros(rows.shape, np.float32)
         if kind == "device":
             return self._score_device_rows(vecs, rows)
@@ -1209,11 +1220,8 @@ class DenseIndex:
     def score_rows_batch(self, queries: Sequence[str], rows) -> np.ndarray:
         """Embeds the query strings (once, where a search would embed them) and scores each against its own list of rows: float32
         [B][m], see `score_vectors`."""
-        rows = np.atleast_2d(np.asarray(rows, dtype=np.int64))
-        if rows.ndim != 2 or rows.shape[0] != len(queries):
-            raise ValueError(f"expected [{len(queries)}][m] rows, one list per query, got {rows.shape}")
-        self._scoring_index()
-        if self._index is None or len(self._ids) == 0 or rows.size == 0:
+        rows = self._row_lists(rows, len(queries))
+        if self._nothing_to_score(rows.size):
             return np.zeros(rows.shape, np.float32)
         return self._score_embedded(self._embed_queries(list(queries)), rows)
 
@@ -1222,8 +1230,7 @@ class DenseIndex:
         it ranked it.  An id the index does not hold scores 0.0 (the reference's value for "not scored"); an empty index returns
         zeros."""
         ids = list(ids)
-        self._scoring_index()
-        if self._index is None or len(self._ids) == 0 or not ids:
+        if self._nothing_to_score(len(ids)):
             return [0.0] * len(ids)
         rows = np.fromiter((self._row_of.get(d, -1) for d in ids), np.int64, len(ids))[None, :]
         return self.score_rows_batch([query], rows)[0].astype(np.float64).tolist()
@@ -1237,52 +1244,30 @@ class DenseIndex:
         _refuse_per_group(per_group, "search_rows_batch")
         B = len(queries)
         each = None if allowed_ids_each is None else self._each_entries(allowed_ids_each, B, allowed_ids, distinct_by, per_group)
-        if self._index is None or len(self._ids) == 0 or top_k <= 0 or B == 0:
-            return np.zeros((B, 0), np.float32), np.zeros((B, 0), np.int64)
-        if each is not None:
-            return self._filtered_each_rows(self._embed_matrix(list(queries)), top_k, each)
-        if distinct_by is not None:   # (one passage per value of that metadata field: `_grouped_rows`)
-            return self._grouped_rows(self._embed_matrix(list(queries)), top_k, distinct_by, allowed_ids)
-        if allowed_ids is not None:
-            return self._filtered_rows(self._embed_matrix(list(queries)), top_k, allowed_ids)
-        if hasattr(self.embedder, "embed_device"):
-            try:
-                d_q = self.embedder.embed_device(list(queries))
-            except Exception as e:
-                logger.error(f"Device embedding failed ({e}); falling back to the host path")
-                d_q = None
-            if d_q is not None:
-                return self._search_device_rows(d_q, top_k)
-        k = min(int(top_k), len(self._ids), _native.MAX_K)
-        return self._index.search(self._embed_matrix(list(queries)), k, self.metric)
+        if self._nothing_to_search(top_k, B):
+            return self._no_rows(B)
+        restricted = each is not None or distinct_by is not None or allowed_ids is not None      # (these queries take the host path)
+        d_q = None if restricted else self._embed_device(queries)
+        if d_q is not None:
+            return self._search_rows(d_q, top_k, on_device=True)
+        return self._search_rows(self._embed_matrix(list(queries)), top_k, allowed_ids, distinct_by, 1, each)
 
     def search_batch(self, queries: Sequence[str], top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
                      per_group: Optional[int] = None, allowed_ids_each=None) -> List[List[Tuple[str, float, str]]]:
         """`allowed_ids_each` (keyword-only): one allowed set per query -- a batch of questions from different tenants, sources or
         users in one native call; see `search_vectors`."""
         per = _per_group_size(distinct_by, per_group)
-        if allowed_ids_each is not None:   # (checked by search_vectors; the queries take the host path)
-            return self.search_vectors(self._embed_matrix(list(queries)) if queries else np.zeros((0, self.dim), np.float32), top_k,
-                                       allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per_group, allowed_ids_each=allowed_ids_each)
-        if not queries:
+        if not queries and allowed_ids_each is None:
             return []
-        if per > 1:
-            return self.search_vectors(self._embed_matrix(list(queries)), top_k, allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per)
-        if distinct_by is not None:   # (the device-embedder route is not extended: the queries take the host path)
-            return self.search_vectors(self._embed_matrix(list(queries)), top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)
-        if allowed_ids is not None:   # (ids or a `make_filter` result: only those passages are ranked)
-            return self.search_vectors(self._embed_matrix(list(queries)), top_k, allowed_ids=allowed_ids)
-        # an embedder that can leave its output in HBM (embedders.NomicBertEmbedder.embed_device) feeds the search directly: no
-        # device -> host -> numpy -> pinned -> device round trip of the query matrix
-        if hasattr(self.embedder, "embed_device") and self._index is not None and len(self._ids):
-            try:
-                d_q = self.embedder.embed_device(list(queries))
-            except Exception as e:     # reference :281-284 semantics live in _embed_matrix (per-text retry, zero vector)
-                logger.error(f"Device embedding failed ({e}); falling back to the host path")
-                d_q = None
-            if d_q is not None:
-                return self.search_device_vectors(d_q, top_k)
-        return self.search_vectors(self._embed_matrix(list(queries)), top_k)
+        # an embedder that can leave its output in HBM (embedders.NomicBertEmbedder.embed_device) feeds the unrestricted search
+        # directly: no device -> host -> numpy -> pinned -> device round trip of the query matrix.  Every restricted search
+        # takes the host path.
+        restricted = allowed_ids_each is not None or per > 1 or distinct_by is not None or allowed_ids is not None
+        d_q = None if restricted else self._embed_device(queries)
+        if d_q is not None:
+            return self.search_device_vectors(d_q, top_k)
+        vectors = self._embed_matrix(list(queries)) if queries else np.zeros((0, self.dim), np.float32)      # (none: `allowed_ids_each` is still checked)
+        return self.search_vectors(vectors, top_k, allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per_group, allowed_ids_each=allowed_ids_each)
 
     def search(self, query: str, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None,
                per_group: Optional[int] = None) -> List[Tuple[str, float, str]]:
@@ -1292,13 +1277,8 @@ class DenseIndex:
         passage of each of the top_k groups; a passage without the field is a group of its own.  It combines with `allowed_ids`.
         `per_group` (with `distinct_by`; default 1): the best per_group passages of each of the top_k groups, group by group, members
         best first -- up to top_k x per_group entries."""
-        if _per_group_size(distinct_by, per_group) > 1:
-            return self.search_batch([query], top_k, allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per_group)[0]
-        if distinct_by is not None:
-            return self.search_batch([query], top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)[0]
-        if allowed_ids is not None:
-            return self.search_batch([query], top_k, allowed_ids=allowed_ids)[0]
-        return self.search_batch([query], top_k)[0]
+        per = _per_group_size(distinct_by, per_group)
+        return self.search_batch([query], top_k, **_given(allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per_group if per > 1 else None))[0]
 
     def __len__(self) -> int:
         return len(self._ids)
@@ -1405,23 +1385,14 @@ class HybridRetriever:
         _refuse_per_group(per_group, "bm25_search")
         if self.bm25_index is None:
             return []
-        if distinct_by is not None:
-            return self.bm25_index.search(query, top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)
-        if allowed_ids is not None:
-            return self.bm25_index.search(query, top_k, allowed_ids=allowed_ids)
-        return self.bm25_index.search(query, top_k)
+        return self.bm25_index.search(query, top_k, **_given(allowed_ids=allowed_ids, distinct_by=distinct_by))
 
     def dense_search(self, query: str, top_k: int = 20, *, allowed_ids=None, distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[Tuple[str, float]]:
         per = _per_group_size(distinct_by, per_group)
         if self.dense_index is None:
             return []
-        if per > 1:   # (the best `per` passages of each of the top_k groups: DenseIndex.search)
-            return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per)]
-        if distinct_by is not None:
-            return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids, distinct_by=distinct_by)]
-        if allowed_ids is not None:
-            return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, allowed_ids=allowed_ids)]
-        return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k)]
+        given = _given(allowed_ids=allowed_ids, distinct_by=distinct_by, per_group=per if per > 1 else None)   # (per > 1: the best `per` passages of each group)
+        return [(doc_id, score) for doc_id, score, _ in self.dense_index.search(query, top_k, **given)]
 
     def dense_search_mmr(self, query: str, top_k: int = 20, fetch_k: int = 50, lambda_mult: float = 0.5, *, allowed_ids=None) -> List[Tuple[str, float]]:
         """`dense_search` diversified: top_k of the exact top fetch_k by maximal marginal relevance, in selection order (DenseIndex.search_mmr)."""
@@ -1500,7 +1471,7 @@ class HybridRetriever:
         The query is embedded once: the vector that searched is the vector that scores."""
         if allowed_ids is not None:
             allowed_ids = list(allowed_ids)
-        bm25_list = self.bm25_search(query, retrieval_pool_size, allowed_ids=allowed_ids) if allowed_ids is not None else self.bm25_search(query, retrieval_pool_size)
+        bm25_list = self.bm25_search(query, retrieval_pool_size, **_given(allowed_ids=allowed_ids))
         dn, bm = self.dense_index, self.bm25_index
         dense_list: List[Tuple[str, float]] = []
         qv = None
@@ -1537,11 +1508,8 @@ class HybridRetriever:
         if complete_scores:
             bm25_list, dense_list, extra = self._pools_completed(query, retrieval_pool_size, allowed_ids)
             return self._fuse(bm25_list, dense_list, top_k, extra)
-        if allowed_ids is not None:
-            allowed_ids = list(allowed_ids)      # (walked twice)
-            return self._fuse(self.bm25_search(query, retrieval_pool_size, allowed_ids=allowed_ids),
-                              self.dense_search(query, retrieval_pool_size, allowed_ids=allowed_ids), top_k)
-        return self._fuse(self.bm25_search(query, retrieval_pool_size), self.dense_search(query, retrieval_pool_size), top_k)
+        given = _given(allowed_ids=None if allowed_ids is None else list(allowed_ids))      # (walked twice)
+        return self._fuse(self.bm25_search(query, retrieval_pool_size, **given), self.dense_search(query, retrieval_pool_size, **given), top_k)
 
     def hybrid_search_batch(self, queries: Sequence[str], top_k: int = 10, retrieval_pool_size: int = 50, *, complete_scores: bool = False
                             ) -> List[List[RetrievalResult]]:
@@ -1594,13 +1562,8 @@ class HybridRetriever:
         """Reference :525-557 (its pools are always 50, :537); `retrieval_pool_size` is a keyword-only extension for
         BASELINE.json configs[4] (top-100 pools), `allowed_ids` restricts both pools to those passages, `complete_scores` fills in the
         score a passage did not get from the other retriever (see `_pools_completed`)."""
-        if complete_scores:
-            return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size, allowed_ids=allowed_ids,
-                                                          complete_scores=True), num_passages)
-        if allowed_ids is not None:
-            return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size, allowed_ids=allowed_ids),
-                                       num_passages)
-        return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size), num_passages)
+        given = _given(allowed_ids=allowed_ids, complete_scores=True if complete_scores else None)
+        return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size, **given), num_passages)
 
     def get_scores_for_router_batch(self, queries: Sequence[str], num_passages: int = 20, *, retrieval_pool_size: int = 50, complete_scores: bool = False):
         """`[get_scores_for_router(q, ...) for q in queries]` (without `allowed_ids`: the batch fusions are not extended) with the pools of the whole batch computed at once.  When both sides are
