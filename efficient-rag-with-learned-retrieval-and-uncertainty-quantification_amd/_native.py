@@ -102,6 +102,13 @@ _SIGNATURES = {
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_search_group_members": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "rq_sparse_create": (C.c_void_p, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "rq_sparse_destroy": (None, [C.c_void_p]),
+    "rq_sparse_postings": (C.c_int64, [C.c_void_p]),
+    "rq_sparse_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rq_sparse_topk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_sparse_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "rq_sparse_get_option": (C.c_double, [C.c_void_p, C.c_char_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int]),
     "rq_nb_rope_table_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
@@ -707,6 +714,74 @@ class NativeIndex:
         if not h:
             raise RqError(f"rq_load({path}): {last_error()}")
         return cls(0, devs[0], _handle=h, devices=devs)
+
+
+# -- sparse search on the device (include/rq.h "sparse search", csrc/rq_sparse.hip) ----------------------------------------------------
+SPARSE_MAX_K = 1024
+
+
+class SparseIndex:
+    """Owner of one rq_sparse handle: a posting index (CSR arrays, COPIED to the device: 12 B per posting + 8 B per token) and the exact
+    BM25 top-k over it -- the rows and score bits of `bm25_topk`.  No host fallback: without the library or a gfx950 device the
+    constructor raises."""
+
+    def __init__(self, indptr: np.ndarray, rows: np.ndarray, contrib: np.ndarray, n_tokens: int, n_docs: int, device: int = 0):
+        self._lib = load_library()
+        indptr = np.ascontiguousarray(indptr, np.int64)
+        rows = np.ascontiguousarray(rows, np.int32)
+        contrib = np.ascontiguousarray(contrib, np.float64)
+        if len(indptr) != int(n_tokens) + 1:
+            raise RqError(f"rq_sparse_create: indptr holds {len(indptr)} entries for {n_tokens} tokens")
+        if len(indptr) and (len(rows) < int(indptr[-1]) or len(contrib) < int(indptr[-1])):
+            raise RqError(f"rq_sparse_create: indptr names {int(indptr[-1])} postings, rows / contrib hold {len(rows)} / {len(contrib)}")
+        h = self._lib.rq_sparse_create(int(device), _ptr(indptr), _ptr(rows), _ptr(contrib), int(n_tokens), int(n_docs))
+        if not h:
+            raise RqError(f"rq_sparse_create: {last_error()}")
+        self._h = C.c_void_p(h)
+        self.n_tokens, self.n_docs, self.device = int(n_tokens), int(n_docs), int(device)
+        self.postings = int(self._lib.rq_sparse_postings(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.rq_sparse_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def topk(self, q_indptr, q_tokens, B: int, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocking, host arrays: (rows int32 [B][k], -1 padded; scores float64 [B][k], 0.0 padded)."""
+        q_indptr = np.ascontiguousarray(q_indptr, np.int64)
+        q_tokens = np.ascontiguousarray(q_tokens, np.int32)
+        if len(q_indptr) != int(B) + 1 or (int(B) >= 1 and len(q_tokens) < int(q_indptr[-1])):
+            raise RqError(f"rq_sparse_topk: q_indptr holds {len(q_indptr)} entries for {B} queries, or names more tokens than q_tokens holds")
+        out_rows = np.empty((max(int(B), 0), max(int(k), 0)), np.int32)
+        out_scores = np.empty((max(int(B), 0), max(int(k), 0)), np.float64)
+        _check(self._lib.rq_sparse_topk(self._h, _ptr(q_indptr), _ptr(q_tokens) if len(q_tokens) else None, int(B), int(k),
+                                        _ptr(out_rows), _ptr(out_scores)), "rq_sparse_topk")
+        return out_rows, out_scores
+
+    def topk_device(self, d_q_indptr, d_q_tokens, B: int, n_q_tokens: int, k: int, d_rows, d_scores, stream: int = 0) -> None:
+        """Asynchronous, device pointers (torch tensors or raw addresses): int64 [B + 1], int32 [n_q_tokens] -> int32 [B][k], float64 [B][k]."""
+        _check(self._lib.rq_sparse_topk_device(self._h, _ptr(d_q_indptr), _ptr(d_q_tokens), int(B), int(n_q_tokens), int(k), _ptr(d_rows),
+                                               _ptr(d_scores), C.c_void_p(stream)), "rq_sparse_topk_device")
+
+    def set_option(self, name: str, value: float) -> None:
+        _check(self._lib.rq_sparse_set_option(self._h, name.encode(), float(value)), f"rq_sparse_set_option({name})")
+
+    def get_option(self, name: str) -> float:
+        return float(self._lib.rq_sparse_get_option(self._h, name.encode()))
+
+
+def sparse_available() -> bool:
+    """librq_hip.so is built and a device is visible (SparseIndex may still refuse a device that is not a gfx950)."""
+    try:
+        return device_count() > 0
+    except (RqError, OSError):
+        return False
 
 
 # -- encoder pieces (include/rq.h "encoder pieces", csrc/rq_encoder.hip): torch tensors or raw device addresses -------------

@@ -1,0 +1,410 @@
+// rq_sparse.hip -- sparse search on the device (include/rq.h rq_sparse_*): exact BM25 top-k over a device-resident posting index,
+// the definition of rq_bm25_topk (include/rq_bm25.h) with the same rows and the same score bits.
+//
+// rq_sparse_tile_kernel, grid (tiles, queries): a workgroup owns tile_docs consecutive documents and one float64 accumulator per
+// document in LDS.  For the query's tokens IN QUERY ORDER it finds the token's postings inside the tile (two binary searches over the
+// token's ascending rows, a chunk of 256 tokens at a time, one thread each) and adds their contributions.
+//   Bit exactness: a token names a row at most once, so within one token every accumulator is touched by at most one thread, once --
+//   no race, no atomic; the barrier after every token keeps the additions to one accumulator in query order.  Every score is thus
+//   0.0 + c_1 + c_2 + ... in float64 (no contraction: -ffp-contract=off, and there is nothing to contract), the very additions of the
+//   host library.
+// A tile in which no token has a posting leaves before it zeroes anything.  Otherwise the tile's best min(k, positives) are cut out
+// exactly (rq_sparse_select.h) and written, in any order, to the tile's slot of the workspace with their count.
+// rq_sparse_final_kernel, one workgroup per query: the best k of the tiles' candidates by the same selection body, sorted best first
+// with ties by descending row (the keys are unique: the result does not depend on the order of the slots), then the padding.
+#include "rq_sparse_plan.h"
+#include "rq_sparse_select.h"
+#include "rq_stage.h"
+
+struct SparseArgs {
+    const int64_t* indptr;      // [n_tokens + 1]
+    const int32_t* rows;        // [nnz]
+    const double* contrib;      // [nnz]
+    int64_t n_tokens, n_docs, tiles;
+    const int64_t* q_indptr;    // [B + 1] of the whole call
+    const int32_t* q_tokens;    // [n_q_tokens]
+    int64_t n_q_tokens;
+    int q0;                     // first query of the round
+    int k, slot, tile_docs;
+    uint64_t* cand_bits;        // [queries of the round][tiles][slot]
+    int32_t* cand_rows;
+    int32_t* counts;            // [queries of the round][tiles]
+    unsigned long long* skipped;
+    int32_t* out_rows;          // [B][k] of the whole call
+    double* out_scores;
+};
+
+// first position in [b, e) whose row is >= v (rows ascending)
+__device__ __forceinline__ int64_t sparse_lower_bound(const int32_t* rows, int64_t b, int64_t e, int64_t v) {
+    while (b < e) {
+        const int64_t m = b + ((e - b) >> 1);
+        if ((int64_t)rows[m] < v) b = m + 1;
+        else e = m;
+    }
+    return b;
+}
+
+// the accumulator of a tile as candidates: position i = document tile_lo + i, a candidate when its score is positive
+struct SparseTileSrc {
+    const double* acc;
+    int n;
+    uint32_t row0;
+    __device__ __forceinline__ int64_t size() const { return n; }
+    __device__ __forceinline__ bool get(int64_t i, uint64_t& hi, uint32_t& lo) const {
+        const double v = acc[i];
+        hi = (uint64_t)__double_as_longlong(v);
+        lo = row0 + (uint32_t)i;
+        return v > 0.0;   // false for NaN, a negative total, an exact cancellation
+    }
+};
+
+__global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_tile_kernel(SparseArgs a) {
+    extern __shared__ double s_acc[];   // [tile_docs]
+    __shared__ int64_t s_lo[RQ_SPARSE_CHUNK], s_hi[RQ_SPARSE_CHUNK];
+    __shared__ SparseSelShared s_sel;
+    __shared__ unsigned s_n;
+    const int tid = (int)threadIdx.x;
+    const int64_t tile = blockIdx.x;
+    const int ql = (int)blockIdx.y;
+    const int64_t tile_lo = tile * (int64_t)a.tile_docs;
+    const int64_t tile_hi = tile_lo + a.tile_docs < a.n_docs ? tile_lo + a.tile_docs : a.n_docs;
+    const int nloc = (int)(tile_hi - tile_lo);
+    // the query's tokens; the arrays may be the caller's device memory, which no host check has seen: stay inside [0, n_q_tokens)
+    int64_t t0 = a.q_indptr[a.q0 + ql], t1 = a.q_indptr[a.q0 + ql + 1];
+    t0 = t0 < 0 ? 0 : (t0 > a.n_q_tokens ? a.n_q_tokens : t0);
+    t1 = t1 < t0 ? t0 : (t1 > a.n_q_tokens ? a.n_q_tokens : t1);
+    bool zeroed = false;
+    for (int64_t c = t0; c < t1; c += RQ_SPARSE_CHUNK) {
+        const int nch = (int)(t1 - c < RQ_SPARSE_CHUNK ? t1 - c : RQ_SPARSE_CHUNK);
+        int64_t lo = 0, hi = 0;
+        if (tid < nch) {
+            const int64_t tok = a.q_tokens[c + tid];
+            if (tok >= 0 && tok < a.n_tokens) {   // an id outside the index is an empty posting list
+                const int64_t b = a.indptr[tok], e = a.indptr[tok + 1];
+                lo = sparse_lower_bound(a.rows, b, e, tile_lo);
+                // rows ascend strictly: rows[lo + j] >= tile_lo + j, so the tile's postings end within nloc positions of lo
+                hi = sparse_lower_bound(a.rows, lo, e - lo > nloc ? lo + nloc : e, tile_hi);
+            }
+        }
+        s_lo[tid] = lo;
+        s_hi[tid] = hi;
+        if (!__syncthreads_or(hi > lo)) continue;   // (nobody reads s_lo / s_hi of this chunk)
+        if (!zeroed) {
+            for (int i = tid; i < nloc; i += RQ_SPARSE_THREADS) s_acc[i] = 0.0;
+            zeroed = true;
+            __syncthreads();
+        }
+        for (int j = 0; j < nch; ++j) {
+            const int64_t pl = s_lo[j], ph = s_hi[j];
+            if (ph <= pl) continue;
+            for (int64_t p = pl + tid; p < ph; p += RQ_SPARSE_THREADS) s_acc[(int64_t)a.rows[p] - tile_lo] += a.contrib[p];
+            __syncthreads();   // the next token's additions come after this token's: query order
+        }
+        __syncthreads();       // s_lo / s_hi are free for the next chunk
+    }
+    int32_t* count = a.counts + (size_t)ql * (size_t)a.tiles + (size_t)tile;
+    if (!zeroed) {             // no token of the query has a posting in this tile
+        if (tid == 0) {
+            *count = 0;
+            atomicAdd(a.skipped, 1ull);
+        }
+        return;
+    }
+    const SparseTileSrc src{s_acc, nloc, (uint32_t)tile_lo};
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    unsigned mine = 0;
+    for (int i = tid; i < nloc; i += RQ_SPARSE_THREADS) mine += s_acc[i] > 0.0 ? 1u : 0u;
+    if (mine) atomicAdd(&s_n, mine);
+    __syncthreads();
+    const unsigned positives = s_n;
+    const unsigned want = positives < (unsigned)a.k ? positives : (unsigned)a.k;   // <= slot = min(k, tile_docs)
+    __syncthreads();
+    if (tid == 0) { *count = (int32_t)want; s_n = 0; }
+    uint64_t thr_hi = 0;
+    uint32_t thr_lo = 0;
+    if (positives > want) sparse_select_threshold(src, want, s_sel, thr_hi, thr_lo);
+    __syncthreads();
+    const size_t base = ((size_t)ql * (size_t)a.tiles + (size_t)tile) * (size_t)a.slot;
+    for (int i = tid; i < nloc; i += RQ_SPARSE_THREADS) {
+        uint64_t hi;
+        uint32_t lo;
+        if (!src.get(i, hi, lo) || !sparse_key_ge(hi, lo, thr_hi, thr_lo)) continue;
+        const unsigned j = atomicAdd(&s_n, 1u);
+        if (j < (unsigned)a.slot) {
+            a.cand_bits[base + j] = hi;
+            a.cand_rows[base + j] = (int32_t)lo;
+        }
+    }
+}
+
+// the candidates of one query in the workspace: position i = entry i % slot of tile i / slot, a candidate below the tile's count
+struct SparseFinalSrc {
+    const uint64_t* bits;
+    const int32_t* rows;
+    const int32_t* counts;
+    int64_t n;
+    int slot;
+    __device__ __forceinline__ int64_t size() const { return n; }
+    __device__ __forceinline__ bool get(int64_t i, uint64_t& hi, uint32_t& lo) const {
+        const int64_t t = i / slot;
+        if ((int)(i - t * slot) >= counts[t]) return false;
+        hi = bits[i];
+        lo = (uint32_t)rows[i];
+        return true;
+    }
+};
+
+__global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_final_kernel(SparseArgs a) {
+    __shared__ uint64_t s_bits[RQ_SPARSE_MAX_K];
+    __shared__ int32_t s_rows[RQ_SPARSE_MAX_K];
+    __shared__ SparseSelShared s_sel;
+    __shared__ unsigned s_n;
+    const int tid = (int)threadIdx.x;
+    const int ql = (int)blockIdx.x;
+    const size_t qt = (size_t)ql * (size_t)a.tiles;
+    const int32_t* counts = a.counts + qt;
+    const SparseFinalSrc src{a.cand_bits + qt * (size_t)a.slot, a.cand_rows + qt * (size_t)a.slot, counts, a.tiles * (int64_t)a.slot, a.slot};
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    unsigned mine = 0;
+    for (int64_t t = tid; t < a.tiles; t += RQ_SPARSE_THREADS) mine += (unsigned)counts[t];
+    if (mine) atomicAdd(&s_n, mine);
+    __syncthreads();
+    const unsigned total = s_n;   // <= the query's positive documents < 2^31
+    const unsigned want = total < (unsigned)a.k ? total : (unsigned)a.k;
+    __syncthreads();
+    if (tid == 0) s_n = 0;
+    uint64_t thr_hi = 0;
+    uint32_t thr_lo = 0;
+    if (total > want) sparse_select_threshold(src, want, s_sel, thr_hi, thr_lo);
+    __syncthreads();
+    if (want > 0)
+        for (int64_t i = tid; i < src.n; i += RQ_SPARSE_THREADS) {
+            uint64_t hi;
+            uint32_t lo;
+            if (!src.get(i, hi, lo) || !sparse_key_ge(hi, lo, thr_hi, thr_lo)) continue;
+            const unsigned j = atomicAdd(&s_n, 1u);
+            if (j < RQ_SPARSE_MAX_K) { s_bits[j] = hi; s_rows[j] = (int32_t)lo; }
+        }
+    unsigned P = 1;
+    while (P < want) P <<= 1;
+    __syncthreads();
+    for (unsigned i = want + tid; i < P; i += RQ_SPARSE_THREADS) { s_bits[i] = 0; s_rows[i] = -1; }   // below every candidate
+    __syncthreads();
+    // bitonic sort of P (a power of two) keys, best first: larger score bits, then larger row
+    for (unsigned size = 2; size <= P; size <<= 1)
+        for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
+            for (unsigned t = tid; t < P / 2; t += RQ_SPARSE_THREADS) {
+                const unsigned i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const uint64_t bi = s_bits[i], bj = s_bits[j];
+                const int32_t ri = s_rows[i], rj = s_rows[j];
+                const bool j_first = bj > bi || (bj == bi && rj > ri);
+                if (((i & size) == 0) == j_first) { s_bits[i] = bj; s_bits[j] = bi; s_rows[i] = rj; s_rows[j] = ri; }
+            }
+            __syncthreads();
+        }
+    int32_t* orow = a.out_rows + (size_t)(a.q0 + ql) * (size_t)a.k;
+    double* osc = a.out_scores + (size_t)(a.q0 + ql) * (size_t)a.k;
+    for (unsigned i = tid; i < (unsigned)a.k; i += RQ_SPARSE_THREADS) {
+        orow[i] = i < want ? s_rows[i] : -1;
+        osc[i] = i < want ? __longlong_as_double((long long)s_bits[i]) : 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct rq_sparse {
+    int device = 0;
+    int64_t n_tokens = 0, n_docs = 0, nnz = 0;
+    int64_t* d_indptr = nullptr;
+    int32_t* d_rows = nullptr;
+    double* d_contrib = nullptr;
+    hipStream_t own = nullptr;
+    char* ws = nullptr;                   // the one workspace (rq_sparse_plan.h SparsePlan)
+    size_t ws_bytes = 0;
+    unsigned long long* d_skipped = nullptr;
+    int tile_docs = RQ_SPARSE_TILE_DEFAULT;
+    int64_t cand_cap = 0;
+    int64_t calls = 0, rounds_last = 0, tiles_last = 0;
+    // option "profile": HIP events before a call's first launch and after every launch; "tile_ms_last" / "final_ms_last" sum them
+    int profile = 0;
+    std::vector<hipEvent_t> ev;
+    size_t ev_used = 0;           // events the last profiled call recorded: 1 + 2 x rounds (0: none)
+};
+
+static void sparse_free(rq_sparse* h) {
+    if (h->own) (void)hipStreamDestroy(h->own);
+    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+    free_dev(h->d_indptr, h->d_rows, h->d_contrib, h->ws, h->d_skipped);
+    delete h;
+}
+
+extern "C" rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, const int32_t* rows, const double* contrib, int64_t n_tokens, int64_t n_docs) {
+    if (sparse_check_csr(indptr, rows, contrib, n_tokens, n_docs) != RQ_OK) return nullptr;
+    const int ndev = rq_device_count();
+    if (ndev <= 0) { err_no_device(); return nullptr; }
+    if (device_id < 0 || device_id >= ndev) { set_err(RQ_EINVAL, "device %d outside 0..%d", device_id, ndev - 1); return nullptr; }
+    DeviceGuard dg_(device_id);
+    hipDeviceProp_t prop;
+    if (!dg_.ok || hipGetDeviceProperties(&prop, device_id) != hipSuccess) { set_err(RQ_EHIP, "cannot open device %d", device_id); return nullptr; }
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        set_err(RQ_ENODEVICE, "device %d is %s; this library holds gfx950 code only", device_id, prop.gcnArchName);
+        return nullptr;
+    }
+    rq_sparse* h = new rq_sparse();
+    h->device = device_id;
+    h->n_tokens = n_tokens;
+    h->n_docs = n_docs;
+    h->nnz = indptr[n_tokens];
+    const size_t nnz = (size_t)h->nnz, pad = nnz ? nnz : 1;   // (empty lists: the kernels still get valid pointers)
+    if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&h->d_skipped, sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc((void**)&h->d_indptr, (size_t)(n_tokens + 1) * 8) != hipSuccess || hipMalloc((void**)&h->d_rows, pad * 4) != hipSuccess ||
+        hipMalloc((void**)&h->d_contrib, pad * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        set_err(RQ_ENOMEM, "no room for %zu postings and %lld tokens on device %d", nnz, (long long)n_tokens, device_id);
+        sparse_free(h);
+        return nullptr;
+    }
+    if (hipMemcpy(h->d_indptr, indptr, (size_t)(n_tokens + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (nnz && (hipMemcpy(h->d_rows, rows, nnz * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(h->d_contrib, contrib, nnz * 8, hipMemcpyHostToDevice) != hipSuccess)) ||
+        hipMemset(h->d_skipped, 0, sizeof(unsigned long long)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)rq_sparse_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RQ_SPARSE_TILE_MAX * (int)sizeof(double)) != hipSuccess) {
+        set_err(RQ_EHIP, "upload of the posting index to device %d failed", device_id);
+        sparse_free(h);
+        return nullptr;
+    }
+    return h;
+}
+
+extern "C" void rq_sparse_destroy(rq_sparse* h) {
+    if (!h) return;
+    DeviceGuard dg_(h->device);
+    (void)hipDeviceSynchronize();
+    sparse_free(h);
+}
+
+extern "C" int64_t rq_sparse_postings(const rq_sparse* h) { return h ? h->nnz : 0; }
+
+extern "C" int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
+                                     int32_t* d_rows, double* d_scores, void* stream) {
+    if (int rc = sparse_check_call(h, d_q_indptr, B, k, d_rows, d_scores)) return rc;
+    if (n_q_tokens < 0 || (n_q_tokens > 0 && !d_q_tokens)) return set_err(RQ_EINVAL, "n_q_tokens %lld negative, or tokens without an array", (long long)n_q_tokens);
+    RQ_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const SparsePlan p = sparse_plan(h->n_docs, h->tile_docs, B, k, h->cand_cap);
+    if (p.bytes() > h->ws_bytes) {   // growing waits for the device once: an earlier call may still read the old block
+        HIPCHK(hipDeviceSynchronize());
+        free_dev(h->ws);
+        h->ws_bytes = 0;
+        if (hipMalloc((void**)&h->ws, p.bytes()) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(RQ_ENOMEM, "sparse workspace of %zu bytes (%d queries x %lld tiles x %d candidates)", p.bytes(), p.per_round, (long long)p.tiles, p.slot);
+        }
+        h->ws_bytes = p.bytes();
+    }
+    HIPCHK(hipMemsetAsync(h->d_skipped, 0, sizeof(unsigned long long), s));
+    SparseArgs a;
+    a.indptr = h->d_indptr; a.rows = h->d_rows; a.contrib = h->d_contrib;
+    a.n_tokens = h->n_tokens; a.n_docs = h->n_docs; a.tiles = p.tiles;
+    a.q_indptr = d_q_indptr; a.q_tokens = d_q_tokens; a.n_q_tokens = n_q_tokens;
+    a.k = k; a.slot = p.slot; a.tile_docs = h->tile_docs;
+    a.cand_bits = (uint64_t*)h->ws;
+    a.cand_rows = (int32_t*)(h->ws + p.rows_offset());
+    a.counts = (int32_t*)(h->ws + p.counts_offset());
+    a.skipped = h->d_skipped;
+    a.out_rows = d_rows; a.out_scores = d_scores;
+    h->ev_used = 0;
+    const size_t n_ev = h->profile ? 1 + 2 * (size_t)p.rounds : 0;
+    while (h->ev.size() < n_ev) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        h->ev.push_back(e);
+    }
+    if (n_ev) HIPCHK(hipEventRecord(h->ev[0], s));
+    for (int r = 0; r < p.rounds; ++r) {   // the rounds share the workspace: stream order keeps them apart
+        a.q0 = p.round_first(r);
+        const SparseGrid g = sparse_grid(p, h->tile_docs, p.round_count(r, B));
+        if (p.tiles > 0) hipLaunchKernelGGL(rq_sparse_tile_kernel, dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
+        if (n_ev) HIPCHK(hipEventRecord(h->ev[1 + 2 * (size_t)r], s));
+        hipLaunchKernelGGL(rq_sparse_final_kernel, dim3(g.final_x), dim3(g.block), 0, s, a);
+        if (n_ev) HIPCHK(hipEventRecord(h->ev[2 + 2 * (size_t)r], s));
+    }
+    h->ev_used = n_ev;
+    HIPCHK(hipGetLastError());
+    h->calls++;
+    h->rounds_last = p.rounds;
+    h->tiles_last = p.tiles * (int64_t)B;
+    return RQ_OK;
+}
+
+extern "C" int rq_sparse_topk(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, int32_t* out_rows, double* out_scores) {
+    if (int rc = sparse_check_call(h, q_indptr, B, k, out_rows, out_scores)) return rc;
+    if (int rc = sparse_check_queries(q_indptr, q_tokens, B, h->n_tokens)) return rc;
+    RQ_ON_DEVICE(h);
+    // the tokens of the call alone: positions [q_indptr[0], q_indptr[B]) (the kernel clamps to [0, n_q_tokens), so the array is staged whole)
+    const int64_t nq = q_indptr[B];
+    const size_t bytes[4] = {(size_t)(B + 1) * 8, (size_t)(nq ? nq : 1) * 4, (size_t)B * (size_t)k * 4, (size_t)B * (size_t)k * 8};
+    Stage st(h->own);
+    if (st.alloc(bytes, 4, "rq_sparse_topk") != RQ_OK) return st.code();
+    st.up(st.at<void>(0), q_indptr, bytes[0]);
+    if (nq) st.up(st.at<void>(1), q_tokens, (size_t)nq * 4);
+    if (st.code() != RQ_OK) return st.code();
+    const int rc = rq_sparse_topk_device(h, st.at<int64_t>(0), st.at<int32_t>(1), B, nq, k, st.at<int32_t>(2), st.at<double>(3), (void*)h->own);
+    st.launched();
+    if (rc != RQ_OK) return rc;
+    st.down(out_rows, st.at<void>(2), bytes[2]);
+    st.down(out_scores, st.at<void>(3), bytes[3]);
+    return st.finish();
+}
+
+extern "C" int rq_sparse_set_option(rq_sparse* h, const char* name, double value) {
+    if (!h || !name) return set_err(RQ_EINVAL, "null argument");
+    if (!strcmp(name, "tile_docs")) {
+        if (!sparse_tile_ok(value)) return set_err(RQ_EINVAL, "tile_docs %g is not a power of two in %d..%d", value, RQ_SPARSE_TILE_MIN, RQ_SPARSE_TILE_MAX);
+        h->tile_docs = (int)value;
+        return RQ_OK;
+    }
+    if (!strcmp(name, "cand_cap")) {
+        if (!(value >= 0) || value > 9e18) return set_err(RQ_EINVAL, "cand_cap %g", value);
+        h->cand_cap = (int64_t)value;
+        return RQ_OK;
+    }
+    if (!strcmp(name, "profile")) {
+        h->profile = value != 0;
+        return RQ_OK;
+    }
+    return set_err(RQ_EINVAL, "unknown or read-only sparse option '%s'", name);
+}
+
+extern "C" double rq_sparse_get_option(const rq_sparse* h, const char* name) {
+    if (!h || !name) { set_err(RQ_EINVAL, "null argument"); return -1.0; }
+    if (!strcmp(name, "tile_docs")) return (double)h->tile_docs;
+    if (!strcmp(name, "cand_cap")) return (double)h->cand_cap;
+    if (!strcmp(name, "calls")) return (double)h->calls;
+    if (!strcmp(name, "rounds_last")) return (double)h->rounds_last;
+    if (!strcmp(name, "tiles_last")) return (double)h->tiles_last;
+    if (!strcmp(name, "skipped_tiles_last")) {   // waits for the device
+        DeviceGuard dg_(h->device);
+        unsigned long long v = 0;
+        if (!dg_.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, h->d_skipped, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
+            set_err(RQ_EHIP, "cannot read the skipped-tile counter");
+            return -1.0;
+        }
+        return (double)v;
+    }
+    if (!strcmp(name, "profile")) return (double)h->profile;
+    const bool tile_ms = !strcmp(name, "tile_ms_last");
+    if (tile_ms || !strcmp(name, "final_ms_last")) {   // waits for the device; -1: the last call was not profiled
+        DeviceGuard dg_(h->device);
+        if (h->ev_used < 3 || !dg_.ok || hipDeviceSynchronize() != hipSuccess) { set_err(RQ_EINVAL, "the last call recorded no events (option \"profile\")"); return -1.0; }
+        double ms = 0.0;
+        for (size_t i = tile_ms ? 1 : 2; i < h->ev_used; i += 2) {
+            float one = 0.f;
+            if (hipEventElapsedTime(&one, h->ev[i - 1], h->ev[i]) != hipSuccess) { set_err(RQ_EHIP, "hipEventElapsedTime failed"); return -1.0; }
+            ms += one;
+        }
+        return ms;
+    }
+    set_err(RQ_EINVAL, "unknown sparse option '%s'", name);
+    return -1.0;
+}

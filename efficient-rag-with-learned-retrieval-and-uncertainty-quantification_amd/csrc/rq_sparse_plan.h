@@ -1,0 +1,106 @@
+// rq_sparse_plan.h -- the host side of a sparse (BM25) top-k call (include/rq.h rq_sparse_create, rq_sparse_topk, rq_sparse_topk_device)
+// that needs no device: the validation of the posting arrays and of a call's arguments, the tiles of the corpus, the launch grids, the
+// workspace bytes and the cut of a call into rounds of queries.  Plain arithmetic in the manner of rq_score_plan.h and
+// rq_filter_each_plan.h: no HIP runtime call, nothing is written anywhere (tests/native/sparse_plan_check.cpp runs it on the host).
+// Results never depend on the plan: every (tile_docs, cand_cap) gives the same rows and the same score bits.
+#pragma once
+#include "rq_index.h"
+
+#define RQ_SPARSE_THREADS 256                     // 4 waves per workgroup, both kernels
+#define RQ_SPARSE_CHUNK 256                       // query tokens whose posting sub-ranges are searched at once, one thread each
+#define RQ_SPARSE_TILE_MIN 64
+#define RQ_SPARSE_TILE_MAX 8192                   // 64 KiB of float64 accumulators in LDS: two workgroups per CU
+#define RQ_SPARSE_TILE_DEFAULT 4096               // 32 KiB: four workgroups per CU; measured best at 1M passages
+#define RQ_SPARSE_CAND_BYTES 12                   // one candidate: the score's 8 bytes + an int32 row
+// candidate bytes of one round, 1 GiB as rq_filter_each_plan.h bounds its ragged rounds ("cand_cap": test hook)
+#define RQ_SPARSE_CAND_CAP ((int64_t)1 << 30)
+
+// What rq_sparse_create refuses: what rq_bm25_create refuses, and rows of a token that are not STRICTLY ascending (the kernel
+// binary-searches them; a repeated row would also be a race inside one token), and n_docs >= 2^31 (rows are int32).
+static inline int sparse_check_csr(const int64_t* indptr, const int32_t* rows, const double* contrib, int64_t n_tokens, int64_t n_docs) {
+    if (!indptr) return set_err(RQ_EINVAL, "null indptr");
+    if (n_tokens < 0 || n_docs < 0) return set_err(RQ_EINVAL, "negative n_tokens or n_docs");
+    if (n_docs >= ((int64_t)1 << 31)) return set_err(RQ_EINVAL, "n_docs %lld is 2^31 or more", (long long)n_docs);
+    if (indptr[0] != 0) return set_err(RQ_EINVAL, "indptr[0] is %lld, not 0", (long long)indptr[0]);
+    for (int64_t t = 0; t < n_tokens; ++t)
+        if (indptr[t] > indptr[t + 1]) return set_err(RQ_EINVAL, "indptr decreases at token %lld", (long long)t);
+    const int64_t nnz = indptr[n_tokens];
+    if (nnz > 0 && (!rows || !contrib)) return set_err(RQ_EINVAL, "null rows or contrib with %lld postings", (long long)nnz);
+    for (int64_t t = 0; t < n_tokens; ++t)
+        for (int64_t p = indptr[t]; p < indptr[t + 1]; ++p) {
+            if (rows[p] < 0 || (int64_t)rows[p] >= n_docs) return set_err(RQ_EINVAL, "row %d of token %lld outside 0..%lld", rows[p], (long long)t, (long long)n_docs - 1);
+            if (p > indptr[t] && rows[p] <= rows[p - 1]) return set_err(RQ_EINVAL, "rows of token %lld are not strictly ascending (%d after %d)", (long long)t, rows[p], rows[p - 1]);
+        }
+    return RQ_OK;
+}
+
+// Both entry points (pointers are only tested for null).
+static inline int sparse_check_call(const void* h, const void* q_indptr, int B, int k, const void* out_rows, const void* out_scores) {
+    if (!h || !q_indptr || !out_rows || !out_scores) return set_err(RQ_EINVAL, "null argument");
+    if (B < 1 || B > 65535) return set_err(RQ_EINVAL, "B %d outside 1..65535", B);
+    if (k < 1 || k > RQ_SPARSE_MAX_K) return set_err(RQ_EINVAL, "k %d outside 1..%d", k, RQ_SPARSE_MAX_K);
+    return RQ_OK;
+}
+
+// The host form sees the queries: q_indptr starts at 0 or above and never decreases, every token id is in [0, n_tokens).
+static inline int sparse_check_queries(const int64_t* q_indptr, const int32_t* q_tokens, int B, int64_t n_tokens) {
+    if (q_indptr[0] < 0) return set_err(RQ_EINVAL, "q_indptr[0] is negative");
+    for (int q = 0; q < B; ++q)
+        if (q_indptr[q] > q_indptr[q + 1]) return set_err(RQ_EINVAL, "q_indptr decreases at query %d", q);
+    if (q_indptr[B] > 0 && !q_tokens) return set_err(RQ_EINVAL, "null q_tokens");
+    for (int64_t t = q_indptr[0]; t < q_indptr[B]; ++t)
+        if (q_tokens[t] < 0 || (int64_t)q_tokens[t] >= n_tokens) return set_err(RQ_EINVAL, "token id %d outside 0..%lld", q_tokens[t], (long long)n_tokens - 1);
+    return RQ_OK;
+}
+
+static inline bool sparse_tile_ok(double v) {
+    if (!(v >= RQ_SPARSE_TILE_MIN && v <= RQ_SPARSE_TILE_MAX)) return false;   // (NaN and values no int holds included)
+    const int t = (int)v;
+    return (double)t == v && (t & (t - 1)) == 0;
+}
+
+// A call: `tiles` tiles of tile_docs consecutive documents (the last one may be short; an empty corpus has none), every tile keeps
+// its best `slot` = min(k, tile_docs) candidates per query in a slot of its own, the queries go in `rounds` rounds of at most
+// `per_round`: round r = queries [r * per_round, min(B, (r + 1) * per_round)).  A query whose candidates alone exceed the cap gets a
+// round of its own.
+struct SparsePlan {
+    int64_t tiles = 0;
+    int slot = 0;
+    int64_t query_bytes = 0;       // candidate bytes of one query: tiles x slot x 12
+    int per_round = 0, rounds = 0;
+    size_t cand_elems = 0;         // per_round x tiles x slot
+    size_t count_elems = 0;        // per_round x tiles
+    // workspace: uint64 score bits [cand_elems], then int32 rows [cand_elems], then int32 counts [count_elems]
+    size_t rows_offset() const { return cand_elems * 8; }
+    size_t counts_offset() const { return cand_elems * 12; }
+    size_t bytes() const { return cand_elems * 12 + count_elems * 4; }
+    int round_first(int r) const { return r * per_round; }
+    int round_count(int r, int B) const { return std::min(per_round, B - r * per_round); }
+};
+static inline int64_t sparse_tiles(int64_t n_docs, int tile_docs) { return (n_docs + tile_docs - 1) / tile_docs; }
+// cand_cap <= 0: RQ_SPARSE_CAND_CAP
+static inline SparsePlan sparse_plan(int64_t n_docs, int tile_docs, int B, int k, int64_t cand_cap) {
+    SparsePlan p;
+    p.tiles = sparse_tiles(n_docs, tile_docs);
+    p.slot = std::min(k, tile_docs);
+    p.query_bytes = p.tiles * (int64_t)p.slot * RQ_SPARSE_CAND_BYTES;
+    const int64_t cap = cand_cap > 0 ? cand_cap : RQ_SPARSE_CAND_CAP;
+    const int64_t fit = p.query_bytes > 0 ? cap / p.query_bytes : (int64_t)B;
+    p.per_round = (int)std::max<int64_t>(1, std::min<int64_t>(B, fit));
+    p.rounds = (B + p.per_round - 1) / p.per_round;
+    p.cand_elems = (size_t)p.per_round * (size_t)p.tiles * (size_t)p.slot;
+    p.count_elems = (size_t)p.per_round * (size_t)p.tiles;
+    return p;
+}
+
+// Launch grids: the tile kernel (tiles, queries of the round), the final kernel (queries of the round); 256 threads each.  The tile
+// kernel's dynamic LDS is its accumulator, tile_docs x 8 bytes.
+struct SparseGrid { unsigned tile_x = 0, tile_y = 0, final_x = 0, block = RQ_SPARSE_THREADS; size_t tile_lds = 0; };
+static inline SparseGrid sparse_grid(const SparsePlan& p, int tile_docs, int queries) {
+    SparseGrid g;
+    g.tile_x = (unsigned)p.tiles;
+    g.tile_y = (unsigned)queries;
+    g.final_x = (unsigned)queries;
+    g.tile_lds = (size_t)tile_docs * sizeof(double);
+    return g;
+}

@@ -414,6 +414,8 @@ class BM25Index:
             return c
         if c is not None and c.get("handle") is not None:
             _native.bm25_destroy(c["handle"])
+        if c is not None and c.get("sparse") is not None:
+            c.pop("sparse").close()
         from itertools import chain
         idf = self._ensure_idf()
         avgdl = self._total_len / n_docs
@@ -432,13 +434,25 @@ class BM25Index:
         self.__dict__["_csr_cache"] = c
         return c
 
-    def search_batch_rows(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None
-                          ) -> Tuple[np.ndarray, np.ndarray]:
+    def _sparse_index(self, c: Dict[str, Any]):
+        """The device copy of the CSR arrays (`backend="gpu"`): built by the first search that wants it, dropped with the arrays it was
+        built from (`_drop_csr`, an add).  Raises RqError without the library or a gfx950 device: there is no silent fallback."""
+        if c.get("sparse") is None:
+            c["sparse"] = _native.SparseIndex(c["indptr"], c["rows"], c["contrib"], len(c["tid"]), c["n_docs"], device=self.__dict__.get("sparse_device", 0))
+        return c["sparse"]
+
+    def search_batch_rows(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None,
+                          backend: str = "host") -> Tuple[np.ndarray, np.ndarray]:
         """The selection of `search` for a whole batch, in ROW space: (rows int32 [B][top_k], -1 padded; scores float64 [B][top_k]).
         librq_bm25.so (include/rq_bm25.h) walks the posting lists of every query on the host cores -- term at a time, one float64
         accumulator per thread, the contributions added in query order (the same additions as get_scores: identical bits), top-k by a
         heap with the tie rule of _select_topk.  Without the library (`use_native=False`, or it is not built) the same arrays are
-        scored with numpy, one query at a time."""
+        scored with numpy, one query at a time.
+        `backend`: "host" (default) is the path above; "gpu" scores and selects on the device (include/rq.h rq_sparse_topk, a
+        `_native.SparseIndex` over the same arrays: the same rows and the same score bits; top_k <= 1024, at most 65 535 queries;
+        RqError without a device); "auto" takes the device when one is visible and the host otherwise."""
+        if backend not in ("host", "gpu", "auto"):
+            raise ValueError(f"backend must be 'host', 'gpu' or 'auto', not {backend!r}")
         B, k = len(queries), max(int(top_k), 1)
         if self.bm25 is None or not self.doc_ids or top_k <= 0 or B == 0:
             return np.full((B, k), -1, np.int32), np.zeros((B, k))
@@ -452,6 +466,8 @@ class BM25Index:
                 if j is not None:
                     q_tok.append(j)
             q_ptr.append(len(q_tok))
+        if backend == "gpu" or (backend == "auto" and _native.sparse_available()):
+            return self._sparse_index(c).topk(np.asarray(q_ptr, np.int64), np.asarray(q_tok, np.int32), B, k)
         if use_native and c["handle"] is None:
             raise _native.RqError("librq_bm25.so is not built: `make -C csrc` (or use_native=False for the numpy path)")
         native = c["handle"] is not None if use_native is None else (use_native and c["handle"] is not None)
@@ -477,12 +493,12 @@ class BM25Index:
             self.__dict__["_ids_np"] = cache
         return cache
 
-    def search_batch(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None
-                     ) -> List[List[Tuple[str, float]]]:
-        """`[self.search(q, top_k) for q in queries]`, scored as one job (search_batch_rows)."""
+    def search_batch(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None,
+                     backend: str = "host") -> List[List[Tuple[str, float]]]:
+        """`[self.search(q, top_k) for q in queries]`, scored as one job (search_batch_rows; `backend` as there)."""
         if self.bm25 is None or not self.doc_ids or top_k <= 0:
             return [[] for _ in queries]
-        out_rows, out_scores = self.search_batch_rows(queries, top_k, n_threads=n_threads, use_native=use_native)
+        out_rows, out_scores = self.search_batch_rows(queries, top_k, n_threads=n_threads, use_native=use_native, backend=backend)
         idl = self._ids_array()[np.where(out_rows >= 0, out_rows, 0)].tolist()
         scl = out_scores.tolist()
         have = (out_rows >= 0).sum(axis=1).tolist()
@@ -492,6 +508,8 @@ class BM25Index:
         c = self.__dict__.pop("_csr_cache", None)
         if c is not None and c.get("handle") is not None:
             _native.bm25_destroy(c["handle"])
+        if c is not None and c.get("sparse") is not None:
+            c.pop("sparse").close()
 
     def __del__(self):
         try:
@@ -1340,12 +1358,17 @@ class DenseIndex:
 class HybridRetriever:
     """Unified hybrid retrieval combining BM25 and dense retrieval (reference :376-560).
 
-    Extra keyword-only arguments: `dense_index` (inject a ready index), `embedder`, `device`.
+    Extra keyword-only arguments: `dense_index` (inject a ready index), `embedder`, `device`, `sparse_backend` ("host" = default:
+    BM25 on the host cores; "gpu": the batch calls -- hybrid_search_batch, get_scores_for_router_batch -- score BM25 on the device,
+    same rows and score bits, RqError without one; "auto": the device when one is visible).
     """
 
     def __init__(self, bm25_persist_path: str = "./data/bm25_index.pkl", chroma_persist_path: str = "./data/chroma_db",
                  chroma_host: Optional[str] = None, embedding_model: str = "nomic-embed-text",
-                 *, dense_index=None, embedder=None, device: int = 0):
+                 *, dense_index=None, embedder=None, device: int = 0, sparse_backend: str = "host"):
+        if sparse_backend not in ("host", "gpu", "auto"):
+            raise ValueError(f"sparse_backend must be 'host', 'gpu' or 'auto', not {sparse_backend!r}")
+        self.sparse_backend = sparse_backend   # where the BATCH calls score BM25 (BM25Index.search_batch_rows `backend`); per-query calls stay on the host
         self.bm25_index = BM25Index(persist_path=bm25_persist_path)
         if dense_index is not None:
             self.dense_index = dense_index
@@ -1360,6 +1383,11 @@ class HybridRetriever:
         # process over a persisted index answers [].  The BM25 pickle holds every Document:
         # restore the store from it (same signatures, DESIGN.md "deviations").
         self.documents: Dict[str, Document] = dict(self.bm25_index.documents)
+
+    def _sparse_kw(self) -> Dict[str, str]:
+        """The `backend` keyword of the BM25 batch calls; nothing for "host", so an injected sparse index needs no such keyword."""
+        backend = getattr(self, "sparse_backend", "host")
+        return {} if backend == "host" else {"backend": backend}
 
     def add_documents(self, documents: List[Document], batch_size: int = 100) -> Dict[str, int]:
         for doc in documents:
@@ -1538,7 +1566,7 @@ class HybridRetriever:
         if self.bm25_index is None:
             sparse = [[] for _ in queries]
         elif hasattr(self.bm25_index, "search_batch"):
-            sparse = self.bm25_index.search_batch(list(queries), retrieval_pool_size)
+            sparse = self.bm25_index.search_batch(list(queries), retrieval_pool_size, **self._sparse_kw())
         else:
             sparse = [self.bm25_search(q, retrieval_pool_size) for q in queries]
         return dense, sparse
@@ -1628,7 +1656,7 @@ class HybridRetriever:
             return None
         B = len(queries)
         ks = self._key_space()
-        sp_rows, sp_scores = bm.search_batch_rows(list(queries), retrieval_pool_size)
+        sp_rows, sp_scores = bm.search_batch_rows(list(queries), retrieval_pool_size, **self._sparse_kw())
         if complete_scores:
             qv = dn._embed_queries(list(queries))
             de_scores, de_rows = dn._search_embedded(qv, retrieval_pool_size)

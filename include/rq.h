@@ -486,6 +486,54 @@ int rq_search_group_members_fixup_device(rq_index* idx, const rq_filter* f, cons
 int rq_search_group_members(rq_index* idx, const rq_filter* f, const float* queries, int B, int k, int s, int metric, float* out_scores, int64_t* out_rows,
                             int32_t* out_groups, int32_t* out_count);
 
+/* ---- sparse search: exact BM25 top-k over a posting index that lives on the device (the sparse half of the hybrid retriever,
+ * reference rag_uq/streaming_index.py:168-177, which include/rq_bm25.h answers on the host cores) ------------------
+ * An rq_sparse is an object of its own, beside rq_index: an inverted index in CSR form -- token t owns postings
+ * [indptr[t], indptr[t+1]): rows[] = document rows, contrib[] = that posting's float64 score contribution -- copied to one device.
+ * Definition: that of rq_bm25_topk, restated.
+ *   score(q, d) = the float64 sum of contrib[p] over the query's tokens, with repetition, added IN QUERY ORDER starting from 0.0.
+ *   Only documents with score > 0 are returned: a NaN or negative total and an exact cancellation are left out; a +inf total is a
+ *     score like any other and ranks first.
+ *   Results are best first, equal scores by DESCENDING row, at most k per query; out_rows is padded with -1, out_scores with 0.0.
+ *   Every returned score has the bits rq_bm25_topk returns, every row list is identical to its list (the kernel performs the same
+ *     additions in the same order; csrc/rq_sparse.hip).
+ * rq_sparse_create: host CSR arrays, COPIED to the device (unlike rq_bm25_create, which borrows them): 12 B per posting + 8 B per
+ *   token of HBM.  It refuses what rq_bm25_create refuses (indptr[0] != 0, a decreasing indptr, a row outside [0, n_docs)), and
+ *   also rows of a token that are not STRICTLY ascending (the kernel binary-searches them; BM25Index produces them so) and
+ *   n_docs >= 2^31: NULL with the message in rq_last_error(); NULL + the "no HIP device" message without a gfx950 device.
+ * Queries: query q owns q_tokens[q_indptr[q] .. q_indptr[q+1]), token ids in query order with repetition.
+ * rq_sparse_topk: blocking, host buffers (out_rows [B][k] int32, out_scores [B][k] float64), staged on a stream the handle owns.
+ *   RQ_EINVAL unless 1 <= B <= 65535, 1 <= k <= RQ_SPARSE_MAX_K, q_indptr[0] >= 0 and never decreasing, every token id in
+ *   [0, n_tokens), non-null pointers.
+ * rq_sparse_topk_device: asynchronous, device pointers, no host synchronisation in steady state; results are complete in stream
+ *   order.  n_q_tokens = the length of d_q_tokens.  The host cannot see the queries: a token id outside [0, n_tokens) is an EMPTY
+ *   posting list, and an entry of d_q_indptr outside [0, n_q_tokens] or below its predecessor is clamped (no read outside the arrays).
+ * Workspace and threading: one workspace per handle, tiles x min(k, tile_docs) x 12 B + 4 B per tile for every query of a round.  A
+ *   handle is used from one thread and its calls are ordered by the caller: one stream, or events between streams.  A call that
+ *   needs a larger workspace than the handle has waits for the device once (hipDeviceSynchronize) and allocates; a call that fits
+ *   does not wait.
+ * Options (rq_sparse_set_option / rq_sparse_get_option; results never depend on them): "tile_docs" (documents per workgroup, a power
+ *   of two in 64 .. 8192, default 4096: one float64 accumulator per document in LDS; settable any time), "cand_cap" (test hook:
+ *   candidate bytes -- tiles x min(k, tile_docs) x 12 per query -- one round of queries may hold, 0 = default = 1 GiB; a call beyond it
+ *   runs in rounds, a query beyond it alone in a round of its own); read-only "calls", "rounds_last", "tiles_last" (tiles x B of the
+ *   last call), "skipped_tiles_last" (tiles of the last call in which no token of the query had a posting: they leave before any
+ *   work; waits for the device); "profile" (measurement hook, default 0: 1 = every call records HIP events around its launches;
+ *   read-only "tile_ms_last" / "final_ms_last" then give the last call's time in the tile and in the final kernels, summed over its
+ *   rounds; they wait for the device, -1 when the last call recorded none).  rq_sparse_get_option returns -1 with a message for
+ *   an unknown name.
+ * Not extended: allowed_ids filters, distinct_by, a device form of BM25Index.score_rows, multi-device handles, fusion of the sparse
+ *   and dense lists on the device. */
+typedef struct rq_sparse rq_sparse;
+#define RQ_SPARSE_MAX_K 1024
+rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, const int32_t* rows, const double* contrib, int64_t n_tokens, int64_t n_docs);
+void rq_sparse_destroy(rq_sparse* h);
+int64_t rq_sparse_postings(const rq_sparse* h);
+int rq_sparse_topk(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, int32_t* out_rows, double* out_scores);
+int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
+                          int32_t* d_rows, double* d_scores, void* stream);
+int rq_sparse_set_option(rq_sparse* h, const char* name, double value);
+double rq_sparse_get_option(const rq_sparse* h, const char* name);
+
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
  * "wg_per_cu", "nt" (non-temporal corpus loads: 0, 1, -1 = auto), "slack_bins" (extra bins beyond k, -1 = auto),
