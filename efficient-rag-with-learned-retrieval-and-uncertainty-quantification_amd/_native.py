@@ -107,6 +107,15 @@ _SIGNATURES = {
     "rq_sparse_postings": (C.c_int64, [C.c_void_p]),
     "rq_sparse_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rq_sparse_topk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_sparse_score_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rq_sparse_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "rq_hybrid_create": (C.c_void_p, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "rq_hybrid_destroy": (None, [C.c_void_p]),
+    "rq_hybrid_get_option": (C.c_double, [C.c_void_p, C.c_char_p]),
+    "rq_hybrid_missing_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_hybrid_missing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rq_hybrid_fuse_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 7),
+    "rq_hybrid_fuse": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6),
     "rq_sparse_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "rq_sparse_get_option": (C.c_double, [C.c_void_p, C.c_char_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -769,6 +778,24 @@ class SparseIndex:
         _check(self._lib.rq_sparse_topk_device(self._h, _ptr(d_q_indptr), _ptr(d_q_tokens), int(B), int(n_q_tokens), int(k), _ptr(d_rows),
                                                _ptr(d_scores), C.c_void_p(stream)), "rq_sparse_topk_device")
 
+    def score_rows(self, q_indptr, q_tokens, B: int, rows) -> np.ndarray:
+        """Blocking, host arrays: the BM25 score of every (query, row) pair of one list of rows per query, rows int32 [B][m] -> float64
+        [B][m] with the bits of a full score vector's entry; a row outside the index (-1 included) scores 0.0 (rq_sparse_score_rows)."""
+        q_indptr = np.ascontiguousarray(q_indptr, np.int64)
+        q_tokens = np.ascontiguousarray(q_tokens, np.int32)
+        rows = np.ascontiguousarray(rows, np.int32)
+        if len(q_indptr) != int(B) + 1 or (int(B) >= 1 and len(q_tokens) < int(q_indptr[-1])) or rows.ndim != 2 or rows.shape[0] != int(B):
+            raise RqError(f"rq_sparse_score_rows: q_indptr holds {len(q_indptr)} entries and rows has shape {rows.shape} for {B} queries, or q_tokens is short")
+        out = np.empty(rows.shape, np.float64)
+        _check(self._lib.rq_sparse_score_rows(self._h, _ptr(q_indptr), _ptr(q_tokens) if len(q_tokens) else None, int(B), _ptr(rows), int(rows.shape[1]),
+                                              _ptr(out)), "rq_sparse_score_rows")
+        return out
+
+    def score_rows_device(self, d_q_indptr, d_q_tokens, B: int, n_q_tokens: int, d_rows, m: int, d_scores, stream: int = 0) -> None:
+        """Asynchronous, device pointers: int64 [B + 1], int32 [n_q_tokens], int32 [B][m] -> float64 [B][m]; complete in stream order."""
+        _check(self._lib.rq_sparse_score_rows_device(self._h, _ptr(d_q_indptr), _ptr(d_q_tokens), int(B), int(n_q_tokens), _ptr(d_rows), int(m),
+                                                     _ptr(d_scores), C.c_void_p(stream)), "rq_sparse_score_rows_device")
+
     def set_option(self, name: str, value: float) -> None:
         _check(self._lib.rq_sparse_set_option(self._h, name.encode(), float(value)), f"rq_sparse_set_option({name})")
 
@@ -782,6 +809,93 @@ def sparse_available() -> bool:
         return device_count() > 0
     except (RqError, OSError):
         return False
+
+
+# -- hybrid fusion on the device (include/rq.h "hybrid fusion", csrc/rq_hybrid.hip) ------------------------------------------------------
+HYBRID_MAX_CAND = 2048
+
+
+class HybridMap:
+    """Owner of one rq_hybrid handle: the key space that joins a sparse and a dense index (dense_key [n_dense] int64, injective; known
+    [n_keys] one byte per key; COPIED to the device with the inverse map) and the two calls over a batch of pools: `missing` (the rows
+    whose score the other retriever did not give) and `fuse` (the hybrid ranking, bit for bit the host path's).  No host fallback."""
+
+    def __init__(self, nb: int, dense_key: np.ndarray, known: np.ndarray, device: int = 0):
+        self._lib = load_library()
+        dense_key = np.ascontiguousarray(dense_key, np.int64)
+        known = np.ascontiguousarray(np.asarray(known) != 0, np.uint8)
+        if dense_key.ndim != 1 or known.ndim != 1:
+            raise RqError("rq_hybrid_create: dense_key and known are one-dimensional")
+        h = self._lib.rq_hybrid_create(int(device), int(nb), len(dense_key), _ptr(dense_key) if len(dense_key) else None,
+                                       _ptr(known) if len(known) else None, len(known))
+        if not h:
+            raise RqError(f"rq_hybrid_create: {last_error()}")
+        self._h = C.c_void_p(h)
+        self.nb, self.n_dense, self.n_keys, self.device = int(nb), len(dense_key), len(known), int(device)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.rq_hybrid_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def get_option(self, name: str) -> float:
+        return float(self._lib.rq_hybrid_get_option(self._h, name.encode()))
+
+    @staticmethod
+    def _pools(sp_rows, de_rows) -> Tuple[np.ndarray, np.ndarray]:
+        sp_rows = np.ascontiguousarray(sp_rows, np.int32)
+        de_rows = np.ascontiguousarray(de_rows, np.int64)
+        if sp_rows.ndim != 2 or de_rows.ndim != 2 or sp_rows.shape[0] != de_rows.shape[0]:
+            raise RqError(f"hybrid pools are [B][K1] and [B][K2], got {sp_rows.shape} and {de_rows.shape}")
+        return sp_rows, de_rows
+
+    def missing(self, sp_rows, de_rows) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocking, host arrays: (miss_dense int64 [B][K1], miss_sparse int32 [B][K2]), -1 where nothing is missing."""
+        sp_rows, de_rows = self._pools(sp_rows, de_rows)
+        B, K1, K2 = sp_rows.shape[0], sp_rows.shape[1], de_rows.shape[1]
+        miss_dense, miss_sparse = np.empty((B, K1), np.int64), np.empty((B, K2), np.int32)
+        _check(self._lib.rq_hybrid_missing(self._h, _ptr(sp_rows) if K1 else None, _ptr(de_rows) if K2 else None, B, K1, K2,
+                                           _ptr(miss_dense) if K1 else None, _ptr(miss_sparse) if K2 else None), "rq_hybrid_missing")
+        return miss_dense, miss_sparse
+
+    def missing_device(self, d_sp_rows, d_de_rows, B: int, K1: int, K2: int, d_miss_dense, d_miss_sparse, stream: int = 0) -> None:
+        """Asynchronous, device pointers: int32 [B][K1], int64 [B][K2] -> int64 [B][K1], int32 [B][K2]; complete in stream order."""
+        _check(self._lib.rq_hybrid_missing_device(self._h, _ptr(d_sp_rows), _ptr(d_de_rows), int(B), int(K1), int(K2), _ptr(d_miss_dense),
+                                                  _ptr(d_miss_sparse), C.c_void_p(stream)), "rq_hybrid_missing_device")
+
+    def fuse(self, sp_rows, sp_scores, de_rows, de_scores, top_k: int, *, miss_dense=None, extra_dense=None, miss_sparse=None, extra_sparse=None):
+        """Blocking, host arrays: (keys int32, b, d, h float64, positions int32 -- all [B][top_k] -- and count int32 [B])."""
+        sp_rows, de_rows = self._pools(sp_rows, de_rows)
+        B, K1, K2, k = sp_rows.shape[0], sp_rows.shape[1], de_rows.shape[1], int(top_k)
+        sp_scores = np.ascontiguousarray(sp_scores, np.float64)
+        de_scores = np.ascontiguousarray(de_scores, np.float32)
+        if sp_scores.shape != sp_rows.shape or de_scores.shape != de_rows.shape:
+            raise RqError("hybrid pools: scores and rows differ in shape")
+        opt = [None if x is None else np.ascontiguousarray(x, t)
+               for x, t in ((miss_dense, np.int64), (extra_dense, np.float32), (miss_sparse, np.int32), (extra_sparse, np.float64))]
+        for x, shape in zip(opt, (sp_rows.shape, sp_rows.shape, de_rows.shape, de_rows.shape)):
+            if x is not None and x.shape != shape:
+                raise RqError(f"hybrid fuse: a miss / extra array of shape {x.shape} for a pool of shape {shape}")
+        kk = max(k, 0)
+        keys, pos, count = np.empty((B, kk), np.int32), np.empty((B, kk), np.int32), np.empty(B, np.int32)
+        b, d, h = np.empty((B, kk)), np.empty((B, kk)), np.empty((B, kk))
+        _check(self._lib.rq_hybrid_fuse(self._h, _ptr(sp_rows) if K1 else None, _ptr(sp_scores) if K1 else None, _ptr(de_rows) if K2 else None,
+                                        _ptr(de_scores) if K2 else None, B, K1, K2, *[_ptr(x) if x is not None and x.size else None for x in opt], k,
+                                        _ptr(keys), _ptr(b), _ptr(d), _ptr(h), _ptr(pos), _ptr(count)), "rq_hybrid_fuse")
+        return keys, b, d, h, pos, count
+
+    def fuse_device(self, d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B: int, K1: int, K2: int, top_k: int, d_keys, d_b, d_d, d_h, d_pos, d_count,
+                    stream: int = 0, *, d_miss_dense=None, d_extra_dense=None, d_miss_sparse=None, d_extra_sparse=None) -> None:
+        """Asynchronous, device pointers (include/rq.h rq_hybrid_fuse_device); d_pos and the four miss / extra arrays may be None."""
+        _check(self._lib.rq_hybrid_fuse_device(self._h, _ptr(d_sp_rows), _ptr(d_sp_scores), _ptr(d_de_rows), _ptr(d_de_scores), int(B), int(K1), int(K2),
+                                               _ptr(d_miss_dense), _ptr(d_extra_dense), _ptr(d_miss_sparse), _ptr(d_extra_sparse), int(top_k), _ptr(d_keys),
+                                               _ptr(d_b), _ptr(d_d), _ptr(d_h), _ptr(d_pos), _ptr(d_count), C.c_void_p(stream)), "rq_hybrid_fuse_device")
 
 
 # -- encoder pieces (include/rq.h "encoder pieces", csrc/rq_encoder.hip): torch tensors or raw device addresses -------------

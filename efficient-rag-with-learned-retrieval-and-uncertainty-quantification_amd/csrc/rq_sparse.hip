@@ -14,6 +14,7 @@
 // with ties by descending row (the keys are unique: the result does not depend on the order of the slots), then the padding.
 #include "rq_sparse_plan.h"
 #include "rq_sparse_select.h"
+#include "rq_sparse_handle.h"
 #include "rq_stage.h"
 
 struct SparseArgs {
@@ -213,25 +214,6 @@ __global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_final_kernel(Spar
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct rq_sparse {
-    int device = 0;
-    int64_t n_tokens = 0, n_docs = 0, nnz = 0;
-    int64_t* d_indptr = nullptr;
-    int32_t* d_rows = nullptr;
-    double* d_contrib = nullptr;
-    hipStream_t own = nullptr;
-    char* ws = nullptr;                   // the one workspace (rq_sparse_plan.h SparsePlan)
-    size_t ws_bytes = 0;
-    unsigned long long* d_skipped = nullptr;
-    int tile_docs = RQ_SPARSE_TILE_DEFAULT;
-    int64_t cand_cap = 0;
-    int64_t calls = 0, rounds_last = 0, tiles_last = 0;
-    // option "profile": HIP events before a call's first launch and after every launch; "tile_ms_last" / "final_ms_last" sum them
-    int profile = 0;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;           // events the last profiled call recorded: 1 + 2 x rounds (0: none)
-};
-
 static void sparse_free(rq_sparse* h) {
     if (h->own) (void)hipStreamDestroy(h->own);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -381,6 +363,7 @@ extern "C" double rq_sparse_get_option(const rq_sparse* h, const char* name) {
     if (!strcmp(name, "tile_docs")) return (double)h->tile_docs;
     if (!strcmp(name, "cand_cap")) return (double)h->cand_cap;
     if (!strcmp(name, "calls")) return (double)h->calls;
+    if (!strcmp(name, "score_calls")) return (double)h->score_calls;
     if (!strcmp(name, "rounds_last")) return (double)h->rounds_last;
     if (!strcmp(name, "tiles_last")) return (double)h->tiles_last;
     if (!strcmp(name, "skipped_tiles_last")) {   // waits for the device

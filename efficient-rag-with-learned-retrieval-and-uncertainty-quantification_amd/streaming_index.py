@@ -308,11 +308,21 @@ class BM25Index:
         repeat."""
         return self._score_rows_tokens(self._tokenize(query), rows)
 
-    def score_rows_batch(self, queries: Sequence[str], rows) -> np.ndarray:
-        """`score_rows` for one list of rows per query: rows [B][m] -> float64 [B][m]."""
+    def score_rows_batch(self, queries: Sequence[str], rows, *, backend: str = "host") -> np.ndarray:
+        """`score_rows` for one list of rows per query: rows [B][m] -> float64 [B][m].
+        `backend` as in `search_batch_rows`: "host" (default) is the loop below; "gpu" scores every pair on the device (include/rq.h
+        rq_sparse_score_rows over the `_native.SparseIndex` of the current corpus: the same bits; m <= 65 536, at most 65 535 queries;
+        RqError without a device); "auto" takes the device when one is visible."""
+        if backend not in ("host", "gpu", "auto"):
+            raise ValueError(f"backend must be 'host', 'gpu' or 'auto', not {backend!r}")
         rows = np.asarray(rows, dtype=np.int64)
         if rows.ndim != 2 or rows.shape[0] != len(queries):
             raise ValueError(f"expected [{len(queries)}][m] rows, one list per query, got {rows.shape}")
+        if (backend == "gpu" or (backend == "auto" and _native.sparse_available())) and self.doc_ids and rows.size:
+            c = self._csr()
+            q_ptr, q_tok = self._query_csr(c, queries)
+            inside = (rows >= 0) & (rows < len(self.doc_ids))
+            return self._sparse_index(c).score_rows(q_ptr, q_tok, len(queries), np.where(inside, rows, -1).astype(np.int32))
         out = np.zeros(rows.shape)
         for b, q in enumerate(queries):
             if (rows[b] >= 0).any():
@@ -441,6 +451,19 @@ class BM25Index:
             c["sparse"] = _native.SparseIndex(c["indptr"], c["rows"], c["contrib"], len(c["tid"]), c["n_docs"], device=self.__dict__.get("sparse_device", 0))
         return c["sparse"]
 
+    def _query_csr(self, c: Dict[str, Any], queries: Sequence[str]) -> Tuple[List[int], List[int]]:
+        """The queries as token ids of `c` in query order, with repetition, tokens the corpus does not hold left out: (offsets [B + 1], ids)."""
+        tid = c["tid"]
+        q_tok: List[int] = []
+        q_ptr = [0]
+        for q in queries:
+            for t in self._tokenize(q):
+                j = tid.get(t)
+                if j is not None:
+                    q_tok.append(j)
+            q_ptr.append(len(q_tok))
+        return q_ptr, q_tok
+
     def search_batch_rows(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None,
                           backend: str = "host") -> Tuple[np.ndarray, np.ndarray]:
         """The selection of `search` for a whole batch, in ROW space: (rows int32 [B][top_k], -1 padded; scores float64 [B][top_k]).
@@ -457,15 +480,7 @@ class BM25Index:
         if self.bm25 is None or not self.doc_ids or top_k <= 0 or B == 0:
             return np.full((B, k), -1, np.int32), np.zeros((B, k))
         c = self._csr()
-        tid = c["tid"]
-        q_tok: List[int] = []
-        q_ptr = [0]
-        for q in queries:
-            for t in self._tokenize(q):
-                j = tid.get(t)
-                if j is not None:
-                    q_tok.append(j)
-            q_ptr.append(len(q_tok))
+        q_ptr, q_tok = self._query_csr(c, queries)
         if backend == "gpu" or (backend == "auto" and _native.sparse_available()):
             return self._sparse_index(c).topk(np.asarray(q_ptr, np.int64), np.asarray(q_tok, np.int32), B, k)
         if use_native and c["handle"] is None:
@@ -1360,15 +1375,21 @@ class HybridRetriever:
 
     Extra keyword-only arguments: `dense_index` (inject a ready index), `embedder`, `device`, `sparse_backend` ("host" = default:
     BM25 on the host cores; "gpu": the batch calls -- hybrid_search_batch, get_scores_for_router_batch -- score BM25 on the device,
-    same rows and score bits, RqError without one; "auto": the device when one is visible).
+    same rows and score bits, RqError without one; "auto": the device when one is visible), `fusion_backend` ("host" = default: the
+    batch calls fuse both pools with numpy on the host; "gpu": both pools stay in HBM and are fused there -- include/rq.h "hybrid
+    fusion", the same values bit for bit -- and only [B][top_k] results come back; it needs `sparse_backend` "gpu" or "auto" and a
+    single-device DenseIndex, and raises RqError with the reason otherwise; "auto": the device when all of that holds, else the host).
     """
 
     def __init__(self, bm25_persist_path: str = "./data/bm25_index.pkl", chroma_persist_path: str = "./data/chroma_db",
                  chroma_host: Optional[str] = None, embedding_model: str = "nomic-embed-text",
-                 *, dense_index=None, embedder=None, device: int = 0, sparse_backend: str = "host"):
+                 *, dense_index=None, embedder=None, device: int = 0, sparse_backend: str = "host", fusion_backend: str = "host"):
         if sparse_backend not in ("host", "gpu", "auto"):
             raise ValueError(f"sparse_backend must be 'host', 'gpu' or 'auto', not {sparse_backend!r}")
+        if fusion_backend not in ("host", "gpu", "auto"):
+            raise ValueError(f"fusion_backend must be 'host', 'gpu' or 'auto', not {fusion_backend!r}")
         self.sparse_backend = sparse_backend   # where the BATCH calls score BM25 (BM25Index.search_batch_rows `backend`); per-query calls stay on the host
+        self.fusion_backend = fusion_backend   # where the BATCH calls fuse the two pools (`_fuse_batch_rows`)
         self.bm25_index = BM25Index(persist_path=bm25_persist_path)
         if dense_index is not None:
             self.dense_index = dense_index
@@ -1629,6 +1650,8 @@ class HybridRetriever:
         c = self.__dict__.get("_keys_cache")
         if c is not None and c["stamp"] == stamp:
             return c
+        if c is not None and c.get("map") is not None:      # the device copy follows the key space it was built from
+            c.pop("map").close()
         nb = len(bm.doc_ids)
         row_of = {d: i for i, d in enumerate(bm.doc_ids)}
         dense_key = np.fromiter((row_of.get(d, nb + j) for j, d in enumerate(dn._ids)), np.int64, len(dn._ids))
@@ -1639,8 +1662,112 @@ class HybridRetriever:
         known = np.fromiter((d in docs for d in all_ids), np.bool_, len(all_ids))
         dense_row = np.full(len(all_ids), -1, np.int64)
         dense_row[dense_key] = np.arange(len(dn._ids), dtype=np.int64)
-        c = self.__dict__["_keys_cache"] = {"stamp": stamp, "nb": nb, "dense_key": dense_key, "ids": ids, "known": known, "dense_row": dense_row}
+        # DenseIndex.add_documents skips ids it holds, but add_vectors, from_native and a loaded collection take ids as they come: whether
+        # dense_key is injective (the device fusion needs it, include/rq.h rq_hybrid_create) is checked once per rebuild
+        injective = len(np.unique(dense_key)) == len(dense_key)
+        c = self.__dict__["_keys_cache"] = {"stamp": stamp, "nb": nb, "dense_key": dense_key, "ids": ids, "known": known, "dense_row": dense_row,
+                                            "injective": injective, "map": None}
         return c
+
+    # ---- the same fusion on the device (extension; include/rq.h "hybrid fusion") -----------------------------------
+    def _device_fusion_refusal(self, top_k: int, retrieval_pool_size: int) -> Optional[str]:
+        """Why this call cannot be fused on the device, or None.  (DenseIndex never sets a row offset: its rows are positions in `_ids`.)"""
+        bm, dn = self.bm25_index, self.dense_index
+        sparse = getattr(self, "sparse_backend", "host")
+        if not _native.sparse_available():
+            return "no HIP device is visible"
+        if sparse == "host":
+            return "sparse_backend is 'host': the sparse pool must be drawn on the device (sparse_backend='gpu' or 'auto')"
+        if dn._index is not None and not (isinstance(dn._index, _native.NativeIndex) and dn._can("device")):
+            return "the dense index is not a single-device NativeIndex"
+        if dn._index is not None and bm.__dict__.get("sparse_device", 0) != dn._index.device:
+            return "the sparse and the dense index are on different devices"
+        if not 1 <= int(top_k) <= _native.MAX_K or max(int(retrieval_pool_size), 1) > _native.SPARSE_MAX_K:
+            return f"top_k {top_k} or pool {retrieval_pool_size} beyond {_native.MAX_K}"
+        if not self._key_space()["injective"]:
+            return "the dense index holds an id twice: dense rows do not map to distinct keys"
+        return None
+
+    def _fuse_on_device(self, top_k: int, retrieval_pool_size: int) -> bool:
+        backend = getattr(self, "fusion_backend", "host")
+        if backend == "host":
+            return False
+        reason = self._device_fusion_refusal(top_k, retrieval_pool_size)
+        if reason is not None and backend == "gpu":
+            raise _native.RqError(f"fusion_backend='gpu': {reason}")
+        return reason is None
+
+    def _hybrid_map(self, ks, device: int):
+        """The device copy of the key space (`_native.HybridMap`): built by the first fusion that wants it, dropped with the key space."""
+        if ks.get("map") is None:
+            ks["map"] = _native.HybridMap(ks["nb"], ks["dense_key"], ks["known"], device=device)
+        return ks["map"]
+
+    def _fuse_batch_device(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool):
+        """`_fuse_batch_rows` with both pools left where they are drawn: token ids and query vectors go down, rq_sparse_topk_device and
+        rq_search_device (with its fixup) fill the pools in HBM, `complete_scores` adds rq_hybrid_missing_device and the two row-scoring
+        calls, rq_hybrid_fuse_device ranks, and one copy brings [B][top_k] keys, scores and the counts back.  Same return value."""
+        import torch
+        bm, dn = self.bm25_index, self.dense_index
+        B, k, K1 = len(queries), int(top_k), max(int(retrieval_pool_size), 1)
+        ks = self._key_space()
+        device = dn._index.device if dn._index is not None else bm.__dict__.get("sparse_device", 0)
+        hm = self._hybrid_map(ks, device)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream(dev).cuda_stream
+            d_sp_rows = torch.empty((B, K1), device=dev, dtype=torch.int32)
+            d_sp_scores = torch.empty((B, K1), device=dev, dtype=torch.float64)
+            sp = None
+            if bm.bm25 is not None and bm.doc_ids and retrieval_pool_size > 0:
+                c = bm._csr()
+                sp = bm._sparse_index(c)
+                q_ptr, q_tok = bm._query_csr(c, queries)
+                d_ptr = torch.tensor(q_ptr, dtype=torch.int64).to(dev)
+                d_tok = torch.tensor(q_tok or [0], dtype=torch.int32).to(dev)
+                sp.topk_device(d_ptr, d_tok, B, len(q_tok), K1, d_sp_rows, d_sp_scores, stream=s)
+            else:
+                d_sp_rows.fill_(-1)
+                d_sp_scores.zero_()
+            K2, d_q, d_de_rows, d_de_scores = 0, None, None, None
+            if not dn._nothing_to_search(retrieval_pool_size, B):
+                d_q = dn._embed_device(queries)
+                if d_q is None:
+                    d_q = torch.from_numpy(np.ascontiguousarray(dn._embed_matrix(list(queries)), dtype=np.float32)).to(dev)
+                d_q = d_q.to(torch.float32).contiguous()
+                dn._check_dim(int(d_q.shape[1]))
+                K2 = dn._k(retrieval_pool_size)
+                d_de_rows = torch.empty((B, K2), device=dev, dtype=torch.int64)
+                d_de_scores = torch.empty((B, K2), device=dev, dtype=torch.float32)
+                d_status = torch.empty((B,), device=dev, dtype=torch.int32)
+                dn._index.search_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, s)
+                dn._index.search_flush_device(s)
+                if bool(d_status.any()):                                       # rare: a certificate failed -> exact repair on the device
+                    dn._index.search_fixup_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, s)
+            extra = {}
+            if complete_scores:
+                d_miss_dense = torch.empty((B, K1), device=dev, dtype=torch.int64)
+                d_miss_sparse = torch.empty((B, max(K2, 1)), device=dev, dtype=torch.int32)
+                hm.missing_device(d_sp_rows, d_de_rows, B, K1, K2, d_miss_dense, d_miss_sparse, s)
+                if K2:
+                    d_extra_dense = torch.empty((B, K1), device=dev, dtype=torch.float32)
+                    dn._index.score_rows_device(d_q, B, d_miss_dense, K1, dn.metric, d_extra_dense, s)
+                    extra.update(d_miss_dense=d_miss_dense, d_extra_dense=d_extra_dense)
+                    if sp is not None:
+                        d_extra_sparse = torch.empty((B, K2), device=dev, dtype=torch.float64)
+                        sp.score_rows_device(d_ptr, d_tok, B, len(q_tok), d_miss_sparse, K2, d_extra_sparse, s)
+                        extra.update(d_miss_sparse=d_miss_sparse, d_extra_sparse=d_extra_sparse)
+            # one block, one copy back: b, d, h (float64) | keys (int32) | count (int32)
+            n = B * k
+            block = torch.empty((7 * n + B,), device=dev, dtype=torch.int32)
+            scores = block[: 6 * n].view(torch.float64)
+            hm.fuse_device(d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B, K1, K2, k, block[6 * n: 7 * n], scores[:n], scores[n: 2 * n], scores[2 * n:],
+                           None, block[7 * n:], s, **extra)
+            host = block.cpu().numpy()
+        sc = host[: 6 * n].view(np.float64)
+        keys = host[6 * n: 7 * n].reshape(B, k)
+        return (ks["ids"][np.where(keys >= 0, keys, 0)], sc[:n].reshape(B, k), sc[n: 2 * n].reshape(B, k), sc[2 * n:].reshape(B, k),
+                host[7 * n:].astype(np.int64))
 
     def _fuse_batch_rows(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool = False):
         """`_fuse_columns` for every query of the batch at once, on integer keys: same candidates (union of both pools in first-seen
@@ -1654,6 +1781,8 @@ class HybridRetriever:
         bm, dn = self.bm25_index, self.dense_index
         if not (isinstance(bm, BM25Index) and isinstance(dn, DenseIndex)) or len(queries) == 0 or top_k <= 0:
             return None
+        if self._fuse_on_device(top_k, retrieval_pool_size):
+            return self._fuse_batch_device(list(queries), top_k, retrieval_pool_size, complete_scores)
         B = len(queries)
         ks = self._key_space()
         sp_rows, sp_scores = bm.search_batch_rows(list(queries), retrieval_pool_size, **self._sparse_kw())
@@ -1711,6 +1840,9 @@ class HybridRetriever:
         """Write the BM25 snapshot if documents were added since the last one (extension; the reference has no close)."""
         if self.bm25_index is not None and hasattr(self.bm25_index, "close"):
             self.bm25_index.close()
+        c = self.__dict__.pop("_keys_cache", None)
+        if c is not None and c.get("map") is not None:
+            c.pop("map").close()
 
     def __len__(self) -> int:
         return len(self.documents)

@@ -521,8 +521,16 @@ int rq_search_group_members(rq_index* idx, const rq_filter* f, const float* quer
  *   read-only "tile_ms_last" / "final_ms_last" then give the last call's time in the tile and in the final kernels, summed over its
  *   rounds; they wait for the device, -1 when the last call recorded none).  rq_sparse_get_option returns -1 with a message for
  *   an unknown name.
- * Not extended: allowed_ids filters, distinct_by, a device form of BM25Index.score_rows, multi-device handles, fusion of the sparse
- *   and dense lists on the device. */
+ * rq_sparse_score_rows_device: the BM25 score of named (query, row) pairs, the device form of BM25Index.score_rows_batch (what hybrid
+ *   fusion needs for a passage that only the dense retriever returned).  d_rows [B][m] int32, d_scores [B][m] float64,
+ *   position for position: the float64 sum of the contributions of the query's tokens whose posting list holds the row, with
+ *   repetition, added IN QUERY ORDER starting from 0.0 -- the bits of the corresponding entry of a full score vector.  A row outside
+ *   [0, n_docs), -1 included, scores 0.0 and reads nothing; rows may repeat.  Token ids and offsets get the clamping rules of
+ *   rq_sparse_topk_device.  One thread per pair, a binary search per token over that token's strictly ascending rows: no atomics, no
+ *   workspace, no synchronisation; complete in stream order.  RQ_EINVAL unless 1 <= B <= 65535, 1 <= m <= RQ_MAX_SCORE_ROWS and
+ *   non-null pointers.  rq_sparse_score_rows: blocking, host buffers, staged on the handle's stream like rq_sparse_topk, with its
+ *   checks of the queries.  Read-only option "score_calls" (both entry points).
+ * Not extended: allowed_ids filters, distinct_by, multi-device handles. */
 typedef struct rq_sparse rq_sparse;
 #define RQ_SPARSE_MAX_K 1024
 rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, const int32_t* rows, const double* contrib, int64_t n_tokens, int64_t n_docs);
@@ -531,8 +539,68 @@ int64_t rq_sparse_postings(const rq_sparse* h);
 int rq_sparse_topk(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, int32_t* out_rows, double* out_scores);
 int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
                           int32_t* d_rows, double* d_scores, void* stream);
+int rq_sparse_score_rows_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, const int32_t* d_rows,
+                                int m, double* d_scores, void* stream);
+int rq_sparse_score_rows(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, const int32_t* rows, int m, double* out_scores);
 int rq_sparse_set_option(rq_sparse* h, const char* name, double value);
 double rq_sparse_get_option(const rq_sparse* h, const char* name);
+
+/* ---- hybrid fusion: both pools of a batch fused on the device (the fusion of reference rag_uq/streaming_index.py:485-523 as
+ * HybridRetriever._fuse_batch_rows computes it for a whole batch, with its `complete_scores` rule) -----------------
+ * An rq_hybrid is an object of its own, beside rq_index and rq_sparse: the KEY SPACE that joins a sparse and a dense index.
+ *   keys 0 .. nb-1 are the sparse rows; dense row j has key dense_key[j]: a sparse row when BM25 holds the same document, else a
+ *     value >= nb.  Every key lies in [0, n_keys), nb <= n_keys < 2^31, and dense_key is INJECTIVE: rq_hybrid_create checks both on
+ *     the host and refuses otherwise.  known[key] (one byte per key, non-zero = the document store knows the key).  dense_row[key],
+ *     the inverse map (-1: no dense row), is derived by the library.  The three tables are COPIED to the device: 4 B per dense row +
+ *     5 B per key.
+ * Per query the inputs are a sparse pool [K1] (int32 rows, float64 scores, -1 padded: the output layout of rq_sparse_topk_device) and
+ *   a dense pool [K2] (int64 rows, fp32 scores, -1 padded: the output layout of rq_search_device, for an index with row offset 0).
+ *   0 <= K1 <= RQ_SPARSE_MAX_K, 0 <= K2 <= RQ_MAX_K, K1 + K2 >= 1 (a pool of width 0 needs no arrays).  A dense row outside
+ *   [0, n_dense) or a sparse row outside [0, nb) is absent.  Rows within one pool are distinct; this is not checked, as for
+ *   rq_mmr_select_device: a repeated row leaves that query's result unspecified, but it causes no read or write outside the arrays.
+ * Definition.  Candidates are the positions 0 .. K1+K2-1, sparse pool first; each has a key, b and d, both float64: the fp32 dense
+ *   score is widened, the missing side is 0.0.
+ *   valid = present and known[key].
+ *   a key in both pools: the sparse position takes the dense position's d, and the dense position becomes invalid.
+ *   missing rows (the `complete_scores` rule): for a valid sparse position without a dense score, miss_dense = dense_row[key] (it may
+ *     be -1); for a valid dense-only position with key < nb, miss_sparse = key; everything else is -1.  Where a miss entry is >= 0
+ *     and an extra score is supplied, the extra replaces the 0.0.
+ *   max_b and max_d are taken over the valid candidates; a NaN among them makes the maximum NaN.  The maximum is then replaced by 1.0
+ *     when it is 0, NaN or infinite (and when no candidate is valid).
+ *   h = (b / max_b + d / max_d) / 2 in float64: two divisions, one addition and one division by 2, each rounded, no fused
+ *     multiply-add.
+ *   order: h descending with -0.0 as +0.0; equal h by ascending candidate position.  A NaN h ranks as -inf, as every score in this
+ *     header, and is returned as it is.
+ *   output [B][top_k]: key (int32), b, d, h (float64), optionally the candidate position (int32: < K1 = the sparse pool);
+ *     count[B] = min(valid candidates, top_k); entries beyond count are (-1, 0.0, 0.0, 0.0), position -1.  1 <= top_k <= RQ_MAX_K.
+ *   Every key, position, count and score has the bits of tests/hybrid_oracle.py, which is the host path's arithmetic.
+ * rq_hybrid_missing_device: d_miss_dense [B][K1] int64 (feeds rq_score_rows_device, where -1 is "absent, 0.0"), d_miss_sparse
+ *   [B][K2] int32 (feeds rq_sparse_score_rows_device); either may be NULL when its K is 0.
+ * rq_hybrid_fuse_device: d_miss_dense / d_extra_dense [B][K1] fp32 / d_miss_sparse / d_extra_sparse [B][K2] float64 may all be NULL
+ *   (missing scores stay 0.0); an extra array without its miss array is RQ_EINVAL.  d_pos may be NULL.  One workgroup per query,
+ *   everything in LDS (at most 2 048 candidates, under 64 KiB), the kernel instantiated for the candidate count padded to a power of
+ *   two (64 .. 2 048).  Both device forms: no workspace, no synchronisation, complete in stream order.
+ * rq_hybrid_missing / rq_hybrid_fuse: blocking, host buffers, staged on a stream the handle owns.
+ * RQ_EINVAL for sizes outside the limits above, B outside 1 .. 65535 and null pointers; RQ_ENODEVICE as everywhere;
+ *   rq_hybrid_create: NULL with the message in rq_last_error(), NULL + the "no HIP device" message without a gfx950 device.  A handle
+ *   is used from one thread.  Read-only options (rq_hybrid_get_option, -1 with a message for an unknown name): "calls", "fuse_calls",
+ *   "missing_calls" (both entry points each), "nb", "n_dense", "n_keys".
+ * Not extended: MMR and grouping over the fused pool, filters, multi-device handles. */
+typedef struct rq_hybrid rq_hybrid;
+#define RQ_HYBRID_MAX_CAND 2048
+rq_hybrid* rq_hybrid_create(int device_id, int64_t nb, int64_t n_dense, const int64_t* dense_key, const uint8_t* known, int64_t n_keys);
+void rq_hybrid_destroy(rq_hybrid* h);
+double rq_hybrid_get_option(const rq_hybrid* h, const char* name);
+int rq_hybrid_missing_device(rq_hybrid* h, const int32_t* d_sp_rows, const int64_t* d_de_rows, int B, int K1, int K2, int64_t* d_miss_dense,
+                             int32_t* d_miss_sparse, void* stream);
+int rq_hybrid_missing(rq_hybrid* h, const int32_t* sp_rows, const int64_t* de_rows, int B, int K1, int K2, int64_t* miss_dense, int32_t* miss_sparse);
+int rq_hybrid_fuse_device(rq_hybrid* h, const int32_t* d_sp_rows, const double* d_sp_scores, const int64_t* d_de_rows, const float* d_de_scores, int B,
+                          int K1, int K2, const int64_t* d_miss_dense, const float* d_extra_dense, const int32_t* d_miss_sparse,
+                          const double* d_extra_sparse, int top_k, int32_t* d_keys, double* d_b, double* d_d, double* d_h, int32_t* d_pos,
+                          int32_t* d_count, void* stream);
+int rq_hybrid_fuse(rq_hybrid* h, const int32_t* sp_rows, const double* sp_scores, const int64_t* de_rows, const float* de_scores, int B, int K1, int K2,
+                   const int64_t* miss_dense, const float* extra_dense, const int32_t* miss_sparse, const double* extra_sparse, int top_k,
+                   int32_t* out_keys, double* out_b, double* out_d, double* out_h, int32_t* out_pos, int32_t* out_count);
 
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
