@@ -107,6 +107,9 @@ _SIGNATURES = {
     "rq_sparse_postings": (C.c_int64, [C.c_void_p]),
     "rq_sparse_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rq_sparse_topk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_sparse_topk_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_sparse_topk_masked_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_sparse_score_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rq_sparse_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "rq_hybrid_create": (C.c_void_p, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -218,6 +221,34 @@ def pack_row_mask(mask_or_rows, n_rows: int) -> np.ndarray:
     packed = np.packbits(mask, bitorder="little")
     packed = np.concatenate([packed, np.zeros((-packed.size) % 4, np.uint8)])        # whole uint32 words
     return np.ascontiguousarray(packed).view("<u4").astype(np.uint32)
+
+
+def mask_words(n_rows: int) -> int:
+    """uint32 words of one row mask over n_rows rows"""
+    return (int(n_rows) + 31) // 32
+
+
+def pack_row_masks(masks_or_rows, n_rows: int) -> np.ndarray:
+    """A mask table [n_masks][mask_words(n_rows)] uint32 for the masked sparse calls (include/rq.h rq_sparse_topk_masked,
+    include/rq_bm25.h rq_bm25_topk_masked): one `pack_row_mask` per entry -- the layout is the same bitmap."""
+    entries = list(masks_or_rows)
+    table = np.zeros((len(entries), mask_words(n_rows)), np.uint32)
+    for i, e in enumerate(entries):
+        table[i] = pack_row_mask(e, n_rows)
+    return table
+
+
+def _mask_args(what: str, masks, mask_of, B: int, n_docs: int) -> Tuple[Optional[np.ndarray], int, np.ndarray]:
+    """(masks or None, n_masks, mask_of) of a masked sparse call on host arrays, shapes checked here: the library cannot see them."""
+    mask_of = np.ascontiguousarray(mask_of, np.int32)
+    if mask_of.shape != (int(B),):
+        raise RqError(f"{what}: mask_of needs one entry per query: {B} queries, shape {mask_of.shape}")
+    if masks is None:
+        return None, 0, mask_of
+    masks = np.ascontiguousarray(masks, np.uint32)
+    if masks.ndim != 2 or masks.shape[1] != mask_words(n_docs):
+        raise RqError(f"{what}: masks must be [n_masks][{mask_words(n_docs)}] uint32 for {n_docs} documents, got shape {masks.shape}")
+    return (masks if masks.size else None), masks.shape[0], mask_of
 
 
 class RowFilter:
@@ -761,20 +792,38 @@ class SparseIndex:
         except Exception:
             pass
 
-    def topk(self, q_indptr, q_tokens, B: int, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        """Blocking, host arrays: (rows int32 [B][k], -1 padded; scores float64 [B][k], 0.0 padded)."""
+    def topk(self, q_indptr, q_tokens, B: int, k: int, *, masks=None, mask_of=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocking, host arrays: (rows int32 [B][k], -1 padded; scores float64 [B][k], 0.0 padded).  With `mask_of` (int32 [B]: the
+        mask of each query, -1 = unrestricted) and `masks` ([n_masks][mask_words(n_docs)] uint32, `pack_row_masks`; None when every
+        entry is -1) query q is answered over its allowed documents only (rq_sparse_topk_masked)."""
         q_indptr = np.ascontiguousarray(q_indptr, np.int64)
         q_tokens = np.ascontiguousarray(q_tokens, np.int32)
         if len(q_indptr) != int(B) + 1 or (int(B) >= 1 and len(q_tokens) < int(q_indptr[-1])):
             raise RqError(f"rq_sparse_topk: q_indptr holds {len(q_indptr)} entries for {B} queries, or names more tokens than q_tokens holds")
         out_rows = np.empty((max(int(B), 0), max(int(k), 0)), np.int32)
         out_scores = np.empty((max(int(B), 0), max(int(k), 0)), np.float64)
+        if masks is not None and mask_of is None:
+            raise RqError("rq_sparse_topk_masked: masks without mask_of")
+        if mask_of is not None:
+            masks, n_masks, mask_of = _mask_args("rq_sparse_topk_masked", masks, mask_of, B, self.n_docs)
+            _check(self._lib.rq_sparse_topk_masked(self._h, _ptr(q_indptr), _ptr(q_tokens) if len(q_tokens) else None, int(B), int(k), _ptr(masks), n_masks,
+                                                   _ptr(mask_of), _ptr(out_rows), _ptr(out_scores)), "rq_sparse_topk_masked")
+            return out_rows, out_scores
         _check(self._lib.rq_sparse_topk(self._h, _ptr(q_indptr), _ptr(q_tokens) if len(q_tokens) else None, int(B), int(k),
                                         _ptr(out_rows), _ptr(out_scores)), "rq_sparse_topk")
         return out_rows, out_scores
 
-    def topk_device(self, d_q_indptr, d_q_tokens, B: int, n_q_tokens: int, k: int, d_rows, d_scores, stream: int = 0) -> None:
-        """Asynchronous, device pointers (torch tensors or raw addresses): int64 [B + 1], int32 [n_q_tokens] -> int32 [B][k], float64 [B][k]."""
+    def topk_device(self, d_q_indptr, d_q_tokens, B: int, n_q_tokens: int, k: int, d_rows, d_scores, stream: int = 0, *,
+                    d_masks=None, n_masks: int = 0, d_mask_of=None) -> None:
+        """Asynchronous, device pointers (torch tensors or raw addresses): int64 [B + 1], int32 [n_q_tokens] -> int32 [B][k], float64 [B][k].
+        With `d_mask_of` (int32 [B]) the masked call: `d_masks` uint32 [n_masks][mask_words(n_docs)] (rq_sparse_topk_masked_device)."""
+        if d_masks is not None and d_mask_of is None:
+            raise RqError("rq_sparse_topk_masked_device: d_masks without d_mask_of")
+        if d_mask_of is not None:
+            _check(self._lib.rq_sparse_topk_masked_device(self._h, _ptr(d_q_indptr), _ptr(d_q_tokens), int(B), int(n_q_tokens), int(k), _ptr(d_masks),
+                                                          int(n_masks), _ptr(d_mask_of), _ptr(d_rows), _ptr(d_scores), C.c_void_p(stream)),
+                   "rq_sparse_topk_masked_device")
+            return
         _check(self._lib.rq_sparse_topk_device(self._h, _ptr(d_q_indptr), _ptr(d_q_tokens), int(B), int(n_q_tokens), int(k), _ptr(d_rows),
                                                _ptr(d_scores), C.c_void_p(stream)), "rq_sparse_topk_device")
 
@@ -944,9 +993,12 @@ _BM25_SIGNATURES = {
     "rq_bm25_create": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
     "rq_bm25_destroy": (None, [C.c_void_p]),
     "rq_bm25_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "rq_bm25_topk_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int]),
     "rq_bm25_version": (C.c_char_p, []),
 }
 _bm25_lib: Optional[C.CDLL] = None
+_bm25_docs: dict = {}      # handle -> n_docs: the width of a mask table is checked against it (the library cannot see an array's length)
 
 
 def load_bm25_library() -> C.CDLL:
@@ -978,19 +1030,33 @@ def bm25_create(indptr: np.ndarray, rows: np.ndarray, contrib: np.ndarray, n_tok
     h = load_bm25_library().rq_bm25_create(_ptr(indptr), _ptr(rows), _ptr(contrib), int(n_tokens), int(n_docs))
     if not h:
         raise RqError("rq_bm25_create: malformed posting arrays")
+    _bm25_docs[h] = int(n_docs)
     return h
 
 
 def bm25_destroy(handle: int) -> None:
+    _bm25_docs.pop(handle, None)
     if handle and _bm25_lib is not None:
         _bm25_lib.rq_bm25_destroy(C.c_void_p(handle))
 
 
-def bm25_topk(handle: int, q_indptr: np.ndarray, q_tokens: np.ndarray, n_queries: int, k: int, n_threads: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+def bm25_topk(handle: int, q_indptr: np.ndarray, q_tokens: np.ndarray, n_queries: int, k: int, n_threads: int = 0, *, masks=None,
+              mask_of=None) -> Tuple[np.ndarray, np.ndarray]:
+    """`mask_of` (int32 [n_queries], -1 = unrestricted) with `masks` ([n_masks][mask_words(n_docs)] uint32; None when every entry is -1)
+    answers each query over its allowed documents only (rq_bm25_topk_masked)."""
     out_rows = np.empty((n_queries, k), np.int32)
     out_scores = np.empty((n_queries, k), np.float64)
     q_indptr = np.ascontiguousarray(q_indptr, np.int64)
     q_tokens = np.ascontiguousarray(q_tokens, np.int32)
+    if masks is not None and mask_of is None:
+        raise RqError("rq_bm25_topk_masked: masks without mask_of")
+    if mask_of is not None:
+        masks, n_masks, mask_of = _mask_args("rq_bm25_topk_masked", masks, mask_of, n_queries, _bm25_docs[handle])
+        rc = load_bm25_library().rq_bm25_topk_masked(C.c_void_p(handle), _ptr(q_indptr), _ptr(q_tokens) if len(q_tokens) else None, int(n_queries), int(k),
+                                                     _ptr(masks), n_masks, _ptr(mask_of), _ptr(out_rows), _ptr(out_scores), int(n_threads))
+        if rc != 0:
+            raise RqError(f"rq_bm25_topk_masked failed (code {rc})")
+        return out_rows, out_scores
     rc = load_bm25_library().rq_bm25_topk(C.c_void_p(handle), _ptr(q_indptr), _ptr(q_tokens) if len(q_tokens) else None, int(n_queries), int(k),
                                           _ptr(out_rows), _ptr(out_scores), int(n_threads))
     if rc != 0:

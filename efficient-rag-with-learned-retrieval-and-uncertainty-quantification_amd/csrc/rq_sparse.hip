@@ -12,6 +12,20 @@
 // exactly (rq_sparse_select.h) and written, in any order, to the tile's slot of the workspace with their count.
 // rq_sparse_final_kernel, one workgroup per query: the best k of the tiles' candidates by the same selection body, sorted best first
 // with ties by descending row (the keys are unique: the result does not depend on the order of the slots), then the padding.
+//
+// Masked calls (rq_sparse_topk_masked*) run rq_sparse_tile_kernel<true>: query q of the CALL answers under mask
+// mask_of[q] ([W] uint32 words, bit r % 32 of word r / 32 = row r is allowed; -1: unrestricted, anything else outside
+// [0, n_masks): nothing is allowed).  The mask enters in two places and nowhere else:
+//   (a) before any posting is looked up, the workgroup ORs the mask words of its tile (tile_docs is a power of two >= 64: a tile starts
+//       on a word boundary and has at most 256 words, one load per thread; the last word of the ragged last tile is cut at n_docs).  A
+//       tile in which no document is allowed leaves with count 0 and is counted in `masked`, not in `skipped`.
+//   (b) after the accumulation and before anything is counted or selected, the accumulators of the disallowed documents are set to 0.0
+//       in one pass.  The positives count, the threshold and the candidate write below it then all see the same masked set -- a count
+//       taken before the mask and a selection after it would write fewer candidates than `want` and leave garbage in the slot.
+//   Bit exactness: the accumulation is untouched -- the same additions in the same order on every touched document, allowed or not --
+//   so an allowed document's score has the bits of the unmasked call, and a disallowed one is exactly the 0.0 that
+//   np.where(keep, scores, 0.0) writes before the score > 0 selection of the host definition.
+// The unmasked instantiation holds none of this (if constexpr): its code, counters and launches are those of the call before masks.
 #include "rq_sparse_plan.h"
 #include "rq_sparse_select.h"
 #include "rq_sparse_handle.h"
@@ -31,6 +45,12 @@ struct SparseArgs {
     int32_t* cand_rows;
     int32_t* counts;            // [queries of the round][tiles]
     unsigned long long* skipped;
+    // masked calls only (rq_sparse_tile_kernel<true>)
+    const uint32_t* masks;      // [n_masks][mask_words]
+    const int32_t* mask_of;     // [B] of the whole call
+    int n_masks;
+    int64_t mask_words;         // ceil(n_docs / 32)
+    unsigned long long* masked; // tiles that left because their mask allows no document
     int32_t* out_rows;          // [B][k] of the whole call
     double* out_scores;
 };
@@ -59,6 +79,7 @@ struct SparseTileSrc {
     }
 };
 
+template <bool MASKED>
 __global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_tile_kernel(SparseArgs a) {
     extern __shared__ double s_acc[];   // [tile_docs]
     __shared__ int64_t s_lo[RQ_SPARSE_CHUNK], s_hi[RQ_SPARSE_CHUNK];
@@ -70,6 +91,30 @@ __global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_tile_kernel(Spars
     const int64_t tile_lo = tile * (int64_t)a.tile_docs;
     const int64_t tile_hi = tile_lo + a.tile_docs < a.n_docs ? tile_lo + a.tile_docs : a.n_docs;
     const int nloc = (int)(tile_hi - tile_lo);
+    const uint32_t* mask = nullptr;   // the mask words of this tile; null: the query is unrestricted
+    uint32_t mask_w = 0;              // word tid of them, cut at n_docs (threads beyond the tile's words: 0)
+    if constexpr (MASKED) {
+        // mask_of is indexed by the query's position in the CALL.  The array may be the caller's device memory: a value outside
+        // [-1, n_masks) allows nothing and reads no mask (the manner of the token clamping below).
+        const int m = a.mask_of[a.q0 + ql];
+        if (m != -1) {
+            const int nw = (nloc + 31) >> 5;   // <= tile_docs / 32 <= 256; tile_lo / 32 + nw <= mask_words as tile_hi <= n_docs
+            if (m >= 0 && m < a.n_masks) {
+                mask = a.masks + (size_t)m * (size_t)a.mask_words + (size_t)(tile_lo >> 5);
+                if (tid < nw) {
+                    mask_w = mask[tid];
+                    if (tid == nw - 1 && (nloc & 31)) mask_w &= (1u << (nloc & 31)) - 1u;   // bits at or beyond n_docs are ignored
+                }
+            }
+            if (!__syncthreads_or(mask_w != 0)) {   // no document of the tile is allowed
+                if (tid == 0) {
+                    a.counts[(size_t)ql * (size_t)a.tiles + (size_t)tile] = 0;
+                    atomicAdd(a.masked, 1ull);
+                }
+                return;
+            }
+        }
+    }
     // the query's tokens; the arrays may be the caller's device memory, which no host check has seen: stay inside [0, n_q_tokens)
     int64_t t0 = a.q_indptr[a.q0 + ql], t1 = a.q_indptr[a.q0 + ql + 1];
     t0 = t0 < 0 ? 0 : (t0 > a.n_q_tokens ? a.n_q_tokens : t0);
@@ -110,6 +155,17 @@ __global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_tile_kernel(Spars
             atomicAdd(a.skipped, 1ull);
         }
         return;
+    }
+    if constexpr (MASKED) {
+        // (b): a disallowed document scores 0.0 from here on (the barrier below orders this pass before every reader).  The words come
+        // from the registers of (a) through s_lo, which is free since the loop's last barrier: no second trip to global memory.
+        if (mask) {
+            uint32_t* s_words = reinterpret_cast<uint32_t*>(s_lo);   // RQ_SPARSE_THREADS words of the 2 x RQ_SPARSE_CHUNK it holds
+            s_words[tid] = mask_w;
+            __syncthreads();
+            for (int i = tid; i < nloc; i += RQ_SPARSE_THREADS)
+                if (!((s_words[i >> 5] >> (i & 31)) & 1u)) s_acc[i] = 0.0;
+        }
     }
     const SparseTileSrc src{s_acc, nloc, (uint32_t)tile_lo};
     if (tid == 0) s_n = 0;
@@ -217,7 +273,7 @@ __global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_final_kernel(Spar
 static void sparse_free(rq_sparse* h) {
     if (h->own) (void)hipStreamDestroy(h->own);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    free_dev(h->d_indptr, h->d_rows, h->d_contrib, h->ws, h->d_skipped);
+    free_dev(h->d_indptr, h->d_rows, h->d_contrib, h->ws, h->d_skipped);   // (d_skipped holds both tile counters)
     delete h;
 }
 
@@ -239,7 +295,7 @@ extern "C" rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, con
     h->n_docs = n_docs;
     h->nnz = indptr[n_tokens];
     const size_t nnz = (size_t)h->nnz, pad = nnz ? nnz : 1;   // (empty lists: the kernels still get valid pointers)
-    if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&h->d_skipped, sizeof(unsigned long long)) != hipSuccess ||
+    if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&h->d_skipped, 2 * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc((void**)&h->d_indptr, (size_t)(n_tokens + 1) * 8) != hipSuccess || hipMalloc((void**)&h->d_rows, pad * 4) != hipSuccess ||
         hipMalloc((void**)&h->d_contrib, pad * 8) != hipSuccess) {
         (void)hipGetLastError();
@@ -249,8 +305,9 @@ extern "C" rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, con
     }
     if (hipMemcpy(h->d_indptr, indptr, (size_t)(n_tokens + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
         (nnz && (hipMemcpy(h->d_rows, rows, nnz * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(h->d_contrib, contrib, nnz * 8, hipMemcpyHostToDevice) != hipSuccess)) ||
-        hipMemset(h->d_skipped, 0, sizeof(unsigned long long)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)rq_sparse_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RQ_SPARSE_TILE_MAX * (int)sizeof(double)) != hipSuccess) {
+        hipMemset(h->d_skipped, 0, 2 * sizeof(unsigned long long)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)rq_sparse_tile_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, RQ_SPARSE_TILE_MAX * (int)sizeof(double)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)rq_sparse_tile_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, RQ_SPARSE_TILE_MAX * (int)sizeof(double)) != hipSuccess) {
         set_err(RQ_EHIP, "upload of the posting index to device %d failed", device_id);
         sparse_free(h);
         return nullptr;
@@ -267,9 +324,9 @@ extern "C" void rq_sparse_destroy(rq_sparse* h) {
 
 extern "C" int64_t rq_sparse_postings(const rq_sparse* h) { return h ? h->nnz : 0; }
 
-extern "C" int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
-                                     int32_t* d_rows, double* d_scores, void* stream) {
-    if (int rc = sparse_check_call(h, d_q_indptr, B, k, d_rows, d_scores)) return rc;
+// Both device forms: d_mask_of == nullptr is the unmasked call.
+static int sparse_topk_launch(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
+                              const uint32_t* d_masks, int n_masks, const int32_t* d_mask_of, int32_t* d_rows, double* d_scores, void* stream) {
     if (n_q_tokens < 0 || (n_q_tokens > 0 && !d_q_tokens)) return set_err(RQ_EINVAL, "n_q_tokens %lld negative, or tokens without an array", (long long)n_q_tokens);
     RQ_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
@@ -284,7 +341,7 @@ extern "C" int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, co
         }
         h->ws_bytes = p.bytes();
     }
-    HIPCHK(hipMemsetAsync(h->d_skipped, 0, sizeof(unsigned long long), s));
+    HIPCHK(hipMemsetAsync(h->d_skipped, 0, 2 * sizeof(unsigned long long), s));   // both tile counters
     SparseArgs a;
     a.indptr = h->d_indptr; a.rows = h->d_rows; a.contrib = h->d_contrib;
     a.n_tokens = h->n_tokens; a.n_docs = h->n_docs; a.tiles = p.tiles;
@@ -294,6 +351,9 @@ extern "C" int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, co
     a.cand_rows = (int32_t*)(h->ws + p.rows_offset());
     a.counts = (int32_t*)(h->ws + p.counts_offset());
     a.skipped = h->d_skipped;
+    a.masks = d_masks; a.mask_of = d_mask_of; a.n_masks = n_masks;
+    a.mask_words = sparse_mask_words(h->n_docs);
+    a.masked = h->d_skipped + 1;
     a.out_rows = d_rows; a.out_scores = d_scores;
     h->ev_used = 0;
     const size_t n_ev = h->profile ? 1 + 2 * (size_t)p.rounds : 0;
@@ -306,7 +366,10 @@ extern "C" int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, co
     for (int r = 0; r < p.rounds; ++r) {   // the rounds share the workspace: stream order keeps them apart
         a.q0 = p.round_first(r);
         const SparseGrid g = sparse_grid(p, h->tile_docs, p.round_count(r, B));
-        if (p.tiles > 0) hipLaunchKernelGGL(rq_sparse_tile_kernel, dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
+        if (p.tiles > 0) {
+            if (d_mask_of) hipLaunchKernelGGL(rq_sparse_tile_kernel<true>, dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
+            else hipLaunchKernelGGL(rq_sparse_tile_kernel<false>, dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
+        }
         if (n_ev) HIPCHK(hipEventRecord(h->ev[1 + 2 * (size_t)r], s));
         hipLaunchKernelGGL(rq_sparse_final_kernel, dim3(g.final_x), dim3(g.block), 0, s, a);
         if (n_ev) HIPCHK(hipEventRecord(h->ev[2 + 2 * (size_t)r], s));
@@ -314,9 +377,24 @@ extern "C" int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, co
     h->ev_used = n_ev;
     HIPCHK(hipGetLastError());
     h->calls++;
+    if (d_mask_of) h->masked_calls++;
     h->rounds_last = p.rounds;
     h->tiles_last = p.tiles * (int64_t)B;
     return RQ_OK;
+}
+
+extern "C" int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
+                                     int32_t* d_rows, double* d_scores, void* stream) {
+    if (int rc = sparse_check_call(h, d_q_indptr, B, k, d_rows, d_scores)) return rc;
+    return sparse_topk_launch(h, d_q_indptr, d_q_tokens, B, n_q_tokens, k, nullptr, 0, nullptr, d_rows, d_scores, stream);
+}
+
+extern "C" int rq_sparse_topk_masked_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
+                                            const uint32_t* d_masks, int n_masks, const int32_t* d_mask_of, int32_t* d_rows, double* d_scores,
+                                            void* stream) {
+    if (int rc = sparse_check_call(h, d_q_indptr, B, k, d_rows, d_scores)) return rc;
+    if (int rc = sparse_check_masks(d_masks, n_masks, d_mask_of)) return rc;
+    return sparse_topk_launch(h, d_q_indptr, d_q_tokens, B, n_q_tokens, k, d_masks, n_masks, d_mask_of, d_rows, d_scores, stream);
 }
 
 extern "C" int rq_sparse_topk(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, int32_t* out_rows, double* out_scores) {
@@ -332,6 +410,33 @@ extern "C" int rq_sparse_topk(rq_sparse* h, const int64_t* q_indptr, const int32
     if (nq) st.up(st.at<void>(1), q_tokens, (size_t)nq * 4);
     if (st.code() != RQ_OK) return st.code();
     const int rc = rq_sparse_topk_device(h, st.at<int64_t>(0), st.at<int32_t>(1), B, nq, k, st.at<int32_t>(2), st.at<double>(3), (void*)h->own);
+    st.launched();
+    if (rc != RQ_OK) return rc;
+    st.down(out_rows, st.at<void>(2), bytes[2]);
+    st.down(out_scores, st.at<void>(3), bytes[3]);
+    return st.finish();
+}
+
+extern "C" int rq_sparse_topk_masked(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, const uint32_t* masks, int n_masks,
+                                     const int32_t* mask_of, int32_t* out_rows, double* out_scores) {
+    if (int rc = sparse_check_call(h, q_indptr, B, k, out_rows, out_scores)) return rc;
+    if (int rc = sparse_check_queries(q_indptr, q_tokens, B, h->n_tokens)) return rc;
+    if (int rc = sparse_check_masks(masks, n_masks, mask_of)) return rc;
+    if (int rc = sparse_check_mask_of(mask_of, B, n_masks)) return rc;
+    RQ_ON_DEVICE(h);
+    const int64_t nq = q_indptr[B];
+    const size_t mask_bytes = (size_t)n_masks * (size_t)sparse_mask_words(h->n_docs) * 4;
+    const size_t bytes[6] = {(size_t)(B + 1) * 8, (size_t)(nq ? nq : 1) * 4, (size_t)B * (size_t)k * 4, (size_t)B * (size_t)k * 8,
+                             mask_bytes ? mask_bytes : 4, (size_t)B * 4};
+    Stage st(h->own);
+    if (st.alloc(bytes, 6, "rq_sparse_topk_masked") != RQ_OK) return st.code();
+    st.up(st.at<void>(0), q_indptr, bytes[0]);
+    if (nq) st.up(st.at<void>(1), q_tokens, (size_t)nq * 4);
+    if (mask_bytes) st.up(st.at<void>(4), masks, mask_bytes);
+    st.up(st.at<void>(5), mask_of, bytes[5]);
+    if (st.code() != RQ_OK) return st.code();
+    const int rc = rq_sparse_topk_masked_device(h, st.at<int64_t>(0), st.at<int32_t>(1), B, nq, k, st.at<uint32_t>(4), n_masks, st.at<int32_t>(5),
+                                                st.at<int32_t>(2), st.at<double>(3), (void*)h->own);
     st.launched();
     if (rc != RQ_OK) return rc;
     st.down(out_rows, st.at<void>(2), bytes[2]);
@@ -363,14 +468,16 @@ extern "C" double rq_sparse_get_option(const rq_sparse* h, const char* name) {
     if (!strcmp(name, "tile_docs")) return (double)h->tile_docs;
     if (!strcmp(name, "cand_cap")) return (double)h->cand_cap;
     if (!strcmp(name, "calls")) return (double)h->calls;
+    if (!strcmp(name, "masked_calls")) return (double)h->masked_calls;
     if (!strcmp(name, "score_calls")) return (double)h->score_calls;
     if (!strcmp(name, "rounds_last")) return (double)h->rounds_last;
     if (!strcmp(name, "tiles_last")) return (double)h->tiles_last;
-    if (!strcmp(name, "skipped_tiles_last")) {   // waits for the device
+    const bool masked_tiles = !strcmp(name, "masked_tiles_last");
+    if (masked_tiles || !strcmp(name, "skipped_tiles_last")) {   // waits for the device
         DeviceGuard dg_(h->device);
         unsigned long long v = 0;
-        if (!dg_.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, h->d_skipped, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
-            set_err(RQ_EHIP, "cannot read the skipped-tile counter");
+        if (!dg_.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, h->d_skipped + (masked_tiles ? 1 : 0), sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
+            set_err(RQ_EHIP, "cannot read the %s-tile counter", masked_tiles ? "masked" : "skipped");
             return -1.0;
         }
         return (double)v;

@@ -12,10 +12,11 @@ struct rq_sparse {
     hipStream_t own = nullptr;
     char* ws = nullptr;                   // the one workspace (rq_sparse_plan.h SparsePlan)
     size_t ws_bytes = 0;
-    unsigned long long* d_skipped = nullptr;
+    unsigned long long* d_skipped = nullptr;   // [2]: tiles of the last call without a posting, tiles whose mask allows no document
     int tile_docs = RQ_SPARSE_TILE_DEFAULT;
     int64_t cand_cap = 0;
     int64_t calls = 0, rounds_last = 0, tiles_last = 0;
+    int64_t masked_calls = 0;             // rq_sparse_topk_masked* (counted in calls too)
     int64_t score_calls = 0;              // rq_sparse_score_rows* (csrc/rq_hybrid.hip)
     // option "profile": HIP events before a call's first launch and after every launch; "tile_ms_last" / "final_ms_last" sum them
     int profile = 0;

@@ -1,4 +1,4 @@
-// rq_sparse_plan.h -- the host side of a sparse (BM25) top-k call (include/rq.h rq_sparse_create, rq_sparse_topk, rq_sparse_topk_device)
+// rq_sparse_plan.h -- the host side of a sparse (BM25) top-k call (include/rq.h rq_sparse_create, rq_sparse_topk*, rq_sparse_topk_masked*)
 // that needs no device: the validation of the posting arrays and of a call's arguments, the tiles of the corpus, the launch grids, the
 // workspace bytes and the cut of a call into rounds of queries.  Plain arithmetic in the manner of rq_score_plan.h and
 // rq_filter_each_plan.h: no HIP runtime call, nothing is written anywhere (tests/native/sparse_plan_check.cpp runs it on the host).
@@ -50,6 +50,21 @@ static inline int sparse_check_queries(const int64_t* q_indptr, const int32_t* q
     if (q_indptr[B] > 0 && !q_tokens) return set_err(RQ_EINVAL, "null q_tokens");
     for (int64_t t = q_indptr[0]; t < q_indptr[B]; ++t)
         if (q_tokens[t] < 0 || (int64_t)q_tokens[t] >= n_tokens) return set_err(RQ_EINVAL, "token id %d outside 0..%lld", q_tokens[t], (long long)n_tokens - 1);
+    return RQ_OK;
+}
+
+// Masks of the masked calls (rq_sparse_topk_masked*): [n_masks][sparse_mask_words(n_docs)] uint32, bit r % 32 of word r / 32 = row r
+// is allowed (the layout of rq_filter_create's bitmap).  Both forms: no table is legal when every query is unrestricted.
+static inline int64_t sparse_mask_words(int64_t n_docs) { return (n_docs + 31) / 32; }
+static inline int sparse_check_masks(const void* masks, int n_masks, const void* mask_of) {
+    if (!mask_of) return set_err(RQ_EINVAL, "null mask_of");
+    if (n_masks < 0 || (n_masks > 0 && !masks)) return set_err(RQ_EINVAL, "n_masks %d negative, or masks without an array", n_masks);
+    return RQ_OK;
+}
+// The host form sees mask_of: every entry is -1 (unrestricted) or a mask of the table.
+static inline int sparse_check_mask_of(const int32_t* mask_of, int B, int n_masks) {
+    for (int q = 0; q < B; ++q)
+        if (mask_of[q] < -1 || mask_of[q] >= n_masks) return set_err(RQ_EINVAL, "mask_of[%d] is %d, outside -1..%d", q, mask_of[q], n_masks - 1);
     return RQ_OK;
 }
 

@@ -138,6 +138,19 @@ def _group_value(doc: "Document", key: str):
     return _meta_group_value({"title": doc.title or "", **(doc.metadata or {})}, key)
 
 
+class SparseMask:
+    """The BM25 rows of one set of ids as mask words (`BM25Index.make_mask`; include/rq_bm25.h rq_bm25_topk_masked: bit r % 32 of
+    word r / 32 = row r is allowed).  It describes the corpus as it is now: adding documents makes it stale."""
+
+    __slots__ = ("words", "n_docs", "count")
+
+    def __init__(self, words: np.ndarray, n_docs: int, count: int):
+        self.words, self.n_docs, self.count = words, int(n_docs), int(count)
+
+    def __len__(self) -> int:
+        return self.count
+
+
 # =============================================================================================
 # sparse side (reference :92-225).  CPU, host logic.
 # =============================================================================================
@@ -464,8 +477,41 @@ class BM25Index:
             q_ptr.append(len(q_tok))
         return q_ptr, q_tok
 
+    # ---- one allowed set per query (extension: the batch form of `search(..., allowed_ids=)`; include/rq.h rq_sparse_topk_masked) ----
+    def make_mask(self, ids) -> SparseMask:
+        """A reusable mask that restricts batch searches to the passages with these ids (`allowed_ids=` / `allowed_ids_each=` accept
+        it as well as the ids themselves).  Ids map to rows through `_row_of_id()`, exactly as in `search`; unknown ids are ignored."""
+        n = len(self.doc_ids)
+        row_of = self._row_of_id()
+        rows = sorted({r for r in (row_of.get(d) for d in ids) if r is not None})
+        return SparseMask(_native.pack_row_mask(np.asarray(rows, np.int64), n), n, len(rows))
+
+    def _mask_entries(self, n_queries: int, allowed_ids=None, allowed_ids_each=None) -> Optional[list]:
+        """The two filter keywords of a batch call as one entry per query (ids, a `make_mask` result, or None), or None without either."""
+        if allowed_ids_each is not None:
+            return DenseIndex._each_entries(allowed_ids_each, n_queries, allowed_ids)
+        return None if allowed_ids is None else [allowed_ids] * int(n_queries)
+
+    def _mask_table(self, entries: list) -> Tuple[Optional[np.ndarray], np.ndarray]:
+        """(masks uint32 [n_masks][words] or None, mask_of int32 [B]) of one batch: one mask per distinct entry OBJECT, -1 for None."""
+        n = len(self.doc_ids)
+        slot: Dict[int, int] = {}
+        words: List[np.ndarray] = []
+        mask_of = np.full(len(entries), -1, np.int32)
+        for q, e in enumerate(entries):
+            if e is None:
+                continue
+            if id(e) not in slot:
+                m = e if isinstance(e, SparseMask) else self.make_mask(e)
+                if m.n_docs != n:
+                    raise _native.RqError(f"the sparse mask is stale: made over {m.n_docs} passages, the index holds {n}")
+                slot[id(e)] = len(words)
+                words.append(m.words)
+            mask_of[q] = slot[id(e)]
+        return (np.stack(words) if words else None), mask_of
+
     def search_batch_rows(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None,
-                          backend: str = "host") -> Tuple[np.ndarray, np.ndarray]:
+                          backend: str = "host", allowed_ids=None, allowed_ids_each=None) -> Tuple[np.ndarray, np.ndarray]:
         """The selection of `search` for a whole batch, in ROW space: (rows int32 [B][top_k], -1 padded; scores float64 [B][top_k]).
         librq_bm25.so (include/rq_bm25.h) walks the posting lists of every query on the host cores -- term at a time, one float64
         accumulator per thread, the contributions added in query order (the same additions as get_scores: identical bits), top-k by a
@@ -473,28 +519,41 @@ class BM25Index:
         scored with numpy, one query at a time.
         `backend`: "host" (default) is the path above; "gpu" scores and selects on the device (include/rq.h rq_sparse_topk, a
         `_native.SparseIndex` over the same arrays: the same rows and the same score bits; top_k <= 1024, at most 65 535 queries;
-        RqError without a device); "auto" takes the device when one is visible and the host otherwise."""
+        RqError without a device); "auto" takes the device when one is visible and the host otherwise.
+        `allowed_ids` (ids or a `make_mask` result: one set for the whole batch) and `allowed_ids_each` (one such entry, or None for
+        an unrestricted query, per query; entries that are the same object become one mask): query q is answered as
+        `search(q, top_k, allowed_ids=entry)` answers it -- scored as ever, every passage outside its set then scores 0.0 before the
+        selection -- under every backend and on the numpy branch (rq_bm25_topk_masked, rq_sparse_topk_masked).  The two do not combine."""
         if backend not in ("host", "gpu", "auto"):
             raise ValueError(f"backend must be 'host', 'gpu' or 'auto', not {backend!r}")
         B, k = len(queries), max(int(top_k), 1)
+        entries = self._mask_entries(B, allowed_ids, allowed_ids_each)
         if self.bm25 is None or not self.doc_ids or top_k <= 0 or B == 0:
             return np.full((B, k), -1, np.int32), np.zeros((B, k))
+        masked = {}
+        if entries is not None:
+            masks, mask_of = self._mask_table(entries)
+            masked = {"masks": masks, "mask_of": mask_of}
         c = self._csr()
         q_ptr, q_tok = self._query_csr(c, queries)
         if backend == "gpu" or (backend == "auto" and _native.sparse_available()):
-            return self._sparse_index(c).topk(np.asarray(q_ptr, np.int64), np.asarray(q_tok, np.int32), B, k)
+            return self._sparse_index(c).topk(np.asarray(q_ptr, np.int64), np.asarray(q_tok, np.int32), B, k, **masked)
         if use_native and c["handle"] is None:
             raise _native.RqError("librq_bm25.so is not built: `make -C csrc` (or use_native=False for the numpy path)")
         native = c["handle"] is not None if use_native is None else (use_native and c["handle"] is not None)
         if native:
-            return _native.bm25_topk(c["handle"], np.asarray(q_ptr, np.int64), np.asarray(q_tok, np.int32), B, k, n_threads)
+            return _native.bm25_topk(c["handle"], np.asarray(q_ptr, np.int64), np.asarray(q_tok, np.int32), B, k, n_threads, **masked)
         indptr, rows, contrib = c["indptr"], c["rows"], c["contrib"]
         out_rows, out_scores = np.full((B, k), -1, np.int32), np.zeros((B, k))
+        n = len(self.doc_ids)
+        keep = [] if not masked or masks is None else [np.unpackbits(m.view(np.uint8), bitorder="little")[:n].astype(bool) for m in masks]
         for b in range(B):
             scores = np.zeros(len(self.doc_ids))
             for j in q_tok[q_ptr[b]: q_ptr[b + 1]]:
                 lo, hi = indptr[j], indptr[j + 1]
                 scores[rows[lo:hi]] += contrib[lo:hi]
+            if masked and mask_of[b] >= 0:
+                scores = np.where(keep[mask_of[b]], scores, 0.0)
             sel = self._select_topk(scores, k)
             out_rows[b, :len(sel)] = sel
             out_scores[b, :len(sel)] = scores[sel]
@@ -509,11 +568,15 @@ class BM25Index:
         return cache
 
     def search_batch(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None,
-                     backend: str = "host") -> List[List[Tuple[str, float]]]:
-        """`[self.search(q, top_k) for q in queries]`, scored as one job (search_batch_rows; `backend` as there)."""
+                     backend: str = "host", allowed_ids=None, allowed_ids_each=None) -> List[List[Tuple[str, float]]]:
+        """`[self.search(q, top_k) for q in queries]`, scored as one job (search_batch_rows; `backend` as there).  With `allowed_ids`
+        (one set for the batch) or `allowed_ids_each` (one entry per query, None = unrestricted), as there:
+        `[self.search(q, top_k, allowed_ids=entry_q) for q in queries]`."""
+        given = _given(allowed_ids=allowed_ids, allowed_ids_each=allowed_ids_each)
         if self.bm25 is None or not self.doc_ids or top_k <= 0:
+            self._mask_entries(len(queries), allowed_ids, allowed_ids_each)      # (the keywords are still checked)
             return [[] for _ in queries]
-        out_rows, out_scores = self.search_batch_rows(queries, top_k, n_threads=n_threads, use_native=use_native, backend=backend)
+        out_rows, out_scores = self.search_batch_rows(queries, top_k, n_threads=n_threads, use_native=use_native, backend=backend, **given)
         idl = self._ids_array()[np.where(out_rows >= 0, out_rows, 0)].tolist()
         scl = out_scores.tolist()
         have = (out_rows >= 0).sum(axis=1).tolist()
@@ -1370,6 +1433,23 @@ class DenseIndex:
 # =============================================================================================
 # hybrid fusion (reference :376-560) -- pure host logic, kept semantically identical
 # =============================================================================================
+class HybridFilter:
+    """One allowed set on both sides of a HybridRetriever (`HybridRetriever.make_filter`): the ids, the sparse mask words over the
+    BM25 rows (`BM25Index.make_mask`) and a dense `RowFilter` (`DenseIndex.make_filter`); a side whose index held nothing has None.
+    The batch calls accept it wherever they take ids.  It is stale once either index has grown."""
+
+    def __init__(self, ids, sparse: Optional[SparseMask], dense, stamp: Tuple[int, int]):
+        self.ids, self.sparse, self.dense, self.stamp = frozenset(ids), sparse, dense, stamp
+
+    def close(self) -> None:
+        if self.dense is not None:
+            self.dense.close()
+            self.dense = None
+
+    def __len__(self) -> int:
+        return len(self.ids)
+
+
 class HybridRetriever:
     """Unified hybrid retrieval combining BM25 and dense retrieval (reference :376-560).
 
@@ -1379,6 +1459,7 @@ class HybridRetriever:
     batch calls fuse both pools with numpy on the host; "gpu": both pools stay in HBM and are fused there -- include/rq.h "hybrid
     fusion", the same values bit for bit -- and only [B][top_k] results come back; it needs `sparse_backend` "gpu" or "auto" and a
     single-device DenseIndex, and raises RqError with the reason otherwise; "auto": the device when all of that holds, else the host).
+    The batch calls take `allowed_ids=` / `allowed_ids_each=` (one allowed set per query; `make_filter` for reuse) under every backend.
     """
 
     def __init__(self, bm25_persist_path: str = "./data/bm25_index.pkl", chroma_persist_path: str = "./data/chroma_db",
@@ -1427,7 +1508,9 @@ class HybridRetriever:
     # `allowed_ids` (keyword-only extension on the per-query calls): only passages with these ids are ranked, on both sides -- the
     # `where` of a Chroma query.  The sparse side needs the ids themselves; the dense side also takes a DenseIndex.make_filter result.
     # `distinct_by` (keyword-only extension on the per-query calls, a metadata key such as "title"): one passage per value of that
-    # field on each side, and the fused list is collapsed once more by best hybrid score.  The `*_batch` fusions are not extended.
+    # field on each side, and the fused list is collapsed once more by best hybrid score.  It stays on the per-query calls.
+    # The `*_batch` calls take `allowed_ids` (one set for the batch) or `allowed_ids_each` (one entry per query: ids, a `make_filter`
+    # result, or None for an unrestricted query); query q's answer is that of the per-query call with that entry, value for value.
     # `per_group` (with `distinct_by`): `dense_search` alone passes it on (DenseIndex.search); the sparse side and the fused list
     # return one passage per group, and refuse any other value.
     def bm25_search(self, query: str, top_k: int = 20, *, allowed_ids=None, distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[Tuple[str, float]]:
@@ -1455,14 +1538,76 @@ class HybridRetriever:
             return []
         return [(doc_id, score) for doc_id, score, _ in self.dense_index.search_threshold(query, threshold, max_results, allowed_ids=allowed_ids)]
 
-    def dense_search_batch(self, queries: Sequence[str], top_k: int = 20) -> List[List[Tuple[str, float]]]:
+    def dense_search_batch(self, queries: Sequence[str], top_k: int = 20, *, allowed_ids=None, allowed_ids_each=None) -> List[List[Tuple[str, float]]]:
+        """`allowed_ids` / `allowed_ids_each`: ids, a `make_filter` result or -- this call has no sparse side -- a dense `RowFilter`."""
+        entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each, dense_only=True)
         if self.dense_index is None:
             return [[] for _ in queries]
-        if hasattr(self.dense_index, "search_batch"):
+        if entries is not None:
+            # the dense half of a hybrid filter, or the entry as it came (DenseIndex makes one filter per distinct object of ids)
+            each = [e if not isinstance(e, HybridFilter) else (list(e.ids) if self._checked(e).dense is None else e.dense) for e in entries]
+            if hasattr(self.dense_index, "search_batch"):
+                res = self.dense_index.search_batch(list(queries), top_k, allowed_ids_each=each)
+            else:
+                res = [self.dense_index.search(q, top_k, **_given(allowed_ids=e)) for q, e in zip(queries, each)]
+        elif hasattr(self.dense_index, "search_batch"):
             res = self.dense_index.search_batch(list(queries), top_k)
         else:
             res = [self.dense_index.search(q, top_k) for q in queries]
         return [[(d, s) for d, s, _ in r] for r in res]
+
+    # ---- one allowed set per query in the batch calls (extension; DESIGN.md 4.21) --------------------------------------------------
+    def _filter_stamp(self) -> Tuple[int, int]:
+        bm, dn = self.bm25_index, self.dense_index
+        return (len(bm.doc_ids) if isinstance(bm, BM25Index) else -1, len(dn._ids) if isinstance(dn, DenseIndex) else -1)
+
+    def make_filter(self, ids) -> HybridFilter:
+        """A reusable filter for the batch calls (`allowed_ids=` / `allowed_ids_each=` accept it wherever they take ids): the id set,
+        its mask over the BM25 rows and a dense `RowFilter`.  Unknown ids are ignored.  It describes both indexes as they are now:
+        once either has grown the calls refuse it as stale.  `close()` frees the dense filter."""
+        ids = list(ids)
+        bm, dn = self.bm25_index, self.dense_index
+        sparse = bm.make_mask(ids) if isinstance(bm, BM25Index) and bm.doc_ids else None
+        dense = dn.make_filter(ids) if isinstance(dn, DenseIndex) and dn._index is not None and len(dn._ids) else None
+        return HybridFilter(ids, sparse, dense, self._filter_stamp())
+
+    def _checked(self, flt: HybridFilter) -> HybridFilter:
+        if flt.stamp != self._filter_stamp():
+            raise _native.RqError(f"the hybrid filter is stale: made over {flt.stamp} (BM25, dense) passages, the indexes hold {self._filter_stamp()}")
+        return flt
+
+    def _filter_entries(self, n_queries: int, allowed_ids=None, allowed_ids_each=None, dense_only: bool = False) -> Optional[list]:
+        """The two filter keywords of a batch call as one entry per query (ids, a `make_filter` result, or None), or None without
+        either.  A bare dense RowFilter is refused by the hybrid calls: it says nothing about BM25 rows."""
+        if allowed_ids_each is not None:
+            entries = DenseIndex._each_entries(allowed_ids_each, n_queries, allowed_ids)
+        elif allowed_ids is not None:
+            entries = [allowed_ids] * int(n_queries)
+        else:
+            return None
+        if any(isinstance(e, SparseMask) or (isinstance(e, _native.RowFilter) and not dense_only) for e in entries):
+            raise ValueError("the hybrid batch calls take ids or a HybridRetriever.make_filter result: a dense RowFilter or a sparse mask covers one side only")
+        return entries
+
+    def _with_filters(self, entries: list, call):
+        """`call(filters)` with every entry a checked HybridFilter or None: a caller's own filter passes through; ids become a filter
+        made now -- one per distinct OBJECT -- and closed once the call has returned or raised (a filter's whole set-up and tear-down
+        per call: reuse a `make_filter` result for repeated questions)."""
+        made: Dict[int, HybridFilter] = {}
+        try:
+            filters = []
+            for e in entries:
+                if isinstance(e, HybridFilter):
+                    e = self._checked(e)
+                elif e is not None:
+                    if id(e) not in made:
+                        made[id(e)] = self.make_filter(e)
+                    e = made[id(e)]
+                filters.append(e)
+            return call(filters)
+        finally:
+            for flt in made.values():
+                flt.close()
 
     def _fuse_columns(self, bm25_list: List[Tuple[str, float]], dense_list: List[Tuple[str, float]], top_k: int, extra=None):
         """Reference :485-523 on parallel lists: union of both pools, ids unknown to `self.documents` dropped, missing score 0.0,
@@ -1560,11 +1705,19 @@ class HybridRetriever:
         given = _given(allowed_ids=None if allowed_ids is None else list(allowed_ids))      # (walked twice)
         return self._fuse(self.bm25_search(query, retrieval_pool_size, **given), self.dense_search(query, retrieval_pool_size, **given), top_k)
 
-    def hybrid_search_batch(self, queries: Sequence[str], top_k: int = 10, retrieval_pool_size: int = 50, *, complete_scores: bool = False
-                            ) -> List[List[RetrievalResult]]:
+    def hybrid_search_batch(self, queries: Sequence[str], top_k: int = 10, retrieval_pool_size: int = 50, *, complete_scores: bool = False,
+                            allowed_ids=None, allowed_ids_each=None) -> List[List[RetrievalResult]]:
         """All dense pools from one GPU batch, all BM25 pools from one pass over the posting lists on the host cores (librq_bm25.so);
-        fusion per query.  (`allowed_ids` is an extension of the per-query calls only: the batch fusions are not extended.)"""
-        fused = self._fuse_batch_rows(queries, top_k, retrieval_pool_size, complete_scores)
+        fusion per query.  `allowed_ids` (one set for the batch) / `allowed_ids_each` (one entry per query: ids, a `make_filter`
+        result, or None) restrict both pools of each query: the answer is `hybrid_search(q, ..., allowed_ids=entry_q)`, value for value,
+        from one masked BM25 call and one per-query-filtered dense call."""
+        entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
+        if entries is None:
+            return self._hybrid_search_batch(queries, top_k, retrieval_pool_size, complete_scores)
+        return self._with_filters(entries, lambda each: self._hybrid_search_batch(queries, top_k, retrieval_pool_size, complete_scores, each))
+
+    def _hybrid_search_batch(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None):
+        fused = self._fuse_batch_rows(queries, top_k, retrieval_pool_size, complete_scores, each)
         if fused is not None:
             ids, b, de, hy, count = fused
             idl, bl, dl, hl = ids.tolist(), b.tolist(), de.tolist(), hy.tolist()
@@ -1577,6 +1730,9 @@ class HybridRetriever:
                                                title=doc.title, metadata=doc.metadata))
                 out.append(res)
             return out
+        if each is not None:       # one side is not this module's own index class: the per-query calls
+            return [self.hybrid_search(q, top_k, retrieval_pool_size, complete_scores=complete_scores, allowed_ids=None if e is None else e.ids)
+                    for q, e in zip(queries, each)]
         if complete_scores:
             return [self.hybrid_search(q, top_k, retrieval_pool_size, complete_scores=True) for q in queries]
         dense, sparse = self._pools_batch(queries, retrieval_pool_size)
@@ -1614,11 +1770,19 @@ class HybridRetriever:
         given = _given(allowed_ids=allowed_ids, complete_scores=True if complete_scores else None)
         return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size, **given), num_passages)
 
-    def get_scores_for_router_batch(self, queries: Sequence[str], num_passages: int = 20, *, retrieval_pool_size: int = 50, complete_scores: bool = False):
-        """`[get_scores_for_router(q, ...) for q in queries]` (without `allowed_ids`: the batch fusions are not extended) with the pools of the whole batch computed at once.  When both sides are
+    def get_scores_for_router_batch(self, queries: Sequence[str], num_passages: int = 20, *, retrieval_pool_size: int = 50, complete_scores: bool = False,
+                                    allowed_ids=None, allowed_ids_each=None):
+        """`[get_scores_for_router(q, ...) for q in queries]` with the pools of the whole batch computed at once.  When both sides are
         this module's own indexes the fusion itself runs on the whole batch in row space (`_fuse_batch_rows`); otherwise per query on the
-        fused columns (no RetrievalResult objects in between)."""
-        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores)
+        fused columns (no RetrievalResult objects in between).  `allowed_ids` / `allowed_ids_each` as in `hybrid_search_batch`: query
+        q's answer is `get_scores_for_router(q, ..., allowed_ids=entry_q)`."""
+        entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
+        if entries is None:
+            return self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores)
+        return self._with_filters(entries, lambda each: self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, each))
+
+    def _scores_for_router_batch(self, queries: Sequence[str], num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None):
+        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores, each)
         if fused is not None:
             ids, b, de, _, count = fused
             ids[np.arange(num_passages)[None, :] >= count[:, None]] = ""
@@ -1626,6 +1790,9 @@ class HybridRetriever:
             documents = self.documents                      # (texts are read from the store at call time, as the per-query path does)
             texts = [[documents[d].text if d else "" for d in row] for row in idl]
             return list(zip(b.tolist(), de.tolist(), idl, texts))
+        if each is not None:       # one side is not this module's own index class: the per-query calls
+            return [self.get_scores_for_router(q, num_passages, retrieval_pool_size=retrieval_pool_size, complete_scores=complete_scores,
+                                               allowed_ids=None if e is None else e.ids) for q, e in zip(queries, each)]
         if complete_scores:
             return [self.get_scores_for_router(q, num_passages, retrieval_pool_size=retrieval_pool_size, complete_scores=True) for q in queries]
         dense, sparse = self._pools_batch(queries, retrieval_pool_size)
@@ -1703,10 +1870,13 @@ class HybridRetriever:
             ks["map"] = _native.HybridMap(ks["nb"], ks["dense_key"], ks["known"], device=device)
         return ks["map"]
 
-    def _fuse_batch_device(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool):
+    def _fuse_batch_device(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None):
         """`_fuse_batch_rows` with both pools left where they are drawn: token ids and query vectors go down, rq_sparse_topk_device and
         rq_search_device (with its fixup) fill the pools in HBM, `complete_scores` adds rq_hybrid_missing_device and the two row-scoring
-        calls, rq_hybrid_fuse_device ranks, and one copy brings [B][top_k] keys, scores and the counts back.  Same return value."""
+        calls, rq_hybrid_fuse_device ranks, and one copy brings [B][top_k] keys, scores and the counts back.  Same return value.
+        `each` (one HybridFilter or None per query): the mask table goes down once, rq_sparse_topk_masked_device and
+        rq_search_filtered_each_device (with its fixup; complete in stream order) fill the pools, the rest runs as it is -- pools that
+        are already filtered fuse as they are."""
         import torch
         bm, dn = self.bm25_index, self.dense_index
         B, k, K1 = len(queries), int(top_k), max(int(retrieval_pool_size), 1)
@@ -1725,7 +1895,13 @@ class HybridRetriever:
                 q_ptr, q_tok = bm._query_csr(c, queries)
                 d_ptr = torch.tensor(q_ptr, dtype=torch.int64).to(dev)
                 d_tok = torch.tensor(q_tok or [0], dtype=torch.int32).to(dev)
-                sp.topk_device(d_ptr, d_tok, B, len(q_tok), K1, d_sp_rows, d_sp_scores, stream=s)
+                masked = {}
+                if each is not None:
+                    masks, mask_of = bm._mask_table([None if e is None else e.sparse for e in each])
+                    # (torch has no arithmetic on uint32 and needs none: the words travel as int32)
+                    masked = {"d_masks": None if masks is None else torch.from_numpy(masks.view(np.int32)).to(dev),
+                              "n_masks": 0 if masks is None else len(masks), "d_mask_of": torch.from_numpy(mask_of).to(dev)}
+                sp.topk_device(d_ptr, d_tok, B, len(q_tok), K1, d_sp_rows, d_sp_scores, stream=s, **masked)
             else:
                 d_sp_rows.fill_(-1)
                 d_sp_scores.zero_()
@@ -1740,10 +1916,16 @@ class HybridRetriever:
                 d_de_rows = torch.empty((B, K2), device=dev, dtype=torch.int64)
                 d_de_scores = torch.empty((B, K2), device=dev, dtype=torch.float32)
                 d_status = torch.empty((B,), device=dev, dtype=torch.int32)
-                dn._index.search_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, s)
-                dn._index.search_flush_device(s)
-                if bool(d_status.any()):                                       # rare: a certificate failed -> exact repair on the device
-                    dn._index.search_fixup_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, s)
+                if each is not None:
+                    filters = [None if e is None else e.dense for e in each]
+                    dn._index.search_filtered_each_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, filters, s)
+                    if bool(d_status.any()):
+                        dn._index.search_filtered_each_fixup_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, filters, s)
+                else:
+                    dn._index.search_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, s)
+                    dn._index.search_flush_device(s)
+                    if bool(d_status.any()):                                   # rare: a certificate failed -> exact repair on the device
+                        dn._index.search_fixup_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, s)
             extra = {}
             if complete_scores:
                 d_miss_dense = torch.empty((B, K1), device=dev, dtype=torch.int64)
@@ -1769,7 +1951,7 @@ class HybridRetriever:
         return (ks["ids"][np.where(keys >= 0, keys, 0)], sc[:n].reshape(B, k), sc[n: 2 * n].reshape(B, k), sc[2 * n:].reshape(B, k),
                 host[7 * n:].astype(np.int64))
 
-    def _fuse_batch_rows(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool = False):
+    def _fuse_batch_rows(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool = False, each: Optional[list] = None):
         """`_fuse_columns` for every query of the batch at once, on integer keys: same candidates (union of both pools in first-seen
         order -- BM25 pool, then dense pool -- ids unknown to `self.documents` dropped), same float64 arithmetic (`max(...) or 1` over all
         candidates, hybrid = (b/max_b + d/max_d)/2), same stable descending sort, first top_k.  Returns (ids [B][top_k] object,
@@ -1777,16 +1959,27 @@ class HybridRetriever:
         is not this module's own index class (then the per-query path runs).
         `complete_scores`: after both pools are drawn and before the maxima are taken, ONE dense scoring call for the batch ([B][K1]
         dense rows of the BM25 pool, -1 where nothing is missing or no dense row exists) and one BM25 batch call for the dense-only
-        entries fill in the scores the reference leaves at 0.0; the queries are embedded once for the search and the scoring."""
+        entries fill in the scores the reference leaves at 0.0; the queries are embedded once for the search and the scoring.
+        `each` (one HybridFilter or None per query, from `_with_filters`): the sparse pool comes from the masked `search_batch_rows`,
+        the dense pool from ONE per-query-filtered call (`DenseIndex._search_rows(each=...)`) over vectors embedded on the host, as the
+        per-query filtered calls embed them; the rest is untouched -- a candidate comes from a filtered pool, its missing score is
+        the plain score of that pair."""
         bm, dn = self.bm25_index, self.dense_index
         if not (isinstance(bm, BM25Index) and isinstance(dn, DenseIndex)) or len(queries) == 0 or top_k <= 0:
             return None
         if self._fuse_on_device(top_k, retrieval_pool_size):
-            return self._fuse_batch_device(list(queries), top_k, retrieval_pool_size, complete_scores)
+            return self._fuse_batch_device(list(queries), top_k, retrieval_pool_size, complete_scores, each)
         B = len(queries)
         ks = self._key_space()
-        sp_rows, sp_scores = bm.search_batch_rows(list(queries), retrieval_pool_size, **self._sparse_kw())
-        if complete_scores:
+        sparse_each = {} if each is None else {"allowed_ids_each": [None if e is None else e.sparse for e in each]}
+        sp_rows, sp_scores = bm.search_batch_rows(list(queries), retrieval_pool_size, **self._sparse_kw(), **sparse_each)
+        if each is not None:
+            qv = dn._embed_queries(list(queries), host_only=True)
+            if dn._nothing_to_search(retrieval_pool_size, B):
+                de_scores, de_rows = dn._no_rows(B)
+            else:
+                de_scores, de_rows = dn._search_rows(qv[1], retrieval_pool_size, each=[None if e is None else e.dense for e in each])
+        elif complete_scores:
             qv = dn._embed_queries(list(queries))
             de_scores, de_rows = dn._search_embedded(qv, retrieval_pool_size)
         else:

@@ -508,6 +508,26 @@ int rq_search_group_members(rq_index* idx, const rq_filter* f, const float* quer
  * rq_sparse_topk_device: asynchronous, device pointers, no host synchronisation in steady state; results are complete in stream
  *   order.  n_q_tokens = the length of d_q_tokens.  The host cannot see the queries: a token id outside [0, n_tokens) is an EMPTY
  *   posting list, and an entry of d_q_indptr outside [0, n_q_tokens] or below its predecessor is clamped (no read outside the arrays).
+ * rq_sparse_topk_masked / rq_sparse_topk_masked_device: the same calls with one ALLOWED SET per query: the batch
+ *   form of BM25Index.search(..., allowed_ids=), behind the `allowed_ids` / `allowed_ids_each` keywords of the batch calls.
+ *   Definition: scores are added exactly as above; a document outside the query's allowed set then scores 0.0 BEFORE the score > 0
+ *     selection.  Query q's answer is therefore rq_sparse_topk's answer over its allowed documents alone -- every row, order, count
+ *     and score bit -- and that of rq_bm25_topk_masked (include/rq_bm25.h).  An empty set returns nothing.
+ *   Masks: `masks` is [n_masks][W] uint32, W = ceil(n_docs / 32); bit r % 32 of word r / 32 set = document row r is allowed (the
+ *     bitmap layout of rq_filter_create).  Bits at or beyond n_docs are ignored, whatever they hold.  mask_of[q] is the mask of query
+ *     q of the CALL, -1 = unrestricted; the same mask may serve any number of queries, in any arrangement.
+ *   Checks: those of rq_sparse_topk / rq_sparse_topk_device, and RQ_EINVAL for mask_of == NULL, n_masks < 0 and masks == NULL with
+ *     n_masks > 0 (n_masks == 0 without a table is legal when every entry is -1).  The blocking form sees mask_of and refuses an
+ *     entry outside [-1, n_masks) with RQ_EINVAL; the device form cannot, and treats such an entry as "allows nothing" (padding, no
+ *     read outside the arrays: the manner of the token clamping).  The device form reads d_masks and d_mask_of in stream order and
+ *     keeps neither.
+ *   Kernel: the tile kernel of rq_sparse_topk, instantiated with the mask in two places.  Before any posting is looked up a
+ *     workgroup ORs the mask words of its tile (at most 256 words, one load per thread, the ragged last tile cut at n_docs) and
+ *     leaves at once when no document is allowed; after the accumulation and before anything is counted or selected, the
+ *     accumulators of the disallowed documents are set to 0.0.  The accumulation itself, the final kernel, the workspace, the rounds,
+ *     "tile_docs", "cand_cap" and "profile" are those of the unmasked call, which keeps its code, counters and launch count.
+ *   Cost: that of the unmasked call, minus the tiles that leave early.  Out of scope: a gather route for selective masks (score only
+ *     the allowed rows with rq_sparse_score_rows_device, then select); whether it pays is a later measurement.
  * Workspace and threading: one workspace per handle, tiles x min(k, tile_docs) x 12 B + 4 B per tile for every query of a round.  A
  *   handle is used from one thread and its calls are ordered by the caller: one stream, or events between streams.  A call that
  *   needs a larger workspace than the handle has waits for the device once (hipDeviceSynchronize) and allocates; a call that fits
@@ -515,9 +535,10 @@ int rq_search_group_members(rq_index* idx, const rq_filter* f, const float* quer
  * Options (rq_sparse_set_option / rq_sparse_get_option; results never depend on them): "tile_docs" (documents per workgroup, a power
  *   of two in 64 .. 8192, default 4096: one float64 accumulator per document in LDS; settable any time), "cand_cap" (test hook:
  *   candidate bytes -- tiles x min(k, tile_docs) x 12 per query -- one round of queries may hold, 0 = default = 1 GiB; a call beyond it
- *   runs in rounds, a query beyond it alone in a round of its own); read-only "calls", "rounds_last", "tiles_last" (tiles x B of the
- *   last call), "skipped_tiles_last" (tiles of the last call in which no token of the query had a posting: they leave before any
- *   work; waits for the device); "profile" (measurement hook, default 0: 1 = every call records HIP events around its launches;
+ *   runs in rounds, a query beyond it alone in a round of its own); read-only "calls" (masked calls included), "masked_calls", "rounds_last", "tiles_last"
+ *   (tiles x B of the last call), "masked_tiles_last" (tiles of the last call whose mask allowed no document: exact, waits for the
+ *   device, 0 after an unmasked call), "skipped_tiles_last" (of the tiles that passed the mask, those in which no token of the query
+ *   had a posting: they leave before any work; waits for the device); "profile" (measurement hook, default 0: 1 = every call records HIP events around its launches;
  *   read-only "tile_ms_last" / "final_ms_last" then give the last call's time in the tile and in the final kernels, summed over its
  *   rounds; they wait for the device, -1 when the last call recorded none).  rq_sparse_get_option returns -1 with a message for
  *   an unknown name.
@@ -530,7 +551,7 @@ int rq_search_group_members(rq_index* idx, const rq_filter* f, const float* quer
  *   workspace, no synchronisation; complete in stream order.  RQ_EINVAL unless 1 <= B <= 65535, 1 <= m <= RQ_MAX_SCORE_ROWS and
  *   non-null pointers.  rq_sparse_score_rows: blocking, host buffers, staged on the handle's stream like rq_sparse_topk, with its
  *   checks of the queries.  Read-only option "score_calls" (both entry points).
- * Not extended: allowed_ids filters, distinct_by, multi-device handles. */
+ * Not extended: distinct_by (it stays on the host), multi-device handles. */
 typedef struct rq_sparse rq_sparse;
 #define RQ_SPARSE_MAX_K 1024
 rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, const int32_t* rows, const double* contrib, int64_t n_tokens, int64_t n_docs);
@@ -539,6 +560,10 @@ int64_t rq_sparse_postings(const rq_sparse* h);
 int rq_sparse_topk(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, int32_t* out_rows, double* out_scores);
 int rq_sparse_topk_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
                           int32_t* d_rows, double* d_scores, void* stream);
+int rq_sparse_topk_masked(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, const uint32_t* masks, int n_masks,
+                          const int32_t* mask_of, int32_t* out_rows, double* out_scores);
+int rq_sparse_topk_masked_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
+                                 const uint32_t* d_masks, int n_masks, const int32_t* d_mask_of, int32_t* d_rows, double* d_scores, void* stream);
 int rq_sparse_score_rows_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, const int32_t* d_rows,
                                 int m, double* d_scores, void* stream);
 int rq_sparse_score_rows(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, const int32_t* rows, int m, double* out_scores);
@@ -585,7 +610,8 @@ double rq_sparse_get_option(const rq_sparse* h, const char* name);
  *   rq_hybrid_create: NULL with the message in rq_last_error(), NULL + the "no HIP device" message without a gfx950 device.  A handle
  *   is used from one thread.  Read-only options (rq_hybrid_get_option, -1 with a message for an unknown name): "calls", "fuse_calls",
  *   "missing_calls" (both entry points each), "nb", "n_dense", "n_keys".
- * Not extended: MMR and grouping over the fused pool, filters, multi-device handles. */
+ *   Filtered pools (rq_sparse_topk_masked_device, rq_search_filtered_each_device) fuse as they are: the fusion needs no filter of its own.
+ * Not extended: MMR and grouping over the fused pool, distinct_by (it stays on the host), multi-device handles. */
 typedef struct rq_hybrid rq_hybrid;
 #define RQ_HYBRID_MAX_CAND 2048
 rq_hybrid* rq_hybrid_create(int device_id, int64_t nb, int64_t n_dense, const int64_t* dense_key, const uint8_t* known, int64_t n_keys);

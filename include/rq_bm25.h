@@ -42,6 +42,17 @@ void rq_bm25_destroy(rq_bm25* h);
 int rq_bm25_topk(const rq_bm25* h, const int64_t* q_indptr, const int32_t* q_tokens, int n_queries, int k,
                  int32_t* out_rows, double* out_scores, int n_threads);
 
+/* rq_bm25_topk with one allowed set per query (the host form of include/rq.h rq_sparse_topk_masked, and its yardstick).
+ * masks is [n_masks][W] uint32, W = ceil(n_docs / 32): bit r % 32 of word r / 32 set = document row r is allowed (the bitmap
+ * layout of rq_filter_create); bits at or beyond n_docs are ignored.  mask_of[q] is the mask of query q, -1 = unrestricted; the
+ * same mask may serve any number of queries.  Scores are added exactly as in rq_bm25_topk; a document outside the query's mask
+ * then scores 0.0 BEFORE the score > 0 selection, so query q's answer is rq_bm25_topk's answer over its allowed documents
+ * alone, bit for bit (an empty mask returns nothing).  RQ_BM25_EINVAL for what rq_bm25_topk refuses, a null mask_of, a null
+ * masks with n_masks > 0 (n_masks == 0 without a table is legal when every entry is -1) and a mask_of entry outside
+ * [-1, n_masks).  Threads and thread safety as rq_bm25_topk. */
+int rq_bm25_topk_masked(const rq_bm25* h, const int64_t* q_indptr, const int32_t* q_tokens, int n_queries, int k,
+                        const uint32_t* masks, int n_masks, const int32_t* mask_of, int32_t* out_rows, double* out_scores, int n_threads);
+
 const char* rq_bm25_version(void);
 
 #ifdef __cplusplus
