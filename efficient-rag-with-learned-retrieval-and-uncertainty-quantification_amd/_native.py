@@ -119,6 +119,13 @@ _SIGNATURES = {
     "rq_hybrid_missing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rq_hybrid_fuse_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 7),
     "rq_hybrid_fuse": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6),
+    "rq_router_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
+    "rq_router_destroy": (None, [C.c_void_p]),
+    "rq_router_get_option": (C.c_double, [C.c_void_p, C.c_char_p]),
+    "rq_router_gate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_router_gate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rq_router_rerank_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    "rq_router_rerank": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
     "rq_sparse_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "rq_sparse_get_option": (C.c_double, [C.c_void_p, C.c_char_p]),
     "rq_search_train_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -945,6 +952,107 @@ class HybridMap:
         _check(self._lib.rq_hybrid_fuse_device(self._h, _ptr(d_sp_rows), _ptr(d_sp_scores), _ptr(d_de_rows), _ptr(d_de_scores), int(B), int(K1), int(K2),
                                                _ptr(d_miss_dense), _ptr(d_extra_dense), _ptr(d_miss_sparse), _ptr(d_extra_sparse), int(top_k), _ptr(d_keys),
                                                _ptr(d_b), _ptr(d_d), _ptr(d_h), _ptr(d_pos), _ptr(d_count), C.c_void_p(stream)), "rq_hybrid_fuse_device")
+
+
+# -- router gate on the device (include/rq.h "router gate", csrc/rq_router.hip) -----------------------------------------------------------
+ROUTER_MAX_HIDDEN = 256
+ROUTER_NORM_STATS = 0
+ROUTER_NORM_QUERY = 1
+
+
+class RouterGate:
+    """Owner of one rq_router handle: the weights of a RetrievalRouter with one or two layers (w0 [H][3], b0 [H], w1 [H] or [3], b1;
+    fp32, COPIED to the device) and the two calls over a batch of fused columns: `gate` (the weight of every slot, in input order) and
+    `rerank` (the best top_r candidates by w*d + (1 - w)*b).  `mode` is ROUTER_NORM_QUERY or ROUTER_NORM_STATS, `stats` the four
+    doubles (bm25_mean, bm25_std, dense_mean, dense_std) of the latter.  No host fallback."""
+
+    def __init__(self, w0, b0, w1, b1: float, *, num_layers: int = 2, use_batch_norm: bool = False, device: int = 0):
+        self._lib = load_library()
+        w1 = np.ascontiguousarray(w1, np.float32).reshape(-1)
+        hidden = 0
+        if int(num_layers) == 2:
+            w0 = np.ascontiguousarray(w0, np.float32)
+            b0 = np.ascontiguousarray(b0, np.float32).reshape(-1)
+            if w0.ndim != 2 or w0.shape[1] != 3 or b0.shape != (w0.shape[0],) or w1.shape != (w0.shape[0],):
+                raise RqError(f"rq_router_create: w0 [H][3], b0 [H] and w1 [H], got {w0.shape}, {b0.shape} and {w1.shape}")
+            hidden = w0.shape[0]
+        elif int(num_layers) == 1:
+            if w1.shape != (3,):
+                raise RqError(f"rq_router_create: one layer takes w1 [3], got {w1.shape}")
+            w0 = b0 = None
+        h = self._lib.rq_router_create(int(device), int(num_layers), hidden, int(bool(use_batch_norm)), _ptr(w0) if hidden else None,
+                                       _ptr(b0) if hidden else None, _ptr(w1), float(b1))
+        if not h:
+            raise RqError(f"rq_router_create: {last_error()}")
+        self._h = C.c_void_p(h)
+        self.hidden, self.layers, self.device = hidden, int(num_layers), int(device)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.rq_router_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def get_option(self, name: str) -> float:
+        return float(self._lib.rq_router_get_option(self._h, name.encode()))
+
+    @staticmethod
+    def _stats(mode: int, stats) -> Optional[np.ndarray]:
+        """The four statistics as the host array the library reads at call time (None: the per-query mode needs none)."""
+        if stats is None:
+            return None
+        stats = np.ascontiguousarray(stats, np.float64)
+        if stats.shape != (4,):
+            raise RqError(f"router statistics are (bm25_mean, bm25_std, dense_mean, dense_std), got shape {stats.shape}")
+        return stats
+
+    @staticmethod
+    def _columns(b, d) -> Tuple[np.ndarray, np.ndarray]:
+        b, d = np.ascontiguousarray(b, np.float64), np.ascontiguousarray(d, np.float64)
+        if b.ndim != 2 or b.shape != d.shape:
+            raise RqError(f"router columns are [B][P] twice, got {b.shape} and {d.shape}")
+        return b, d
+
+    def gate(self, b, d, mode: int = ROUTER_NORM_QUERY, stats=None) -> np.ndarray:
+        """Blocking, host arrays: w float64 [B][P] in input order."""
+        b, d = self._columns(b, d)
+        stats = self._stats(mode, stats)
+        w = np.empty(b.shape, np.float64)
+        _check(self._lib.rq_router_gate(self._h, _ptr(b), _ptr(d), b.shape[0], b.shape[1], int(mode), _ptr(stats), _ptr(w)), "rq_router_gate")
+        return w
+
+    def gate_device(self, d_b, d_d, B: int, P: int, d_w, mode: int = ROUTER_NORM_QUERY, stats=None, stream: int = 0) -> None:
+        """Asynchronous, device pointers: float64 [B][P] twice -> float64 [B][P]; complete in stream order."""
+        stats = self._stats(mode, stats)
+        _check(self._lib.rq_router_gate_device(self._h, _ptr(d_b), _ptr(d_d), int(B), int(P), int(mode), _ptr(stats), _ptr(d_w), C.c_void_p(stream)),
+               "rq_router_gate_device")
+
+    def rerank(self, keys, b, d, count, top_r: int, mode: int = ROUTER_NORM_QUERY, stats=None):
+        """Blocking, host arrays: (keys int32, b, d, w, h float64, positions int32 -- all [B][top_r] -- and count int32 [B])."""
+        b, d = self._columns(b, d)
+        keys, count = np.ascontiguousarray(keys, np.int32), np.ascontiguousarray(count, np.int32)
+        if keys.shape != b.shape or count.shape != (b.shape[0],):
+            raise RqError(f"router rerank: keys {keys.shape} and count {count.shape} for columns {b.shape}")
+        stats = self._stats(mode, stats)
+        B, k = b.shape[0], max(int(top_r), 0)
+        ok, op, oc = np.empty((B, k), np.int32), np.empty((B, k), np.int32), np.empty(B, np.int32)
+        ob, od, ow, oh = np.empty((B, k)), np.empty((B, k)), np.empty((B, k)), np.empty((B, k))
+        _check(self._lib.rq_router_rerank(self._h, _ptr(keys), _ptr(b), _ptr(d), _ptr(count), B, b.shape[1], int(mode), _ptr(stats), int(top_r), _ptr(ok),
+                                          _ptr(ob), _ptr(od), _ptr(ow), _ptr(oh), _ptr(op), _ptr(oc)), "rq_router_rerank")
+        return ok, ob, od, ow, oh, op, oc
+
+    def rerank_device(self, d_keys, d_b, d_d, d_count, B: int, P: int, top_r: int, d_out_keys, d_out_b, d_out_d, d_out_w, d_out_h, d_out_pos, d_out_count,
+                      mode: int = ROUTER_NORM_QUERY, stats=None, stream: int = 0) -> None:
+        """Asynchronous, device pointers (include/rq.h rq_router_rerank_device); complete in stream order."""
+        stats = self._stats(mode, stats)
+        _check(self._lib.rq_router_rerank_device(self._h, _ptr(d_keys), _ptr(d_b), _ptr(d_d), _ptr(d_count), int(B), int(P), int(mode), _ptr(stats), int(top_r),
+                                                 _ptr(d_out_keys), _ptr(d_out_b), _ptr(d_out_d), _ptr(d_out_w), _ptr(d_out_h), _ptr(d_out_pos), _ptr(d_out_count),
+                                                 C.c_void_p(stream)), "rq_router_rerank_device")
 
 
 # -- encoder pieces (include/rq.h "encoder pieces", csrc/rq_encoder.hip): torch tensors or raw device addresses -------------

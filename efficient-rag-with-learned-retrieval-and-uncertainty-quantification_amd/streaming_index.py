@@ -1460,15 +1460,23 @@ class HybridRetriever:
     fusion", the same values bit for bit -- and only [B][top_k] results come back; it needs `sparse_backend` "gpu" or "auto" and a
     single-device DenseIndex, and raises RqError with the reason otherwise; "auto": the device when all of that holds, else the host).
     The batch calls take `allowed_ids=` / `allowed_ids_each=` (one allowed set per query; `make_filter` for reuse) under every backend.
+    `router_backend` ("host" = default: `route_batch` gates and reranks the fused columns with numpy, `router.RouterGate`; "gpu": the
+    fused pool stays in HBM, rq_router_rerank_device reranks it there -- include/rq.h "router gate" -- and only [B][top_k] results
+    come back; it needs what `fusion_backend`'s device route needs, and raises RqError with the reason otherwise; "auto": the device
+    when all of that holds, else the host).
     """
 
     def __init__(self, bm25_persist_path: str = "./data/bm25_index.pkl", chroma_persist_path: str = "./data/chroma_db",
                  chroma_host: Optional[str] = None, embedding_model: str = "nomic-embed-text",
-                 *, dense_index=None, embedder=None, device: int = 0, sparse_backend: str = "host", fusion_backend: str = "host"):
+                 *, dense_index=None, embedder=None, device: int = 0, sparse_backend: str = "host", fusion_backend: str = "host",
+                 router_backend: str = "host"):
         if sparse_backend not in ("host", "gpu", "auto"):
             raise ValueError(f"sparse_backend must be 'host', 'gpu' or 'auto', not {sparse_backend!r}")
         if fusion_backend not in ("host", "gpu", "auto"):
             raise ValueError(f"fusion_backend must be 'host', 'gpu' or 'auto', not {fusion_backend!r}")
+        if router_backend not in ("host", "gpu", "auto"):
+            raise ValueError(f"router_backend must be 'host', 'gpu' or 'auto', not {router_backend!r}")
+        self.router_backend = router_backend   # where `route_batch` gates and reranks the fused pool
         self.sparse_backend = sparse_backend   # where the BATCH calls score BM25 (BM25Index.search_batch_rows `backend`); per-query calls stay on the host
         self.fusion_backend = fusion_backend   # where the BATCH calls fuse the two pools (`_fuse_batch_rows`)
         self.bm25_index = BM25Index(persist_path=bm25_persist_path)
@@ -1807,6 +1815,84 @@ class HybridRetriever:
             out.append((b, de, ids, texts))
         return out
 
+    # ---- the learned router over the fused pool (extension; include/rq.h "router gate") ------------------------------
+    def _route_on_device(self, router, num_passages: int, retrieval_pool_size: int, usable: bool) -> bool:
+        backend = getattr(self, "router_backend", "host")
+        if backend == "host":
+            return False
+        reason = None if usable else "one of the two indexes is not this module's own index class"
+        if reason is None:
+            reason = self._device_fusion_refusal(num_passages, retrieval_pool_size)
+        if reason is None:
+            try:
+                dn, bm = self.dense_index, self.bm25_index
+                router.native(dn._index.device if dn._index is not None else bm.__dict__.get("sparse_device", 0))
+            except _native.RqError as e:
+                reason = f"the gate cannot be placed on the device: {e}"
+        if reason is not None and backend == "gpu":
+            raise _native.RqError(f"router_backend='gpu': {reason}")
+        return reason is None
+
+    def _router_columns(self, queries: Sequence[str], num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list]):
+        """The columns `get_scores_for_router_batch` hands the router, as arrays: ids [B][P] ("" = padding), b, d float64 [B][P]."""
+        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores, each)
+        if fused is not None:
+            ids, b, de, _, count = fused
+            ids[np.arange(num_passages)[None, :] >= count[:, None]] = ""
+            return ids, b, de
+        cols = self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, each)
+        ids = np.empty((len(cols), num_passages), dtype=object)
+        for q, c in enumerate(cols):
+            ids[q, :] = c[2]
+        return ids, np.array([c[0] for c in cols], np.float64).reshape(len(cols), num_passages), np.array([c[1] for c in cols], np.float64).reshape(len(cols), num_passages)
+
+    def _route_batch(self, queries: Sequence[str], router, top_k: int, num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None):
+        bm, dn = self.bm25_index, self.dense_index
+        r = min(int(top_k), int(num_passages))
+        usable = isinstance(bm, BM25Index) and isinstance(dn, DenseIndex)
+        if self._route_on_device(router, num_passages, retrieval_pool_size, usable):
+            ids, b, de, w, h, count = self._fuse_batch_device(list(queries), num_passages, retrieval_pool_size, complete_scores, each, route=(router, r))
+        else:
+            ids, cb, cd = self._router_columns(queries, num_passages, retrieval_pool_size, complete_scores, each)
+            keys = np.where(ids != "", np.arange(num_passages, dtype=np.int32)[None, :], -1)
+            _, b, de, w, h, pos, count = router.rerank(keys, cb, cd, np.full(len(queries), num_passages), r)
+            ids = np.take_along_axis(ids, np.where(pos >= 0, pos, 0).astype(np.int64), 1)
+        idl, bl, dl, hl = ids.tolist(), b.tolist(), de.tolist(), h.tolist()
+        out = []
+        for q in range(len(queries)):
+            res = []
+            for i in range(int(count[q])):
+                doc = self.documents[idl[q][i]]
+                res.append(RetrievalResult(doc_id=doc.id, text=doc.text, bm25_score=bl[q][i], dense_score=dl[q][i], hybrid_score=hl[q][i],
+                                           title=doc.title, metadata=doc.metadata))
+            out.append(res)
+        return out, w
+
+    def route_batch(self, queries: Sequence[str], router, top_k: int = 10, *, num_passages: int = 20, retrieval_pool_size: int = 50, complete_scores: bool = False,
+                    allowed_ids=None, allowed_ids_each=None, return_weights: bool = False):
+        """Retrieve, gate and rerank a batch: the loop of reference experiments/run_evaluation.py:165-184 as one call.  For every
+        question the `num_passages` fused passages of `get_scores_for_router` are weighted by `router` (a `router.RouterGate`) and
+        reordered by h = w*dense + (1 - w)*bm25; the first `top_k` real passages come back, best first, `hybrid_score` = h.  Question
+        q's answer is the host gate's rerank of `get_scores_for_router(q, num_passages, ...)`'s columns, with the same filters and
+        `complete_scores`.  `return_weights=True` adds the gate weights, float64 [B][top_k] (0.0 beyond a question's results).
+        Where it runs is `router_backend`'s choice."""
+        queries = list(queries)
+        if int(num_passages) < 1 or int(top_k) < 1:
+            raise ValueError(f"num_passages {num_passages} and top_k {top_k} must be at least 1")
+        if not queries:
+            return ([], np.zeros((0, min(int(top_k), int(num_passages))))) if return_weights else []
+        entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
+        if entries is None:
+            out, w = self._route_batch(queries, router, top_k, int(num_passages), retrieval_pool_size, complete_scores)
+        else:
+            out, w = self._with_filters(entries, lambda each: self._route_batch(queries, router, top_k, int(num_passages), retrieval_pool_size, complete_scores, each))
+        return (out, w) if return_weights else out
+
+    def route(self, query: str, router, top_k: int = 10, **keywords):
+        """`route_batch([query], ...)[0]` (with `return_weights=True`: the list and the weights of that one question)."""
+        out = self.route_batch([query], router, top_k, **keywords)
+        return (out[0][0], out[1][0]) if keywords.get("return_weights") else out[0]
+
     # ---- batched fusion in row space (extension; configs[4]: 500 questions x two pools of 100) ------------------------------------
     def _key_space(self):
         """One integer key per document either index can return: BM25 row r -> r, dense row j -> the BM25 row of the same id if BM25
@@ -1870,13 +1956,17 @@ class HybridRetriever:
             ks["map"] = _native.HybridMap(ks["nb"], ks["dense_key"], ks["known"], device=device)
         return ks["map"]
 
-    def _fuse_batch_device(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None):
+    def _fuse_batch_device(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
+                           route: Optional[tuple] = None):
         """`_fuse_batch_rows` with both pools left where they are drawn: token ids and query vectors go down, rq_sparse_topk_device and
         rq_search_device (with its fixup) fill the pools in HBM, `complete_scores` adds rq_hybrid_missing_device and the two row-scoring
         calls, rq_hybrid_fuse_device ranks, and one copy brings [B][top_k] keys, scores and the counts back.  Same return value.
         `each` (one HybridFilter or None per query): the mask table goes down once, rq_sparse_topk_masked_device and
         rq_search_filtered_each_device (with its fixup; complete in stream order) fill the pools, the rest runs as it is -- pools that
-        are already filtered fuse as they are."""
+        are already filtered fuse as they are.
+        `route` = (router.RouterGate, top_r): the fused block stays on the device, rq_router_rerank_device runs on the same stream
+        over its keys, b, d and counts, and the one copy brings [B][top_r] up instead; the return value is then
+        (ids, b, d, w, h -- [B][top_r] -- and count [B])."""
         import torch
         bm, dn = self.bm25_index, self.dense_index
         B, k, K1 = len(queries), int(top_k), max(int(retrieval_pool_size), 1)
@@ -1945,6 +2035,18 @@ class HybridRetriever:
             scores = block[: 6 * n].view(torch.float64)
             hm.fuse_device(d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B, K1, K2, k, block[6 * n: 7 * n], scores[:n], scores[n: 2 * n], scores[2 * n:],
                            None, block[7 * n:], s, **extra)
+            if route is not None:
+                gate, r = route
+                m = B * r
+                out = torch.empty((10 * m + B,), device=dev, dtype=torch.int32)      # b, d, w, h (float64) | keys, pos (int32) | count (int32)
+                o64 = out[: 8 * m].view(torch.float64)
+                gate.native(device).rerank_device(block[6 * n: 7 * n], scores[:n], scores[n: 2 * n], block[7 * n:], B, k, r, out[8 * m: 9 * m], o64[:m],
+                                                  o64[m: 2 * m], o64[2 * m: 3 * m], o64[3 * m:], out[9 * m: 10 * m], out[10 * m:], mode=gate.mode,
+                                                  stats=gate.stats, stream=s)
+                host = out.cpu().numpy()
+                sc = host[: 8 * m].view(np.float64).reshape(4, B, r)
+                keys = host[8 * m: 9 * m].reshape(B, r)
+                return ks["ids"][np.where(keys >= 0, keys, 0)], sc[0], sc[1], sc[2], sc[3], host[10 * m:].astype(np.int64)
             host = block.cpu().numpy()
         sc = host[: 6 * n].view(np.float64)
         keys = host[6 * n: 7 * n].reshape(B, k)

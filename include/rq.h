@@ -628,6 +628,60 @@ int rq_hybrid_fuse(rq_hybrid* h, const int32_t* sp_rows, const double* sp_scores
                    const int64_t* miss_dense, const float* extra_dense, const int32_t* miss_sparse, const double* extra_sparse, int top_k,
                    int32_t* out_keys, double* out_b, double* out_d, double* out_h, int32_t* out_pos, int32_t* out_count);
 
+/* ---- router gate: the learned gate and the rerank of the fused pool on the device (reference rag_uq/router.py:74-177 as the
+ * evaluation loop applies it, experiments/run_evaluation.py:165-184) ------------------------------------------------
+ * An rq_router holds the weights of a RetrievalRouter with num_layers 1 or 2, COPIED to one device and read-only after creation.
+ *   num_layers 2: W0 [H][3], b0 [H], w1 [H], b1 (Linear(3, H) -> ReLU -> Linear(H, 1) -> Sigmoid), 1 <= H <= RQ_ROUTER_MAX_HIDDEN;
+ *   num_layers 1: w1 [3], b1: a logistic unit on the three features (hidden, w0 and b0 are ignored).
+ *   Weights are given as fp32, as they are in a state dict, and widened exactly.  use_batch_norm != 0 and num_layers > 2 are
+ *   refused with the reason in rq_last_error(): the reference never builds them.
+ * Input per query: columns key [P] (int32), b [P], d [P] (float64) and count -- the output layout of rq_hybrid_fuse_device,
+ *   1 <= P <= RQ_MAX_K.  ALL P slots, padding included, take part in the normalisation and get a weight (the reference pads the
+ *   columns to num_passages with 0.0 before the router sees them).
+ * Definition.  All arithmetic is float64, every operation rounded on its own, no fused multiply-add.
+ *   normalisation, mode RQ_ROUTER_NORM_STATS: stats = (bm25_mean, bm25_std, dense_mean, dense_std), four doubles in HOST memory
+ *     read at call time: nb = (b - bm25_mean) / (bm25_std + 1e-6), nd likewise.
+ *   mode RQ_ROUTER_NORM_QUERY (stats may be NULL): per query and per column x, mean = S(x) / P,
+ *     var = S((x - mean) * (x - mean)) / (P - 1), scale = sqrt(var) + 1e-6, nx = (x - mean) / scale.  P = 1 gives 0/0 = NaN.
+ *     S is a fixed pairwise tree: the column is padded with +0.0 to the next power of two n, then a[i] = a[i] + a[i + n/2] for
+ *     i < n/2, n halved each time; the sum does not depend on the thread count.
+ *     The reference's batch-wise form over the whole [B][P] tensor is deliberately not offered: a question's answer would depend
+ *     on its neighbours in the batch.
+ *   gate: df = nd - nb; z = 0.0; for j = 0 .. H-1 in order: a_j = ((W0[j][0]*nb + W0[j][1]*nd) + W0[j][2]*df) + b0[j],
+ *     r_j = a_j > 0 ? a_j : 0, z = z + w1[j]*r_j; then z = z + b1 and w = 1.0 / (1.0 + exp(-z)).
+ *     num_layers 1: z = ((w1[0]*nb + w1[1]*nd) + w1[2]*df) + b1.
+ *   rerank: h = w*d + (1.0 - w)*b: a product, a subtraction, a product and an addition.  Candidates are the positions i < count
+ *     with key[i] >= 0 (a count outside 0 .. P is clamped).  order: h descending with -0.0 as +0.0; a NaN h ranks as -inf, as every
+ *     score in this header, and is returned as it is; equal h by ascending position.
+ *   output [B][top_r], 1 <= top_r <= P: key (int32), b, d, w, h (float64), pos (int32: the position in the input);
+ *     count_out[B] = min(candidates, top_r); entries beyond it are (-1, 0.0, 0.0, 0.0, 0.0, -1).
+ *   Everything but exp has the bits of tests/router_gate_oracle.py; w is within 2^-49 relative of it (3 ulp of the device
+ *     library's exp), and exactly 0, 1 or NaN where the definition gives that.
+ * rq_router_gate_device: d_w [B][P] in input order (RetrievalRouter.forward).  rq_router_rerank_device: as above; its w is the
+ *   bits of rq_router_gate_device's w at that position (one device function serves both).  One workgroup per query, everything in
+ *   LDS (about 47 KiB at P = 1 024, under 64 KiB), the kernel instantiated for P padded to a power of two (64 .. 1 024).  Both
+ *   device forms: no workspace, no synchronisation, complete in stream order.
+ * rq_router_gate / rq_router_rerank: blocking, host buffers, staged on a stream the handle owns.
+ * RQ_EINVAL for sizes outside the limits above, B outside 1 .. 65535, null pointers or an unknown mode; RQ_ENODEVICE as
+ *   everywhere; rq_router_create: NULL with the message in rq_last_error(), NULL + the "no HIP device" message without a gfx950
+ *   device.  A handle is used from one thread.  Read-only options (rq_router_get_option, -1 with a message for an unknown name):
+ *   "calls", "gate_calls", "rerank_calls" (both entry points each), "hidden", "layers".
+ * Not extended: router training, batch norm and deeper nets, multi-device handles, MMR or grouping over the routed pool. */
+typedef struct rq_router rq_router;
+#define RQ_ROUTER_MAX_HIDDEN 256
+#define RQ_ROUTER_NORM_STATS 0
+#define RQ_ROUTER_NORM_QUERY 1
+rq_router* rq_router_create(int device_id, int num_layers, int hidden, int use_batch_norm, const float* w0, const float* b0, const float* w1, float b1);
+void rq_router_destroy(rq_router* r);
+double rq_router_get_option(const rq_router* r, const char* name);
+int rq_router_gate_device(rq_router* r, const double* d_b, const double* d_d, int B, int P, int mode, const double* stats, double* d_w, void* stream);
+int rq_router_gate(rq_router* r, const double* b, const double* d, int B, int P, int mode, const double* stats, double* out_w);
+int rq_router_rerank_device(rq_router* r, const int32_t* d_keys, const double* d_b, const double* d_d, const int32_t* d_count, int B, int P, int mode,
+                            const double* stats, int top_r, int32_t* d_out_keys, double* d_out_b, double* d_out_d, double* d_out_w, double* d_out_h,
+                            int32_t* d_out_pos, int32_t* d_out_count, void* stream);
+int rq_router_rerank(rq_router* r, const int32_t* keys, const double* b, const double* d, const int32_t* count, int B, int P, int mode, const double* stats,
+                     int top_r, int32_t* out_keys, double* out_b, double* out_d, double* out_w, double* out_h, int32_t* out_pos, int32_t* out_count);
+
 /* Tuning / test hooks: "kstage" (1: an LDS stage holds whole rows, 2: half rows), "ring" (LDS stages 2..6; the
  * (kstage, ring, prefetch) triples built are listed in csrc/rq_scan.hip, others fail with RQ_EHIP at search time),
  * "wg_per_cu", "nt" (non-temporal corpus loads: 0, 1, -1 = auto), "slack_bins" (extra bins beyond k, -1 = auto),
