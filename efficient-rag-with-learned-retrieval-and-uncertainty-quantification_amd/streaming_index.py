@@ -1214,8 +1214,9 @@ class DenseIndex:
                 pinned[:n].copy_(block[:n], non_blocking=True)
                 stream.synchronize()
         host = pinned.numpy()
-        rows = host[: 2 * B * k].view(np.int64).reshape(B, k)
-        scores = host[2 * B * k: 3 * B * k].view(np.float32).reshape(B, k)
+        # copies: the pinned block is written again by the next call, and `search_rows_batch` hands these arrays to its caller
+        rows = host[: 2 * B * k].view(np.int64).reshape(B, k).copy()
+        scores = host[2 * B * k: 3 * B * k].view(np.float32).reshape(B, k).copy()
         return scores, rows
 
     # ---- range searches (extension: every passage at least this similar, and how many there are -- what a caller of reference

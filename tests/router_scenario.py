@@ -37,10 +37,12 @@ def gate(normalize="query"):
     return g
 
 
-def retriever(path, dense_index=None, **keywords):
+def retriever(path, dense_index=None, embedder=None, **keywords):
+    """`embedder`: HashEmbedder() unless given (tests/test_gpu_device_queries.py passes the twins of tests/device_twin.py)."""
     from rag_uq_amd.embedders import HashEmbedder
     os.makedirs(path, exist_ok=True)
-    return si.HybridRetriever(bm25_persist_path=str(path / "bm25.pkl"), chroma_persist_path=str(path / "dense"), embedder=HashEmbedder(), dense_index=dense_index, **keywords)
+    return si.HybridRetriever(bm25_persist_path=str(path / "bm25.pkl"), chroma_persist_path=str(path / "dense"),
+                              embedder=HashEmbedder() if embedder is None else embedder, dense_index=dense_index, **keywords)
 
 
 def answers(out):
