@@ -110,6 +110,14 @@ _SIGNATURES = {
     "rq_sparse_topk_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rq_sparse_topk_masked_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_sparse_set_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "rq_sparse_topk_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "rq_sparse_topk_grouped_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rq_hybrid_set_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "rq_hybrid_fuse_grouped_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p] * 7),
+    "rq_hybrid_fuse_grouped": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p] * 6),
     "rq_sparse_score_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rq_sparse_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "rq_hybrid_create": (C.c_void_p, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -834,6 +842,42 @@ class SparseIndex:
         _check(self._lib.rq_sparse_topk_device(self._h, _ptr(d_q_indptr), _ptr(d_q_tokens), int(B), int(n_q_tokens), int(k), _ptr(d_rows),
                                                _ptr(d_scores), C.c_void_p(stream)), "rq_sparse_topk_device")
 
+    def set_groups(self, groups) -> None:
+        """The group of every document, int32 [n_docs]: -1 (`GROUP_NONE`) = a group of its own, any other value >= 0; COPIED to the
+        device, a second call replaces the table (rq_sparse_set_groups)."""
+        groups = np.ascontiguousarray(groups, np.int32)
+        if groups.shape != (self.n_docs,):
+            raise RqError(f"rq_sparse_set_groups: one group id per document: {self.n_docs} documents, shape {groups.shape}")
+        _check(self._lib.rq_sparse_set_groups(self._h, _ptr(groups) if self.n_docs else None, self.n_docs), "rq_sparse_set_groups")
+
+    def topk_grouped(self, q_indptr, q_tokens, B: int, k: int, *, masks=None, mask_of=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Blocking, host arrays: `topk` with one document per group of the `set_groups` table -- (rows int32 [B][k], -1 padded; scores
+        float64 [B][k], 0.0 padded; count int32 [B]); `masks` / `mask_of` as in `topk` (rq_sparse_topk_grouped)."""
+        q_indptr = np.ascontiguousarray(q_indptr, np.int64)
+        q_tokens = np.ascontiguousarray(q_tokens, np.int32)
+        if len(q_indptr) != int(B) + 1 or (int(B) >= 1 and len(q_tokens) < int(q_indptr[-1])):
+            raise RqError(f"rq_sparse_topk_grouped: q_indptr holds {len(q_indptr)} entries for {B} queries, or names more tokens than q_tokens holds")
+        out_rows = np.empty((max(int(B), 0), max(int(k), 0)), np.int32)
+        out_scores = np.empty((max(int(B), 0), max(int(k), 0)), np.float64)
+        out_count = np.empty(max(int(B), 0), np.int32)
+        if masks is not None and mask_of is None:
+            raise RqError("rq_sparse_topk_grouped: masks without mask_of")
+        n_masks = 0
+        if mask_of is not None:
+            masks, n_masks, mask_of = _mask_args("rq_sparse_topk_grouped", masks, mask_of, B, self.n_docs)
+        _check(self._lib.rq_sparse_topk_grouped(self._h, _ptr(q_indptr), _ptr(q_tokens) if len(q_tokens) else None, int(B), int(k), _ptr(masks), n_masks,
+                                                _ptr(mask_of), _ptr(out_rows), _ptr(out_scores), _ptr(out_count)), "rq_sparse_topk_grouped")
+        return out_rows, out_scores, out_count
+
+    def topk_grouped_device(self, d_q_indptr, d_q_tokens, B: int, n_q_tokens: int, k: int, d_rows, d_scores, d_count, stream: int = 0, *,
+                            d_masks=None, n_masks: int = 0, d_mask_of=None) -> None:
+        """Asynchronous, device pointers: `topk_device` with one document per group and int32 [B] counts (rq_sparse_topk_grouped_device)."""
+        if d_masks is not None and d_mask_of is None:
+            raise RqError("rq_sparse_topk_grouped_device: d_masks without d_mask_of")
+        _check(self._lib.rq_sparse_topk_grouped_device(self._h, _ptr(d_q_indptr), _ptr(d_q_tokens), int(B), int(n_q_tokens), int(k), _ptr(d_masks), int(n_masks),
+                                                       _ptr(d_mask_of), _ptr(d_rows), _ptr(d_scores), _ptr(d_count), C.c_void_p(stream)),
+               "rq_sparse_topk_grouped_device")
+
     def score_rows(self, q_indptr, q_tokens, B: int, rows) -> np.ndarray:
         """Blocking, host arrays: the BM25 score of every (query, row) pair of one list of rows per query, rows int32 [B][m] -> float64
         [B][m] with the bits of a full score vector's entry; a row outside the index (-1 included) scores 0.0 (rq_sparse_score_rows)."""
@@ -952,6 +996,37 @@ class HybridMap:
         _check(self._lib.rq_hybrid_fuse_device(self._h, _ptr(d_sp_rows), _ptr(d_sp_scores), _ptr(d_de_rows), _ptr(d_de_scores), int(B), int(K1), int(K2),
                                                _ptr(d_miss_dense), _ptr(d_extra_dense), _ptr(d_miss_sparse), _ptr(d_extra_sparse), int(top_k), _ptr(d_keys),
                                                _ptr(d_b), _ptr(d_d), _ptr(d_h), _ptr(d_pos), _ptr(d_count), C.c_void_p(stream)), "rq_hybrid_fuse_device")
+
+    def set_groups(self, key_group) -> None:
+        """The group of every key, int32 [n_keys]: -1 = a group of its own, any other value >= 0; COPIED to the device, a second call
+        replaces the table (rq_hybrid_set_groups)."""
+        key_group = np.ascontiguousarray(key_group, np.int32)
+        if key_group.shape != (self.n_keys,):
+            raise RqError(f"rq_hybrid_set_groups: one group id per key: {self.n_keys} keys, shape {key_group.shape}")
+        _check(self._lib.rq_hybrid_set_groups(self._h, _ptr(key_group) if self.n_keys else None, self.n_keys), "rq_hybrid_set_groups")
+
+    def fuse_grouped(self, sp_rows, sp_scores, de_rows, de_scores, top_k: int):
+        """Blocking, host arrays: `fuse` with the first candidate of every group of the `set_groups` table only -- the same six arrays."""
+        sp_rows, de_rows = self._pools(sp_rows, de_rows)
+        B, K1, K2, k = sp_rows.shape[0], sp_rows.shape[1], de_rows.shape[1], int(top_k)
+        sp_scores = np.ascontiguousarray(sp_scores, np.float64)
+        de_scores = np.ascontiguousarray(de_scores, np.float32)
+        if sp_scores.shape != sp_rows.shape or de_scores.shape != de_rows.shape:
+            raise RqError("hybrid pools: scores and rows differ in shape")
+        kk = max(k, 0)
+        keys, pos, count = np.empty((B, kk), np.int32), np.empty((B, kk), np.int32), np.empty(B, np.int32)
+        b, d, h = np.empty((B, kk)), np.empty((B, kk)), np.empty((B, kk))
+        _check(self._lib.rq_hybrid_fuse_grouped(self._h, _ptr(sp_rows) if K1 else None, _ptr(sp_scores) if K1 else None, _ptr(de_rows) if K2 else None,
+                                                _ptr(de_scores) if K2 else None, B, K1, K2, k, _ptr(keys), _ptr(b), _ptr(d), _ptr(h), _ptr(pos), _ptr(count)),
+               "rq_hybrid_fuse_grouped")
+        return keys, b, d, h, pos, count
+
+    def fuse_grouped_device(self, d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B: int, K1: int, K2: int, top_k: int, d_keys, d_b, d_d, d_h, d_pos, d_count,
+                            stream: int = 0) -> None:
+        """Asynchronous, device pointers (include/rq.h rq_hybrid_fuse_grouped_device); d_pos may be None."""
+        _check(self._lib.rq_hybrid_fuse_grouped_device(self._h, _ptr(d_sp_rows), _ptr(d_sp_scores), _ptr(d_de_rows), _ptr(d_de_scores), int(B), int(K1), int(K2),
+                                                       int(top_k), _ptr(d_keys), _ptr(d_b), _ptr(d_d), _ptr(d_h), _ptr(d_pos), _ptr(d_count), C.c_void_p(stream)),
+               "rq_hybrid_fuse_grouped_device")
 
 
 # -- router gate on the device (include/rq.h "router gate", csrc/rq_router.hip) -----------------------------------------------------------

@@ -50,6 +50,7 @@ struct HybridArgs {
     double* h;
     int32_t* pos;                // may be NULL
     int32_t* count;              // [B]
+    const int32_t* key_group;    // [n_keys], grouped fusion only (rq_hybrid_kernel<P, true, true>): -1 = a group of its own
 };
 
 // the key of a VALID position (its row was range-checked when the flags were set)
@@ -58,7 +59,7 @@ __device__ __forceinline__ int32_t hybrid_key_of(const HybridArgs& a, int q, int
     return a.dense_key[a.de_rows[(size_t)q * (size_t)a.K2 + (size_t)(p - a.K1)]];
 }
 
-template <int P, bool FUSE>
+template <int P, bool FUSE, bool GROUPED = false>
 __global__ __launch_bounds__(P / 2 < 64 ? 64 : (P / 2 > RQ_HYBRID_MAX_THREADS ? RQ_HYBRID_MAX_THREADS : P / 2)) void rq_hybrid_kernel(HybridArgs a) {
     constexpr int T = P / 2 < 64 ? 64 : (P / 2 > RQ_HYBRID_MAX_THREADS ? RQ_HYBRID_MAX_THREADS : P / 2);
     constexpr int W = T / 64;
@@ -194,9 +195,82 @@ __global__ __launch_bounds__(P / 2 < 64 ? 64 : (P / 2 > RQ_HYBRID_MAX_THREADS ? 
             }
             __syncthreads();
         }
+    const size_t base = (size_t)q * (size_t)a.top_k;
+    if constexpr (GROUPED) {
+        // ---- 5g. one ordered pass over the full ranking: the first candidate of every group stays (include/rq.h rq_hybrid_fuse_grouped*) ----
+        // Ranks 0 .. cnt-1 hold the valid candidates in order.  The (group, rank) pairs -- unique: the rank is part of them -- are
+        // sorted; a pair whose predecessor has another group is its group's first rank.  Group -1 is a group of its own and never
+        // enters the sort.  s_a (the sort keys are spent) holds the pairs, s_f (the flags are spent) the keep flag of every RANK.
+        for (int r = tid; r < P; r += T) {
+            uint64_t pair = ~0ull;
+            uint8_t keep = 0;
+            if (r < cnt) {
+                const int32_t g = a.key_group[hybrid_key_of(a, q, s_pos[r])];
+                if (g < 0) keep = 1;
+                else pair = ((uint64_t)(uint32_t)g << 32) | (uint32_t)r;
+            }
+            s_a[r] = pair;
+            s_f[r] = keep;
+        }
+        __syncthreads();
+        for (int size = 2; size <= P; size <<= 1)
+            for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                for (int t = tid; t < P / 2; t += T) {
+                    const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                    const uint64_t x = s_a[i], y = s_a[j];
+                    if ((x > y) == ((i & size) == 0)) { s_a[i] = y; s_a[j] = x; }
+                }
+                __syncthreads();
+            }
+        for (int t = tid; t < P; t += T) {
+            const uint64_t x = s_a[t];
+            if (x == ~0ull) continue;
+            if (t == 0 || (uint32_t)(s_a[t - 1] >> 32) != (uint32_t)(x >> 32)) s_f[(uint32_t)x] = 1;   // (one writer per rank)
+        }
+        __syncthreads();
+        // thread t owns ranks C x t .. C x t + C - 1: the exclusive prefix sum of the keep flags is the output position
+        constexpr int C = P / T;
+        int own = 0;
+        for (int j = 0; j < C; ++j) own += s_f[C * tid + j];
+        int inc = own;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(inc, o, 64);
+            if ((tid & 63) >= o) inc += v;
+        }
+        if ((tid & 63) == 63) s_cnt[tid >> 6] = inc;   // (the reduction's slots were read before the sort's barriers)
+        __syncthreads();
+        int at = inc - own, kept = 0;
+        for (int w = 0; w < W; ++w) {
+            if (w < (tid >> 6)) at += s_cnt[w];
+            kept += s_cnt[w];
+        }
+        const int want = kept < a.top_k ? kept : a.top_k;
+        for (int j = 0; j < C; ++j) {
+            const int r = C * tid + j;
+            if (!s_f[r]) continue;
+            if (at < a.top_k) {
+                const int p = s_pos[r];
+                const double b = s_b[p], d = s_d[p];
+                a.keys[base + at] = hybrid_key_of(a, q, p);
+                a.b[base + at] = b;
+                a.d[base + at] = d;
+                a.h[base + at] = (b / max_b + d / max_d) / 2.0;
+                if (a.pos) a.pos[base + at] = p;
+            }
+            ++at;
+        }
+        for (int i = want + tid; i < a.top_k; i += T) {
+            a.keys[base + i] = -1;
+            a.b[base + i] = 0.0;
+            a.d[base + i] = 0.0;
+            a.h[base + i] = 0.0;
+            if (a.pos) a.pos[base + i] = -1;
+        }
+        if (tid == 0) a.count[q] = want;
+        return;
+    }
     // ---- 5. output ----
     const int want = cnt < a.top_k ? cnt : a.top_k;
-    const size_t base = (size_t)q * (size_t)a.top_k;
     for (int i = tid; i < a.top_k; i += T) {
         int32_t key = -1, p = -1;
         double b = 0.0, d = 0.0, h = 0.0;
@@ -255,11 +329,13 @@ struct rq_hybrid {
     int32_t* d_dense_row = nullptr;
     hipStream_t own = nullptr;
     int64_t calls = 0, fuse_calls = 0, missing_calls = 0;
+    int32_t* d_key_group = nullptr;   // [n_keys], rq_hybrid_set_groups (null: no table)
+    int64_t grouped_calls = 0;        // rq_hybrid_fuse_grouped* (counted in calls and fuse_calls too)
 };
 
 static void hybrid_free(rq_hybrid* h) {
     if (h->own) (void)hipStreamDestroy(h->own);
-    free_dev(h->d_dense_key, h->d_known, h->d_dense_row);
+    free_dev(h->d_dense_key, h->d_known, h->d_dense_row, h->d_key_group);
     delete h;
 }
 
@@ -312,6 +388,8 @@ extern "C" double rq_hybrid_get_option(const rq_hybrid* h, const char* name) {
     if (!strcmp(name, "calls")) return (double)h->calls;
     if (!strcmp(name, "fuse_calls")) return (double)h->fuse_calls;
     if (!strcmp(name, "missing_calls")) return (double)h->missing_calls;
+    if (!strcmp(name, "grouped_calls")) return (double)h->grouped_calls;
+    if (!strcmp(name, "grouped")) return h->d_key_group ? 1.0 : 0.0;
     if (!strcmp(name, "nb")) return (double)h->nb;
     if (!strcmp(name, "n_dense")) return (double)h->n_dense;
     if (!strcmp(name, "n_keys")) return (double)h->n_keys;
@@ -330,6 +408,19 @@ static void hybrid_launch(const HybridArgs& a, int B, hipStream_t s) {
     case 512: hipLaunchKernelGGL((rq_hybrid_kernel<512, FUSE>), grid, block, 0, s, a); break;
     case 1024: hipLaunchKernelGGL((rq_hybrid_kernel<1024, FUSE>), grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL((rq_hybrid_kernel<RQ_HYBRID_MAX_CAND, FUSE>), grid, block, 0, s, a); break;
+    }
+}
+
+static void hybrid_launch_grouped(const HybridArgs& a, int B, hipStream_t s) {
+    const int pad = hybrid_pad(a.K1 + a.K2);
+    const dim3 grid((unsigned)B), block((unsigned)hybrid_threads(pad));
+    switch (pad) {
+    case 64: hipLaunchKernelGGL((rq_hybrid_kernel<64, true, true>), grid, block, 0, s, a); break;
+    case 128: hipLaunchKernelGGL((rq_hybrid_kernel<128, true, true>), grid, block, 0, s, a); break;
+    case 256: hipLaunchKernelGGL((rq_hybrid_kernel<256, true, true>), grid, block, 0, s, a); break;
+    case 512: hipLaunchKernelGGL((rq_hybrid_kernel<512, true, true>), grid, block, 0, s, a); break;
+    case 1024: hipLaunchKernelGGL((rq_hybrid_kernel<1024, true, true>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((rq_hybrid_kernel<RQ_HYBRID_MAX_CAND, true, true>), grid, block, 0, s, a); break;
     }
 }
 
@@ -373,6 +464,45 @@ extern "C" int rq_hybrid_fuse_device(rq_hybrid* h, const int32_t* d_sp_rows, con
     HIPCHK(hipGetLastError());
     h->calls++;
     h->fuse_calls++;
+    return RQ_OK;
+}
+
+extern "C" int rq_hybrid_set_groups(rq_hybrid* h, const int32_t* key_group, int64_t n_keys) {
+    if (int rc = hybrid_check_groups(h, key_group, n_keys, h ? h->n_keys : 0)) return rc;
+    RQ_ON_DEVICE(h);
+    int32_t* fresh = nullptr;
+    if (hipMalloc((void**)&fresh, (size_t)(n_keys ? n_keys : 1) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(RQ_ENOMEM, "no room for a group table of %lld keys on device %d", (long long)n_keys, h->device);
+    }
+    if (n_keys && hipMemcpy(fresh, key_group, (size_t)n_keys * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(fresh);
+        return set_err(RQ_EHIP, "upload of the group table to device %d failed", h->device);
+    }
+    if (h->d_key_group) {        // an earlier call may still read the table it replaces
+        HIPCHK(hipDeviceSynchronize());
+        free_dev(h->d_key_group);
+    }
+    h->d_key_group = fresh;
+    return RQ_OK;
+}
+
+extern "C" int rq_hybrid_fuse_grouped_device(rq_hybrid* h, const int32_t* d_sp_rows, const double* d_sp_scores, const int64_t* d_de_rows, const float* d_de_scores,
+                                             int B, int K1, int K2, int top_k, int32_t* d_keys, double* d_b, double* d_d, double* d_h, int32_t* d_pos,
+                                             int32_t* d_count, void* stream) {
+    if (int rc = hybrid_check_fuse(h, d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B, K1, K2, nullptr, nullptr, nullptr, nullptr, top_k, d_keys, d_b, d_d, d_h, d_count))
+        return rc;
+    if (!h->d_key_group) return set_err(RQ_EINVAL, "no group table: call rq_hybrid_set_groups first");
+    RQ_ON_DEVICE(h);
+    HybridArgs a = hybrid_args(h, d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, K1, K2);
+    a.top_k = top_k;
+    a.keys = d_keys; a.b = d_b; a.d = d_d; a.h = d_h; a.pos = d_pos; a.count = d_count;
+    a.key_group = h->d_key_group;
+    hybrid_launch_grouped(a, B, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    h->calls++;
+    h->fuse_calls++;
+    h->grouped_calls++;
     return RQ_OK;
 }
 
@@ -422,6 +552,38 @@ extern "C" int rq_hybrid_fuse(rq_hybrid* h, const int32_t* sp_rows, const double
     int32_t* oc = (int32_t*)(out + no * 32);
     const int rc = rq_hybrid_fuse_device(h, (const int32_t*)at(4), (const double*)at(0), (const int64_t*)at(1), (const float*)at(5), B, K1, K2, (const int64_t*)at(2),
                                          (const float*)at(6), (const int32_t*)at(7), (const double*)at(3), top_k, ok, ob, ob + no, ob + 2 * no, ok + no, oc, (void*)h->own);
+    st.launched();
+    if (rc != RQ_OK) return rc;
+    st.down(out_b, ob, no * 8);
+    st.down(out_d, ob + no, no * 8);
+    st.down(out_h, ob + 2 * no, no * 8);
+    st.down(out_keys, ok, no * 4);
+    if (out_pos) st.down(out_pos, ok + no, no * 4);
+    st.down(out_count, oc, (size_t)B * 4);
+    return st.finish();
+}
+
+extern "C" int rq_hybrid_fuse_grouped(rq_hybrid* h, const int32_t* sp_rows, const double* sp_scores, const int64_t* de_rows, const float* de_scores, int B, int K1,
+                                      int K2, int top_k, int32_t* out_keys, double* out_b, double* out_d, double* out_h, int32_t* out_pos, int32_t* out_count) {
+    if (int rc = hybrid_check_fuse(h, sp_rows, sp_scores, de_rows, de_scores, B, K1, K2, nullptr, nullptr, nullptr, nullptr, top_k, out_keys, out_b, out_d, out_h,
+                                   out_count))
+        return rc;
+    if (!h->d_key_group) return set_err(RQ_EINVAL, "no group table: call rq_hybrid_set_groups first");
+    RQ_ON_DEVICE(h);
+    const size_t n1 = (size_t)B * (size_t)K1, n2 = (size_t)B * (size_t)K2, no = (size_t)B * (size_t)top_k;
+    // sp_scores, de_rows (8-byte elements first: every offset stays aligned), sp_rows, de_scores | b, d, h, keys, pos, count
+    const size_t bytes[5] = {(n1 ? n1 : 1) * 8, (n2 ? n2 : 1) * 8, (n1 ? n1 : 1) * 4, (n2 ? n2 : 1) * 4, no * 32 + (size_t)B * 4};
+    Stage st(h->own);
+    if (st.alloc(bytes, 5, "rq_hybrid_fuse_grouped") != RQ_OK) return st.code();
+    if (n1) { st.up(st.at<void>(0), sp_scores, n1 * 8); st.up(st.at<void>(2), sp_rows, n1 * 4); }
+    if (n2) { st.up(st.at<void>(1), de_rows, n2 * 8); st.up(st.at<void>(3), de_scores, n2 * 4); }
+    if (st.code() != RQ_OK) return st.code();
+    char* out = st.at<char>(4);
+    double* ob = (double*)out;
+    int32_t* ok = (int32_t*)(out + no * 24);
+    int32_t* oc = (int32_t*)(out + no * 32);
+    const int rc = rq_hybrid_fuse_grouped_device(h, n1 ? st.at<int32_t>(2) : nullptr, n1 ? st.at<double>(0) : nullptr, n2 ? st.at<int64_t>(1) : nullptr,
+                                                 n2 ? st.at<float>(3) : nullptr, B, K1, K2, top_k, ok, ob, ob + no, ob + 2 * no, ok + no, oc, (void*)h->own);
     st.launched();
     if (rc != RQ_OK) return rc;
     st.down(out_b, ob, no * 8);

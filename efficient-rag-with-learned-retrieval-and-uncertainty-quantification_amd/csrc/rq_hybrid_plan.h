@@ -57,6 +57,16 @@ static inline int hybrid_check_fuse(const void* h, const void* sp_rows, const vo
     return RQ_OK;
 }
 
+// rq_hybrid_set_groups: one int32 per key, -1 = a group of its own, any other value >= 0 (the conventions of rq_sparse_set_groups).
+static inline int hybrid_check_groups(const void* h, const int32_t* key_group, int64_t n_keys, int64_t handle_keys) {
+    if (!h) return set_err(RQ_EINVAL, "null handle");
+    if (n_keys != handle_keys) return set_err(RQ_EINVAL, "n_keys %lld, the key space holds %lld keys", (long long)n_keys, (long long)handle_keys);
+    if (n_keys > 0 && !key_group) return set_err(RQ_EINVAL, "null key_group");
+    for (int64_t i = 0; i < n_keys; ++i)
+        if (key_group[i] < -1) return set_err(RQ_EINVAL, "key_group[%lld] is %d: a group id is -1 or not negative", (long long)i, key_group[i]);
+    return RQ_OK;
+}
+
 // The fuse kernel is instantiated for `pad` candidates, the count K1 + K2 rounded up to a power of two in 64 .. 2 048: the smallest
 // pools run a one-wave workgroup over 64 slots and do not pay for the sorts and the LDS of 2 048.
 static inline int hybrid_pad(int n_cand) {
@@ -71,6 +81,9 @@ static inline size_t hybrid_lds_bytes(int pad, bool fuse) {
     const size_t waves = (size_t)hybrid_threads(pad) / 64;
     return (size_t)pad * (fuse ? 8 + 1 + 16 + 4 : 8 + 1) + (fuse ? waves * 32 : 0);
 }
+
+// The grouped fuse kernel adds nothing: its third sort runs in the sort array, its keep flags in the flag bytes, both spent by then.
+static inline size_t hybrid_grouped_lds_bytes(int pad) { return hybrid_lds_bytes(pad, true); }
 
 // rq_sparse_score_rows*: 1 <= B <= 65535, 1 <= m <= RQ_MAX_SCORE_ROWS, non-null pointers; one thread per pair.
 static inline int hybrid_check_score_rows(const void* h, const void* q_indptr, int B, const void* rows, int m, const void* scores) {

@@ -26,6 +26,17 @@
 //   so an allowed document's score has the bits of the unmasked call, and a disallowed one is exactly the 0.0 that
 //   np.where(keep, scores, 0.0) writes before the score > 0 selection of the host definition.
 // The unmasked instantiation holds none of this (if constexpr): its code, counters and launches are those of the call before masks.
+//
+// Grouped calls (rq_sparse_set_groups, rq_sparse_topk_grouped*) run rq_sparse_tile_kernel<*, true> over tiles of
+// min(tile_docs, 4096) documents and rq_sparse_final_grouped_kernel: one document per group of the table (-1: a group of its own), the
+// definition of BM25Index._search_distinct.
+//   (c) after the accumulation and the mask pass (b) and before anything is counted, every document that is not the best of its group
+//       INSIDE THE TILE -- the larger (score bits, row) -- is set to 0.0.  Exact: a query's winner is the best document of its group
+//       everywhere, so it survives its own tile's collapse; and if k other group-bests of its tile ranked above it, k distinct groups
+//       would beat it globally.  So the tile's min(k, tile_docs) best group-bests hold every winner of the tile.
+//   The final kernel walks the tiles' candidates (a group at most once per tile) in ranked chunks and emits the first of every group.
+// Neither mechanism depends on the order in which threads arrive: the table slot ends at a maximum, the set entry at a minimum.
+// The ungrouped instantiations and rq_sparse_final_kernel hold none of this: same instructions as before the grouped calls.
 #include "rq_sparse_plan.h"
 #include "rq_sparse_select.h"
 #include "rq_sparse_handle.h"
@@ -53,6 +64,11 @@ struct SparseArgs {
     unsigned long long* masked; // tiles that left because their mask allows no document
     int32_t* out_rows;          // [B][k] of the whole call
     double* out_scores;
+    // grouped calls only (rq_sparse_tile_kernel<*, true>, rq_sparse_final_grouped_kernel)
+    const int32_t* groups;      // [n_docs], -1 = a group of its own
+    int group_log2;             // log2 of the collapse table's 2 x tile_docs slots
+    int32_t* out_count;         // [B] of the whole call
+    unsigned long long* final_chunks;   // the largest number of chunks one query's final walk took
 };
 
 // first position in [b, e) whose row is >= v (rows ascending)
@@ -79,9 +95,9 @@ struct SparseTileSrc {
     }
 };
 
-template <bool MASKED>
+template <bool MASKED, bool GROUPED>
 __global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_tile_kernel(SparseArgs a) {
-    extern __shared__ double s_acc[];   // [tile_docs]
+    extern __shared__ double s_acc[];   // [tile_docs]; grouped: then the collapse table, uint32 ids and int32 best indices [2 x tile_docs] each
     __shared__ int64_t s_lo[RQ_SPARSE_CHUNK], s_hi[RQ_SPARSE_CHUNK];
     __shared__ SparseSelShared s_sel;
     __shared__ unsigned s_n;
@@ -165,6 +181,49 @@ __global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_tile_kernel(Spars
             __syncthreads();
             for (int i = tid; i < nloc; i += RQ_SPARSE_THREADS)
                 if (!((s_words[i >> 5] >> (i & 31)) & 1u)) s_acc[i] = 0.0;
+        }
+    }
+    if constexpr (GROUPED) {
+        // (c): of every group, only the tile's best document -- the larger (score bits, row) -- keeps its score; the others score 0.0
+        // from here on, like the disallowed ones.  A slot of the table is claimed for a group id by atomicCAS (linear probing: at
+        // most nloc <= tile_docs groups in 2 x tile_docs slots), its value is raised to the local index of the best document by a CAS
+        // loop over keys read from s_acc, which nobody writes meanwhile: whatever the order of arrival, the slot ends at the maximum.
+        uint32_t* s_gid = reinterpret_cast<uint32_t*>(s_acc + a.tile_docs);
+        int* s_best = reinterpret_cast<int*>(s_gid + 2 * a.tile_docs);
+        const unsigned slots = 2u * (unsigned)a.tile_docs;
+        for (unsigned i = tid; i < slots; i += RQ_SPARSE_THREADS) { s_gid[i] = 0xFFFFFFFFu; s_best[i] = -1; }
+        __syncthreads();   // (and the mask pass above is complete)
+        for (int i = tid; i < nloc; i += RQ_SPARSE_THREADS) {
+            const double v = s_acc[i];
+            if (!(v > 0.0)) continue;
+            const int32_t g = a.groups[tile_lo + i];
+            if (g < 0) continue;   // a group of its own
+            unsigned s = sparse_group_hash((uint32_t)g, (unsigned)a.group_log2);
+            for (;;) {
+                const uint32_t prev = atomicCAS(&s_gid[s], 0xFFFFFFFFu, (uint32_t)g);
+                if (prev == 0xFFFFFFFFu || prev == (uint32_t)g) break;
+                s = (s + 1) & (slots - 1);
+            }
+            const uint64_t mine = (uint64_t)__double_as_longlong(v);
+            int cur = s_best[s];
+            for (;;) {
+                if (cur >= 0) {
+                    const uint64_t other = (uint64_t)__double_as_longlong(s_acc[cur]);
+                    if (other > mine || (other == mine && cur > i)) break;   // (cur == i cannot be: i is offered once)
+                }
+                const int prev = atomicCAS(&s_best[s], cur, i);
+                if (prev == cur) break;
+                cur = prev;
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < nloc; i += RQ_SPARSE_THREADS) {   // (a thread writes its own documents only and reads no other's score)
+            if (!(s_acc[i] > 0.0)) continue;
+            const int32_t g = a.groups[tile_lo + i];
+            if (g < 0) continue;
+            unsigned s = sparse_group_hash((uint32_t)g, (unsigned)a.group_log2);
+            while (s_gid[s] != (uint32_t)g) s = (s + 1) & (slots - 1);
+            if (s_best[s] != i) s_acc[i] = 0.0;
         }
     }
     const SparseTileSrc src{s_acc, nloc, (uint32_t)tile_lo};
@@ -269,11 +328,152 @@ __global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_final_kernel(Spar
     }
 }
 
+// the candidates of one query whose key lies strictly below a bound (the previous chunk's threshold); unbounded: all of them
+struct SparseBelowSrc {
+    SparseFinalSrc s;
+    bool bounded;
+    uint64_t b_hi;
+    uint32_t b_lo;
+    __device__ __forceinline__ int64_t size() const { return s.n; }
+    __device__ __forceinline__ bool get(int64_t i, uint64_t& hi, uint32_t& lo) const {
+        if (!s.get(i, hi, lo)) return false;
+        return !bounded || !sparse_key_ge(hi, lo, b_hi, b_lo);
+    }
+};
+
+// The final kernel of a grouped call, one workgroup per query.  The tiles' candidates hold a group at most once per tile; they are
+// walked in ranked chunks of at most RQ_SPARSE_GROUPED_CHUNK: the next-best chunk is cut out by the selection body (keys strictly
+// below the previous chunk's threshold), sorted by the bitonic body of rq_sparse_final_kernel, and walked in order -- a candidate is
+// emitted when its group is -1 or has not been walked before.  "Walked before" is an LDS set keyed by group id whose value is the
+// ORDER INDEX (chunk x chunk size + rank) of the group's first candidate, lowered by atomicMin: a minimum does not depend on the
+// order in which threads arrive.  A candidate is its group's first exactly when the set holds its own order index; the emitted ones
+// get their output position from a prefix sum over the chunk.  Every walked group either wins or has won, and the walk stops at k
+// winners: the set never holds more than k - 1 + one chunk of groups, half of its RQ_SPARSE_GROUPED_SET slots at the most.
+__global__ __launch_bounds__(RQ_SPARSE_THREADS) void rq_sparse_final_grouped_kernel(SparseArgs a) {
+    constexpr unsigned CH = RQ_SPARSE_GROUPED_CHUNK, SET = RQ_SPARSE_GROUPED_SET, PER = CH / RQ_SPARSE_THREADS;
+    static_assert(SET == 1u << 12 && CH % RQ_SPARSE_THREADS == 0 && 2 * (RQ_SPARSE_MAX_K + CH) <= SET, "the group set: 4 096 slots, at most half full");
+    __shared__ uint64_t s_bits[CH];
+    __shared__ int32_t s_rows[CH];
+    __shared__ int32_t s_grp[CH];
+    __shared__ uint32_t s_set_id[SET], s_set_ord[SET];
+    __shared__ SparseSelShared s_sel;
+    __shared__ unsigned s_n, s_wave[RQ_SPARSE_THREADS / 64];
+    const int tid = (int)threadIdx.x;
+    const int ql = (int)blockIdx.x;
+    const size_t qt = (size_t)ql * (size_t)a.tiles;
+    const int32_t* counts = a.counts + qt;
+    const SparseFinalSrc all{a.cand_bits + qt * (size_t)a.slot, a.cand_rows + qt * (size_t)a.slot, counts, a.tiles * (int64_t)a.slot, a.slot};
+    for (unsigned i = tid; i < SET; i += RQ_SPARSE_THREADS) { s_set_id[i] = 0xFFFFFFFFu; s_set_ord[i] = 0xFFFFFFFFu; }
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    unsigned mine = 0;
+    for (int64_t t = tid; t < a.tiles; t += RQ_SPARSE_THREADS) mine += (unsigned)counts[t];
+    if (mine) atomicAdd(&s_n, mine);
+    __syncthreads();
+    unsigned below = s_n;        // candidates not yet walked: < 2^31
+    unsigned emitted = 0, chunks = 0;
+    SparseBelowSrc src{all, false, 0, 0};
+    int32_t* orow = a.out_rows + (size_t)(a.q0 + ql) * (size_t)a.k;
+    double* osc = a.out_scores + (size_t)(a.q0 + ql) * (size_t)a.k;
+    while (below > 0 && emitted < (unsigned)a.k) {   // (uniform: every thread holds the same counts)
+        const unsigned want = below < CH ? below : CH;
+        __syncthreads();
+        if (tid == 0) s_n = 0;
+        uint64_t thr_hi = 0;
+        uint32_t thr_lo = 0;
+        if (below > want) sparse_select_threshold(src, want, s_sel, thr_hi, thr_lo);
+        __syncthreads();
+        for (int64_t i = tid; i < src.s.n; i += RQ_SPARSE_THREADS) {
+            uint64_t hi;
+            uint32_t lo;
+            if (!src.get(i, hi, lo) || !sparse_key_ge(hi, lo, thr_hi, thr_lo)) continue;
+            const unsigned j = atomicAdd(&s_n, 1u);
+            if (j < CH) { s_bits[j] = hi; s_rows[j] = (int32_t)lo; }
+        }
+        unsigned P = 1;
+        while (P < want) P <<= 1;
+        __syncthreads();
+        for (unsigned i = want + tid; i < P; i += RQ_SPARSE_THREADS) { s_bits[i] = 0; s_rows[i] = -1; }   // below every candidate
+        __syncthreads();
+        for (unsigned size = 2; size <= P; size <<= 1)
+            for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
+                for (unsigned t = tid; t < P / 2; t += RQ_SPARSE_THREADS) {
+                    const unsigned i = 2 * t - (t & (stride - 1)), j = i + stride;
+                    const uint64_t bi = s_bits[i], bj = s_bits[j];
+                    const int32_t ri = s_rows[i], rj = s_rows[j];
+                    const bool j_first = bj > bi || (bj == bi && rj > ri);
+                    if (((i & size) == 0) == j_first) { s_bits[i] = bj; s_bits[j] = bi; s_rows[i] = rj; s_rows[j] = ri; }
+                }
+                __syncthreads();
+            }
+        // the groups of the chunk (a candidate's row lies in [0, n_docs): the tile kernel wrote it), and their first order index
+        const unsigned base = chunks * CH;
+        for (unsigned i = tid; i < want; i += RQ_SPARSE_THREADS) {
+            const int32_t g = a.groups[s_rows[i]];
+            s_grp[i] = g;
+            if (g < 0) continue;
+            unsigned s = sparse_group_hash((uint32_t)g, 12);
+            for (;;) {
+                const uint32_t prev = atomicCAS(&s_set_id[s], 0xFFFFFFFFu, (uint32_t)g);
+                if (prev == 0xFFFFFFFFu || prev == (uint32_t)g) break;
+                s = (s + 1) & (SET - 1);
+            }
+            atomicMin(&s_set_ord[s], base + i);
+        }
+        __syncthreads();
+        // thread t owns ranks PER x t .. PER x t + PER - 1: keep flags, then their exclusive prefix sum over the workgroup
+        unsigned keep = 0, cnt = 0;
+        for (unsigned j = 0; j < PER; ++j) {
+            const unsigned i = PER * tid + j;
+            if (i >= want) break;
+            const int32_t g = s_grp[i];
+            bool first = g < 0;
+            if (!first) {
+                unsigned s = sparse_group_hash((uint32_t)g, 12);
+                while (s_set_id[s] != (uint32_t)g) s = (s + 1) & (SET - 1);
+                first = s_set_ord[s] == base + i;
+            }
+            if (first) { keep |= 1u << j; ++cnt; }
+        }
+        unsigned inc = cnt;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned v = __shfl_up(inc, o, 64);
+            if ((tid & 63) >= o) inc += v;
+        }
+        if ((tid & 63) == 63) s_wave[tid >> 6] = inc;
+        __syncthreads();
+        unsigned before = emitted + inc - cnt, kept = 0;
+        for (int w = 0; w < RQ_SPARSE_THREADS / 64; ++w) {
+            if (w < (tid >> 6)) before += s_wave[w];
+            kept += s_wave[w];
+        }
+        for (unsigned j = 0; j < PER; ++j) {
+            if (!((keep >> j) & 1u)) continue;
+            if (before < (unsigned)a.k) {
+                orow[before] = s_rows[PER * tid + j];
+                osc[before] = __longlong_as_double((long long)s_bits[PER * tid + j]);
+            }
+            ++before;
+        }
+        emitted = emitted + kept < (unsigned)a.k ? emitted + kept : (unsigned)a.k;
+        src.bounded = true;
+        src.b_hi = thr_hi;
+        src.b_lo = thr_lo;
+        below -= want;
+        ++chunks;
+    }
+    for (unsigned i = emitted + tid; i < (unsigned)a.k; i += RQ_SPARSE_THREADS) { orow[i] = -1; osc[i] = 0.0; }
+    if (tid == 0) {
+        a.out_count[a.q0 + ql] = (int32_t)emitted;
+        atomicMax(a.final_chunks, (unsigned long long)chunks);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 static void sparse_free(rq_sparse* h) {
     if (h->own) (void)hipStreamDestroy(h->own);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    free_dev(h->d_indptr, h->d_rows, h->d_contrib, h->ws, h->d_skipped);   // (d_skipped holds both tile counters)
+    free_dev(h->d_indptr, h->d_rows, h->d_contrib, h->ws, h->d_skipped, h->d_groups);   // (d_skipped holds all three counters)
     delete h;
 }
 
@@ -295,7 +495,7 @@ extern "C" rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, con
     h->n_docs = n_docs;
     h->nnz = indptr[n_tokens];
     const size_t nnz = (size_t)h->nnz, pad = nnz ? nnz : 1;   // (empty lists: the kernels still get valid pointers)
-    if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&h->d_skipped, 2 * sizeof(unsigned long long)) != hipSuccess ||
+    if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&h->d_skipped, 3 * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc((void**)&h->d_indptr, (size_t)(n_tokens + 1) * 8) != hipSuccess || hipMalloc((void**)&h->d_rows, pad * 4) != hipSuccess ||
         hipMalloc((void**)&h->d_contrib, pad * 8) != hipSuccess) {
         (void)hipGetLastError();
@@ -305,9 +505,9 @@ extern "C" rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, con
     }
     if (hipMemcpy(h->d_indptr, indptr, (size_t)(n_tokens + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
         (nnz && (hipMemcpy(h->d_rows, rows, nnz * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(h->d_contrib, contrib, nnz * 8, hipMemcpyHostToDevice) != hipSuccess)) ||
-        hipMemset(h->d_skipped, 0, 2 * sizeof(unsigned long long)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)rq_sparse_tile_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, RQ_SPARSE_TILE_MAX * (int)sizeof(double)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)rq_sparse_tile_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, RQ_SPARSE_TILE_MAX * (int)sizeof(double)) != hipSuccess) {
+        hipMemset(h->d_skipped, 0, 3 * sizeof(unsigned long long)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)rq_sparse_tile_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RQ_SPARSE_TILE_MAX * (int)sizeof(double)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)rq_sparse_tile_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RQ_SPARSE_TILE_MAX * (int)sizeof(double)) != hipSuccess) {
         set_err(RQ_EHIP, "upload of the posting index to device %d failed", device_id);
         sparse_free(h);
         return nullptr;
@@ -324,13 +524,17 @@ extern "C" void rq_sparse_destroy(rq_sparse* h) {
 
 extern "C" int64_t rq_sparse_postings(const rq_sparse* h) { return h ? h->nnz : 0; }
 
-// Both device forms: d_mask_of == nullptr is the unmasked call.
+// Every device form: d_mask_of == nullptr is the unmasked call, d_count != nullptr the grouped one (its tiles are
+// sparse_grouped_tile(tile_docs) wide, its tile kernel carries the collapse table, its final kernel is the grouped one).
 static int sparse_topk_launch(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
-                              const uint32_t* d_masks, int n_masks, const int32_t* d_mask_of, int32_t* d_rows, double* d_scores, void* stream) {
+                              const uint32_t* d_masks, int n_masks, const int32_t* d_mask_of, int32_t* d_rows, double* d_scores, void* stream,
+                              int32_t* d_count = nullptr) {
     if (n_q_tokens < 0 || (n_q_tokens > 0 && !d_q_tokens)) return set_err(RQ_EINVAL, "n_q_tokens %lld negative, or tokens without an array", (long long)n_q_tokens);
     RQ_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    const SparsePlan p = sparse_plan(h->n_docs, h->tile_docs, B, k, h->cand_cap);
+    const bool grouped = d_count != nullptr;
+    const int tile = grouped ? sparse_grouped_tile(h->tile_docs) : h->tile_docs;
+    const SparsePlan p = sparse_plan(h->n_docs, tile, B, k, h->cand_cap);
     if (p.bytes() > h->ws_bytes) {   // growing waits for the device once: an earlier call may still read the old block
         HIPCHK(hipDeviceSynchronize());
         free_dev(h->ws);
@@ -341,12 +545,12 @@ static int sparse_topk_launch(rq_sparse* h, const int64_t* d_q_indptr, const int
         }
         h->ws_bytes = p.bytes();
     }
-    HIPCHK(hipMemsetAsync(h->d_skipped, 0, 2 * sizeof(unsigned long long), s));   // both tile counters
+    HIPCHK(hipMemsetAsync(h->d_skipped, 0, 3 * sizeof(unsigned long long), s));   // both tile counters and the chunk count
     SparseArgs a;
     a.indptr = h->d_indptr; a.rows = h->d_rows; a.contrib = h->d_contrib;
     a.n_tokens = h->n_tokens; a.n_docs = h->n_docs; a.tiles = p.tiles;
     a.q_indptr = d_q_indptr; a.q_tokens = d_q_tokens; a.n_q_tokens = n_q_tokens;
-    a.k = k; a.slot = p.slot; a.tile_docs = h->tile_docs;
+    a.k = k; a.slot = p.slot; a.tile_docs = tile;
     a.cand_bits = (uint64_t*)h->ws;
     a.cand_rows = (int32_t*)(h->ws + p.rows_offset());
     a.counts = (int32_t*)(h->ws + p.counts_offset());
@@ -355,6 +559,9 @@ static int sparse_topk_launch(rq_sparse* h, const int64_t* d_q_indptr, const int
     a.mask_words = sparse_mask_words(h->n_docs);
     a.masked = h->d_skipped + 1;
     a.out_rows = d_rows; a.out_scores = d_scores;
+    a.groups = h->d_groups; a.out_count = d_count; a.final_chunks = h->d_skipped + 2;
+    a.group_log2 = 0;
+    while ((1 << a.group_log2) < sparse_grouped_slots(tile)) ++a.group_log2;
     h->ev_used = 0;
     const size_t n_ev = h->profile ? 1 + 2 * (size_t)p.rounds : 0;
     while (h->ev.size() < n_ev) {
@@ -365,19 +572,23 @@ static int sparse_topk_launch(rq_sparse* h, const int64_t* d_q_indptr, const int
     if (n_ev) HIPCHK(hipEventRecord(h->ev[0], s));
     for (int r = 0; r < p.rounds; ++r) {   // the rounds share the workspace: stream order keeps them apart
         a.q0 = p.round_first(r);
-        const SparseGrid g = sparse_grid(p, h->tile_docs, p.round_count(r, B));
+        const SparseGrid g = grouped ? sparse_grouped_grid(p, tile, p.round_count(r, B)) : sparse_grid(p, tile, p.round_count(r, B));
         if (p.tiles > 0) {
-            if (d_mask_of) hipLaunchKernelGGL(rq_sparse_tile_kernel<true>, dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
-            else hipLaunchKernelGGL(rq_sparse_tile_kernel<false>, dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
+            if (grouped && d_mask_of) hipLaunchKernelGGL((rq_sparse_tile_kernel<true, true>), dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
+            else if (grouped) hipLaunchKernelGGL((rq_sparse_tile_kernel<false, true>), dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
+            else if (d_mask_of) hipLaunchKernelGGL((rq_sparse_tile_kernel<true, false>), dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
+            else hipLaunchKernelGGL((rq_sparse_tile_kernel<false, false>), dim3(g.tile_x, g.tile_y), dim3(g.block), g.tile_lds, s, a);
         }
         if (n_ev) HIPCHK(hipEventRecord(h->ev[1 + 2 * (size_t)r], s));
-        hipLaunchKernelGGL(rq_sparse_final_kernel, dim3(g.final_x), dim3(g.block), 0, s, a);
+        if (grouped) hipLaunchKernelGGL(rq_sparse_final_grouped_kernel, dim3(g.final_x), dim3(g.block), 0, s, a);
+        else hipLaunchKernelGGL(rq_sparse_final_kernel, dim3(g.final_x), dim3(g.block), 0, s, a);
         if (n_ev) HIPCHK(hipEventRecord(h->ev[2 + 2 * (size_t)r], s));
     }
     h->ev_used = n_ev;
     HIPCHK(hipGetLastError());
     h->calls++;
     if (d_mask_of) h->masked_calls++;
+    if (grouped) h->grouped_calls++;
     h->rounds_last = p.rounds;
     h->tiles_last = p.tiles * (int64_t)B;
     return RQ_OK;
@@ -395,6 +606,40 @@ extern "C" int rq_sparse_topk_masked_device(rq_sparse* h, const int64_t* d_q_ind
     if (int rc = sparse_check_call(h, d_q_indptr, B, k, d_rows, d_scores)) return rc;
     if (int rc = sparse_check_masks(d_masks, n_masks, d_mask_of)) return rc;
     return sparse_topk_launch(h, d_q_indptr, d_q_tokens, B, n_q_tokens, k, d_masks, n_masks, d_mask_of, d_rows, d_scores, stream);
+}
+
+extern "C" int rq_sparse_set_groups(rq_sparse* h, const int32_t* groups, int64_t n_docs) {
+    if (int rc = sparse_check_groups(h, groups, n_docs, h ? h->n_docs : 0)) return rc;
+    RQ_ON_DEVICE(h);
+    if (!h->grouped_lds_set) {   // the grouped tile kernels: accumulators + collapse table, 96 KiB at the most
+        const int lds = (int)sparse_grouped_tile_lds(RQ_SPARSE_GROUPED_TILE_MAX);
+        HIPCHK(hipFuncSetAttribute((const void*)rq_sparse_tile_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute((const void*)rq_sparse_tile_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        h->grouped_lds_set = true;
+    }
+    int32_t* fresh = nullptr;
+    if (hipMalloc((void**)&fresh, (size_t)(n_docs ? n_docs : 1) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(RQ_ENOMEM, "no room for a group table of %lld documents on device %d", (long long)n_docs, h->device);
+    }
+    if (n_docs && hipMemcpy(fresh, groups, (size_t)n_docs * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(fresh);
+        return set_err(RQ_EHIP, "upload of the group table to device %d failed", h->device);
+    }
+    if (h->d_groups) {           // an earlier call may still read the table it replaces
+        HIPCHK(hipDeviceSynchronize());
+        free_dev(h->d_groups);
+    }
+    h->d_groups = fresh;
+    return RQ_OK;
+}
+
+extern "C" int rq_sparse_topk_grouped_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
+                                             const uint32_t* d_masks, int n_masks, const int32_t* d_mask_of, int32_t* d_rows, double* d_scores,
+                                             int32_t* d_count, void* stream) {
+    if (int rc = sparse_check_call(h, d_q_indptr, B, k, d_rows, d_scores)) return rc;
+    if (int rc = sparse_check_grouped(h->d_groups != nullptr, d_masks, n_masks, d_mask_of, d_count)) return rc;
+    return sparse_topk_launch(h, d_q_indptr, d_q_tokens, B, n_q_tokens, k, d_masks, n_masks, d_mask_of, d_rows, d_scores, stream, d_count);
 }
 
 extern "C" int rq_sparse_topk(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, int32_t* out_rows, double* out_scores) {
@@ -444,6 +689,35 @@ extern "C" int rq_sparse_topk_masked(rq_sparse* h, const int64_t* q_indptr, cons
     return st.finish();
 }
 
+extern "C" int rq_sparse_topk_grouped(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, const uint32_t* masks, int n_masks,
+                                      const int32_t* mask_of, int32_t* out_rows, double* out_scores, int32_t* out_count) {
+    if (int rc = sparse_check_call(h, q_indptr, B, k, out_rows, out_scores)) return rc;
+    if (int rc = sparse_check_grouped(h->d_groups != nullptr, masks, n_masks, mask_of, out_count)) return rc;
+    if (int rc = sparse_check_queries(q_indptr, q_tokens, B, h->n_tokens)) return rc;
+    if (mask_of)
+        if (int rc = sparse_check_mask_of(mask_of, B, n_masks)) return rc;
+    RQ_ON_DEVICE(h);
+    const int64_t nq = q_indptr[B];
+    const size_t mask_bytes = mask_of ? (size_t)n_masks * (size_t)sparse_mask_words(h->n_docs) * 4 : 0;
+    const size_t bytes[7] = {(size_t)(B + 1) * 8, (size_t)(nq ? nq : 1) * 4, (size_t)B * (size_t)k * 4, (size_t)B * (size_t)k * 8,
+                             mask_bytes ? mask_bytes : 4, (size_t)B * 4, (size_t)B * 4};
+    Stage st(h->own);
+    if (st.alloc(bytes, 7, "rq_sparse_topk_grouped") != RQ_OK) return st.code();
+    st.up(st.at<void>(0), q_indptr, bytes[0]);
+    if (nq) st.up(st.at<void>(1), q_tokens, (size_t)nq * 4);
+    if (mask_bytes) st.up(st.at<void>(4), masks, mask_bytes);
+    if (mask_of) st.up(st.at<void>(5), mask_of, bytes[5]);
+    if (st.code() != RQ_OK) return st.code();
+    const int rc = rq_sparse_topk_grouped_device(h, st.at<int64_t>(0), st.at<int32_t>(1), B, nq, k, mask_bytes ? st.at<uint32_t>(4) : nullptr, mask_of ? n_masks : 0,
+                                                 mask_of ? st.at<int32_t>(5) : nullptr, st.at<int32_t>(2), st.at<double>(3), st.at<int32_t>(6), (void*)h->own);
+    st.launched();
+    if (rc != RQ_OK) return rc;
+    st.down(out_rows, st.at<void>(2), bytes[2]);
+    st.down(out_scores, st.at<void>(3), bytes[3]);
+    st.down(out_count, st.at<void>(6), bytes[6]);
+    return st.finish();
+}
+
 extern "C" int rq_sparse_set_option(rq_sparse* h, const char* name, double value) {
     if (!h || !name) return set_err(RQ_EINVAL, "null argument");
     if (!strcmp(name, "tile_docs")) {
@@ -469,15 +743,17 @@ extern "C" double rq_sparse_get_option(const rq_sparse* h, const char* name) {
     if (!strcmp(name, "cand_cap")) return (double)h->cand_cap;
     if (!strcmp(name, "calls")) return (double)h->calls;
     if (!strcmp(name, "masked_calls")) return (double)h->masked_calls;
+    if (!strcmp(name, "grouped_calls")) return (double)h->grouped_calls;
+    if (!strcmp(name, "grouped")) return h->d_groups ? 1.0 : 0.0;
     if (!strcmp(name, "score_calls")) return (double)h->score_calls;
     if (!strcmp(name, "rounds_last")) return (double)h->rounds_last;
     if (!strcmp(name, "tiles_last")) return (double)h->tiles_last;
-    const bool masked_tiles = !strcmp(name, "masked_tiles_last");
-    if (masked_tiles || !strcmp(name, "skipped_tiles_last")) {   // waits for the device
+    const bool masked_tiles = !strcmp(name, "masked_tiles_last"), final_chunks = !strcmp(name, "final_chunks_last");
+    if (masked_tiles || final_chunks || !strcmp(name, "skipped_tiles_last")) {   // waits for the device
         DeviceGuard dg_(h->device);
         unsigned long long v = 0;
-        if (!dg_.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, h->d_skipped + (masked_tiles ? 1 : 0), sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
-            set_err(RQ_EHIP, "cannot read the %s-tile counter", masked_tiles ? "masked" : "skipped");
+        if (!dg_.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, h->d_skipped + (final_chunks ? 2 : masked_tiles ? 1 : 0), sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
+            set_err(RQ_EHIP, "cannot read the %s counter", final_chunks ? "final-chunk" : masked_tiles ? "masked-tile" : "skipped-tile");
             return -1.0;
         }
         return (double)v;

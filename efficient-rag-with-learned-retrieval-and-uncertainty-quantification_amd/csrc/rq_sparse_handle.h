@@ -12,7 +12,11 @@ struct rq_sparse {
     hipStream_t own = nullptr;
     char* ws = nullptr;                   // the one workspace (rq_sparse_plan.h SparsePlan)
     size_t ws_bytes = 0;
-    unsigned long long* d_skipped = nullptr;   // [2]: tiles of the last call without a posting, tiles whose mask allows no document
+    unsigned long long* d_skipped = nullptr;   // [3]: tiles of the last call without a posting, tiles whose mask allows no document,
+                                               //      the largest chunk count of a grouped call's final kernel
+    int32_t* d_groups = nullptr;          // [n_docs], rq_sparse_set_groups (null: no table)
+    bool grouped_lds_set = false;         // the grouped tile kernels may take their 96 KiB of dynamic LDS
+    int64_t grouped_calls = 0;            // rq_sparse_topk_grouped* (counted in calls too, and in masked_calls when they carry masks)
     int tile_docs = RQ_SPARSE_TILE_DEFAULT;
     int64_t cand_cap = 0;
     int64_t calls = 0, rounds_last = 0, tiles_last = 0;

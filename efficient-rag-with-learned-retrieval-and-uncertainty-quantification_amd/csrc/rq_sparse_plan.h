@@ -68,6 +68,40 @@ static inline int sparse_check_mask_of(const int32_t* mask_of, int B, int n_mask
     return RQ_OK;
 }
 
+// Grouped calls (rq_sparse_set_groups, rq_sparse_topk_grouped*).  The table: one int32 per document, -1 = a group of
+// its own, any other value >= 0 (ids need not be dense or small).
+#define RQ_SPARSE_GROUP_NONE (-1)
+#define RQ_SPARSE_GROUPED_TILE_MAX 4096           // accumulators (32 KiB) + the collapse table (64 KiB) = 96 KiB of the CU's 160 KiB
+#define RQ_SPARSE_GROUPED_CHUNK RQ_SPARSE_MAX_K   // candidates the grouped final kernel ranks and walks at a time
+#define RQ_SPARSE_GROUPED_SET (4 * RQ_SPARSE_MAX_K)   // slots of its group set: at most k winners + one chunk of groups, load <= 1/2
+static inline int sparse_check_groups(const void* h, const int32_t* groups, int64_t n_docs, int64_t handle_docs) {
+    if (!h) return set_err(RQ_EINVAL, "null handle");
+    if (n_docs != handle_docs) return set_err(RQ_EINVAL, "n_docs %lld, the index holds %lld documents", (long long)n_docs, (long long)handle_docs);
+    if (n_docs > 0 && !groups) return set_err(RQ_EINVAL, "null groups");
+    for (int64_t i = 0; i < n_docs; ++i)
+        if (groups[i] < RQ_SPARSE_GROUP_NONE) return set_err(RQ_EINVAL, "groups[%lld] is %d: a group id is -1 or not negative", (long long)i, groups[i]);
+    return RQ_OK;
+}
+// Both grouped entry points: the masked call's checks with mask_of == NULL legal (every query unrestricted), and the count array.
+static inline int sparse_check_grouped(bool has_table, const void* masks, int n_masks, const void* mask_of, const void* out_count) {
+    if (!has_table) return set_err(RQ_EINVAL, "no group table: call rq_sparse_set_groups first");
+    if (!out_count) return set_err(RQ_EINVAL, "null out_count");
+    if (n_masks < 0 || (n_masks > 0 && !masks)) return set_err(RQ_EINVAL, "n_masks %d negative, or masks without an array", n_masks);
+    if (!mask_of && n_masks > 0) return set_err(RQ_EINVAL, "masks without mask_of");
+    return RQ_OK;
+}
+// A grouped call runs in tiles of min(tile_docs, 4096) documents: the tile kernel keeps, beside the accumulators, an open-addressing
+// table of 2 x tile slots (a uint32 group id and the int32 local index of the group's best document: 8 B per slot) in dynamic LDS.
+static inline int sparse_grouped_tile(int tile_docs) { return std::min(tile_docs, RQ_SPARSE_GROUPED_TILE_MAX); }
+static inline int sparse_grouped_slots(int tile) { return 2 * tile; }
+static inline size_t sparse_grouped_tile_lds(int tile) { return (size_t)tile * sizeof(double) + (size_t)sparse_grouped_slots(tile) * 8; }
+// static LDS of the grouped final kernel: one chunk (score bits, rows, groups) and the group set (id + order index), beside the
+// selection body's histogram
+static inline size_t sparse_grouped_final_lds() { return (size_t)RQ_SPARSE_GROUPED_CHUNK * (8 + 4 + 4) + (size_t)RQ_SPARSE_GROUPED_SET * 8; }
+// slot of a group id in a table of `slots` (a power of two): the top bits of a multiplicative hash, so ids that share their low
+// bits (multiples of 8 192) or their high bits (values near 2^31) spread; collisions probe linearly
+static inline __host__ __device__ unsigned sparse_group_hash(uint32_t g, unsigned log2_slots) { return (g * 2654435761u) >> (32 - log2_slots); }
+
 static inline bool sparse_tile_ok(double v) {
     if (!(v >= RQ_SPARSE_TILE_MIN && v <= RQ_SPARSE_TILE_MAX)) return false;   // (NaN and values no int holds included)
     const int t = (int)v;
@@ -117,5 +151,12 @@ static inline SparseGrid sparse_grid(const SparsePlan& p, int tile_docs, int que
     g.tile_y = (unsigned)queries;
     g.final_x = (unsigned)queries;
     g.tile_lds = (size_t)tile_docs * sizeof(double);
+    return g;
+}
+// A grouped call: the plan is sparse_plan over sparse_grouped_tile(tile_docs), the grids are the same, the tile kernel's dynamic LDS
+// adds the collapse table, and the final kernel is the grouped one (static LDS: sparse_grouped_final_lds()).
+static inline SparseGrid sparse_grouped_grid(const SparsePlan& p, int tile, int queries) {
+    SparseGrid g = sparse_grid(p, tile, queries);
+    g.tile_lds = sparse_grouped_tile_lds(tile);
     return g;
 }

@@ -374,13 +374,20 @@ class BM25Index:
         """`search` with one passage per value of the documents' `distinct_by` field (extension, the sparse side of a grouped search):
         collapsed on the host over `get_scores`, in the order of `_select_topk` -- score descending, exact ties by DESCENDING row --
         keeping the first passage of every value.  A document without the field, or with "", is a group of its own."""
-        scores = self.get_scores(self._tokenize(query))
+        keep = None
         if allowed_ids is not None:
-            keep = np.zeros(len(scores), dtype=bool)
+            keep = np.zeros(len(self.doc_ids), dtype=bool)
             keep[[r for r in (self._row_of_id().get(d) for d in allowed_ids) if r is not None]] = True
+        rows, scores = self._distinct_rows(query, top_k, distinct_by, keep)
+        return [(self.doc_ids[i], float(scores[i])) for i in rows]
+
+    def _distinct_rows(self, query: str, top_k: int, distinct_by: str, keep: Optional[np.ndarray] = None) -> Tuple[List[int], np.ndarray]:
+        """The walk of `_search_distinct` in row space: (the kept rows in order, the score vector); `keep`: the allowed rows as booleans."""
+        scores = self.get_scores(self._tokenize(query))
+        if keep is not None:
             scores = np.where(keep, scores, 0.0)
         pos = np.flatnonzero(scores > 0)
-        out: List[Tuple[str, float]] = []
+        out: List[int] = []
         seen = set()
         for i in pos[np.lexsort((-pos, -scores[pos]))].tolist():
             if len(out) >= top_k:
@@ -390,8 +397,8 @@ class BM25Index:
                 if value in seen:
                     continue
                 seen.add(value)
-            out.append((self.doc_ids[i], float(scores[i])))
-        return out
+            out.append(i)
+        return out, scores
 
     def search(self, query: str, top_k: int = 10, *, allowed_ids=None, distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[Tuple[str, float]]:
         if self.bm25 is None or not self.doc_ids:
@@ -464,6 +471,25 @@ class BM25Index:
             c["sparse"] = _native.SparseIndex(c["indptr"], c["rows"], c["contrib"], len(c["tid"]), c["n_docs"], device=self.__dict__.get("sparse_device", 0))
         return c["sparse"]
 
+    def _group_table(self, c: Dict[str, Any], key: str) -> np.ndarray:
+        """One int32 per document for `distinct_by=key` (include/rq.h rq_sparse_set_groups): `_group_value` -> an id in first-seen order,
+        -1 for a document that is a group of its own.  Cached per key with the CSR arrays, dropped with them on every add."""
+        tables = c.setdefault("groups", {})
+        if key not in tables:
+            ids: Dict[Any, int] = {}
+            docs = self.documents
+            values = (_group_value(docs[d], key) for d in self.doc_ids)
+            tables[key] = np.fromiter((_native.GROUP_NONE if v is None else ids.setdefault(v, len(ids)) for v in values), np.int32, len(self.doc_ids))
+        return tables[key]
+
+    def _sparse_index_grouped(self, c: Dict[str, Any], key: str):
+        """`_sparse_index` with the group table of `key` on the device (it is sent when the key changes)."""
+        sp = self._sparse_index(c)
+        if c.get("sparse_group_key") != key:
+            sp.set_groups(self._group_table(c, key))
+            c["sparse_group_key"] = key
+        return sp
+
     def _query_csr(self, c: Dict[str, Any], queries: Sequence[str]) -> Tuple[List[int], List[int]]:
         """The queries as token ids of `c` in query order, with repetition, tokens the corpus does not hold left out: (offsets [B + 1], ids)."""
         tid = c["tid"]
@@ -511,7 +537,7 @@ class BM25Index:
         return (np.stack(words) if words else None), mask_of
 
     def search_batch_rows(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None,
-                          backend: str = "host", allowed_ids=None, allowed_ids_each=None) -> Tuple[np.ndarray, np.ndarray]:
+                          backend: str = "host", allowed_ids=None, allowed_ids_each=None, distinct_by: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
         """The selection of `search` for a whole batch, in ROW space: (rows int32 [B][top_k], -1 padded; scores float64 [B][top_k]).
         librq_bm25.so (include/rq_bm25.h) walks the posting lists of every query on the host cores -- term at a time, one float64
         accumulator per thread, the contributions added in query order (the same additions as get_scores: identical bits), top-k by a
@@ -523,7 +549,11 @@ class BM25Index:
         `allowed_ids` (ids or a `make_mask` result: one set for the whole batch) and `allowed_ids_each` (one such entry, or None for
         an unrestricted query, per query; entries that are the same object become one mask): query q is answered as
         `search(q, top_k, allowed_ids=entry)` answers it -- scored as ever, every passage outside its set then scores 0.0 before the
-        selection -- under every backend and on the numpy branch (rq_bm25_topk_masked, rq_sparse_topk_masked).  The two do not combine."""
+        selection -- under every backend and on the numpy branch (rq_bm25_topk_masked, rq_sparse_topk_masked).  The two do not combine.
+        `distinct_by` (a metadata key such as "title"): one passage per value of that field, query q answered as
+        `search(q, top_k, distinct_by=key, allowed_ids=entry)` answers it (`_search_distinct`); it combines with either filter keyword.
+        "gpu" collapses on the device (rq_sparse_topk_grouped over a group table built from `_group_value`, cached per key); "host" is the
+        loop of `_search_distinct` itself -- no host-core grouped scorer exists, `n_threads` and `use_native` do not apply to it."""
         if backend not in ("host", "gpu", "auto"):
             raise ValueError(f"backend must be 'host', 'gpu' or 'auto', not {backend!r}")
         B, k = len(queries), max(int(top_k), 1)
@@ -534,9 +564,21 @@ class BM25Index:
         if entries is not None:
             masks, mask_of = self._mask_table(entries)
             masked = {"masks": masks, "mask_of": mask_of}
+        on_device = backend == "gpu" or (backend == "auto" and _native.sparse_available())
+        if distinct_by is not None and not on_device:
+            n = len(self.doc_ids)
+            keep = [] if not masked or masks is None else [np.unpackbits(m.view(np.uint8), bitorder="little")[:n].astype(bool) for m in masks]
+            out_rows, out_scores = np.full((B, k), -1, np.int32), np.zeros((B, k))
+            for b, q in enumerate(queries):
+                sel, scores = self._distinct_rows(q, k, distinct_by, keep[mask_of[b]] if masked and mask_of[b] >= 0 else None)
+                out_rows[b, :len(sel)] = sel
+                out_scores[b, :len(sel)] = scores[sel]
+            return out_rows, out_scores
         c = self._csr()
         q_ptr, q_tok = self._query_csr(c, queries)
-        if backend == "gpu" or (backend == "auto" and _native.sparse_available()):
+        if on_device and distinct_by is not None:
+            return self._sparse_index_grouped(c, distinct_by).topk_grouped(np.asarray(q_ptr, np.int64), np.asarray(q_tok, np.int32), B, k, **masked)[:2]
+        if on_device:
             return self._sparse_index(c).topk(np.asarray(q_ptr, np.int64), np.asarray(q_tok, np.int32), B, k, **masked)
         if use_native and c["handle"] is None:
             raise _native.RqError("librq_bm25.so is not built: `make -C csrc` (or use_native=False for the numpy path)")
@@ -568,11 +610,12 @@ class BM25Index:
         return cache
 
     def search_batch(self, queries: Sequence[str], top_k: int = 10, *, n_threads: int = 0, use_native: Optional[bool] = None,
-                     backend: str = "host", allowed_ids=None, allowed_ids_each=None) -> List[List[Tuple[str, float]]]:
+                     backend: str = "host", allowed_ids=None, allowed_ids_each=None, distinct_by: Optional[str] = None) -> List[List[Tuple[str, float]]]:
         """`[self.search(q, top_k) for q in queries]`, scored as one job (search_batch_rows; `backend` as there).  With `allowed_ids`
         (one set for the batch) or `allowed_ids_each` (one entry per query, None = unrestricted), as there:
-        `[self.search(q, top_k, allowed_ids=entry_q) for q in queries]`."""
-        given = _given(allowed_ids=allowed_ids, allowed_ids_each=allowed_ids_each)
+        `[self.search(q, top_k, allowed_ids=entry_q) for q in queries]`; with `distinct_by`, as there: one passage per value of that
+        field, `[self.search(q, top_k, distinct_by=key, allowed_ids=entry_q) for q in queries]`."""
+        given = _given(allowed_ids=allowed_ids, allowed_ids_each=allowed_ids_each, distinct_by=distinct_by)
         if self.bm25 is None or not self.doc_ids or top_k <= 0:
             self._mask_entries(len(queries), allowed_ids, allowed_ids_each)      # (the keywords are still checked)
             return [[] for _ in queries]
@@ -1517,7 +1560,9 @@ class HybridRetriever:
     # `allowed_ids` (keyword-only extension on the per-query calls): only passages with these ids are ranked, on both sides -- the
     # `where` of a Chroma query.  The sparse side needs the ids themselves; the dense side also takes a DenseIndex.make_filter result.
     # `distinct_by` (keyword-only extension on the per-query calls, a metadata key such as "title"): one passage per value of that
-    # field on each side, and the fused list is collapsed once more by best hybrid score.  It stays on the per-query calls.
+    # field on each side, and the fused list is collapsed once more by best hybrid score.  The `*_batch` calls and `route_batch` take
+    # it too: query q's answer is that of the per-query call, value for value; with `allowed_ids`, not with
+    # `allowed_ids_each` or `complete_scores`.
     # The `*_batch` calls take `allowed_ids` (one set for the batch) or `allowed_ids_each` (one entry per query: ids, a `make_filter`
     # result, or None for an unrestricted query); query q's answer is that of the per-query call with that entry, value for value.
     # `per_group` (with `distinct_by`): `dense_search` alone passes it on (DenseIndex.search); the sparse side and the fused list
@@ -1547,12 +1592,24 @@ class HybridRetriever:
             return []
         return [(doc_id, score) for doc_id, score, _ in self.dense_index.search_threshold(query, threshold, max_results, allowed_ids=allowed_ids)]
 
-    def dense_search_batch(self, queries: Sequence[str], top_k: int = 20, *, allowed_ids=None, allowed_ids_each=None) -> List[List[Tuple[str, float]]]:
-        """`allowed_ids` / `allowed_ids_each`: ids, a `make_filter` result or -- this call has no sparse side -- a dense `RowFilter`."""
+    def dense_search_batch(self, queries: Sequence[str], top_k: int = 20, *, allowed_ids=None, allowed_ids_each=None,
+                           distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[List[Tuple[str, float]]]:
+        """`allowed_ids` / `allowed_ids_each`: ids, a `make_filter` result or -- this call has no sparse side -- a dense `RowFilter`.
+        `distinct_by`: one passage per value of that field, `[dense_search(q, top_k, distinct_by=key, allowed_ids=...) for q in queries]`
+        from one grouped search; it takes one filter for the batch (`allowed_ids`), not `allowed_ids_each`."""
+        self._check_distinct(distinct_by, per_group, False, allowed_ids_each, "dense_search_batch")
         entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each, dense_only=True)
         if self.dense_index is None:
             return [[] for _ in queries]
-        if entries is not None:
+        if distinct_by is not None:
+            e = None if entries is None else entries[0]
+            if isinstance(e, HybridFilter):
+                e = list(e.ids) if self._checked(e).dense is None else e.dense
+            if hasattr(self.dense_index, "search_batch"):
+                res = self.dense_index.search_batch(list(queries), top_k, distinct_by=distinct_by, **_given(allowed_ids=e))
+            else:
+                res = [self.dense_index.search(q, top_k, distinct_by=distinct_by, **_given(allowed_ids=e)) for q in queries]
+        elif entries is not None:
             # the dense half of a hybrid filter, or the entry as it came (DenseIndex makes one filter per distinct object of ids)
             each = [e if not isinstance(e, HybridFilter) else (list(e.ids) if self._checked(e).dense is None else e.dense) for e in entries]
             if hasattr(self.dense_index, "search_batch"):
@@ -1564,6 +1621,18 @@ class HybridRetriever:
         else:
             res = [self.dense_index.search(q, top_k) for q in queries]
         return [[(d, s) for d, s, _ in r] for r in res]
+
+    @staticmethod
+    def _check_distinct(distinct_by: Optional[str], per_group: Optional[int], complete_scores: bool, allowed_ids_each, what: str) -> None:
+        """What the batch calls refuse around `distinct_by=`: the refusals of the per-query calls, and one allowed set
+        per query -- the grouped dense search takes one filter for the batch."""
+        _refuse_per_group(per_group, what)
+        if distinct_by is None:
+            return
+        if complete_scores:
+            raise ValueError("distinct_by does not combine with complete_scores")
+        if allowed_ids_each is not None:
+            raise ValueError(f"{what}: distinct_by does not combine with allowed_ids_each (the grouped dense search takes one filter for the batch: allowed_ids)")
 
     # ---- one allowed set per query in the batch calls (extension; DESIGN.md 4.21) --------------------------------------------------
     def _filter_stamp(self) -> Tuple[int, int]:
@@ -1715,18 +1784,23 @@ class HybridRetriever:
         return self._fuse(self.bm25_search(query, retrieval_pool_size, **given), self.dense_search(query, retrieval_pool_size, **given), top_k)
 
     def hybrid_search_batch(self, queries: Sequence[str], top_k: int = 10, retrieval_pool_size: int = 50, *, complete_scores: bool = False,
-                            allowed_ids=None, allowed_ids_each=None) -> List[List[RetrievalResult]]:
+                            allowed_ids=None, allowed_ids_each=None, distinct_by: Optional[str] = None, per_group: Optional[int] = None) -> List[List[RetrievalResult]]:
         """All dense pools from one GPU batch, all BM25 pools from one pass over the posting lists on the host cores (librq_bm25.so);
         fusion per query.  `allowed_ids` (one set for the batch) / `allowed_ids_each` (one entry per query: ids, a `make_filter`
         result, or None) restrict both pools of each query: the answer is `hybrid_search(q, ..., allowed_ids=entry_q)`, value for value,
-        from one masked BM25 call and one per-query-filtered dense call."""
+        from one masked BM25 call and one per-query-filtered dense call.  `distinct_by` (a metadata key): one passage per value of that
+        field in both pools and in the fused list, `hybrid_search(q, ..., distinct_by=key, allowed_ids=...)` value for value -- on the
+        device route one grouped BM25 call, one grouped dense search and the grouped fusion (include/rq.h rq_sparse_topk_grouped_device,
+        rq_search_grouped_device, rq_hybrid_fuse_grouped_device)."""
+        self._check_distinct(distinct_by, per_group, complete_scores, allowed_ids_each, "hybrid_search_batch")
         entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
         if entries is None:
-            return self._hybrid_search_batch(queries, top_k, retrieval_pool_size, complete_scores)
-        return self._with_filters(entries, lambda each: self._hybrid_search_batch(queries, top_k, retrieval_pool_size, complete_scores, each))
+            return self._hybrid_search_batch(queries, top_k, retrieval_pool_size, complete_scores, None, distinct_by)
+        return self._with_filters(entries, lambda each: self._hybrid_search_batch(queries, top_k, retrieval_pool_size, complete_scores, each, distinct_by))
 
-    def _hybrid_search_batch(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None):
-        fused = self._fuse_batch_rows(queries, top_k, retrieval_pool_size, complete_scores, each)
+    def _hybrid_search_batch(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
+                             distinct_by: Optional[str] = None):
+        fused = self._fuse_batch_rows(queries, top_k, retrieval_pool_size, complete_scores, each, distinct_by)
         if fused is not None:
             ids, b, de, hy, count = fused
             idl, bl, dl, hl = ids.tolist(), b.tolist(), de.tolist(), hy.tolist()
@@ -1739,9 +1813,9 @@ class HybridRetriever:
                                                title=doc.title, metadata=doc.metadata))
                 out.append(res)
             return out
-        if each is not None:       # one side is not this module's own index class: the per-query calls
-            return [self.hybrid_search(q, top_k, retrieval_pool_size, complete_scores=complete_scores, allowed_ids=None if e is None else e.ids)
-                    for q, e in zip(queries, each)]
+        if each is not None or distinct_by is not None:       # one side is not this module's own index class: the per-query calls
+            return [self.hybrid_search(q, top_k, retrieval_pool_size, complete_scores=complete_scores, allowed_ids=None if e is None else e.ids,
+                                       **_given(distinct_by=distinct_by)) for q, e in zip(queries, each or [None] * len(queries))]
         if complete_scores:
             return [self.hybrid_search(q, top_k, retrieval_pool_size, complete_scores=True) for q in queries]
         dense, sparse = self._pools_batch(queries, retrieval_pool_size)
@@ -1772,26 +1846,31 @@ class HybridRetriever:
         return bm25_scores, dense_scores, doc_ids, texts
 
     def get_scores_for_router(self, query: str, num_passages: int = 20, *, retrieval_pool_size: int = 50, allowed_ids=None,
-                              complete_scores: bool = False) -> Tuple[List[float], List[float], List[str], List[str]]:
+                              complete_scores: bool = False, distinct_by: Optional[str] = None,
+                              per_group: Optional[int] = None) -> Tuple[List[float], List[float], List[str], List[str]]:
         """Reference :525-557 (its pools are always 50, :537); `retrieval_pool_size` is a keyword-only extension for
         BASELINE.json configs[4] (top-100 pools), `allowed_ids` restricts both pools to those passages, `complete_scores` fills in the
-        score a passage did not get from the other retriever (see `_pools_completed`)."""
-        given = _given(allowed_ids=allowed_ids, complete_scores=True if complete_scores else None)
+        score a passage did not get from the other retriever (see `_pools_completed`), `distinct_by` is `hybrid_search`'s: one passage
+        per value of that field."""
+        given = _given(allowed_ids=allowed_ids, complete_scores=True if complete_scores else None, distinct_by=distinct_by, per_group=per_group)
         return self._router_arrays(self.hybrid_search(query, top_k=num_passages, retrieval_pool_size=retrieval_pool_size, **given), num_passages)
 
     def get_scores_for_router_batch(self, queries: Sequence[str], num_passages: int = 20, *, retrieval_pool_size: int = 50, complete_scores: bool = False,
-                                    allowed_ids=None, allowed_ids_each=None):
+                                    allowed_ids=None, allowed_ids_each=None, distinct_by: Optional[str] = None, per_group: Optional[int] = None):
         """`[get_scores_for_router(q, ...) for q in queries]` with the pools of the whole batch computed at once.  When both sides are
         this module's own indexes the fusion itself runs on the whole batch in row space (`_fuse_batch_rows`); otherwise per query on the
         fused columns (no RetrievalResult objects in between).  `allowed_ids` / `allowed_ids_each` as in `hybrid_search_batch`: query
-        q's answer is `get_scores_for_router(q, ..., allowed_ids=entry_q)`."""
+        q's answer is `get_scores_for_router(q, ..., allowed_ids=entry_q)`.  `distinct_by` as in `hybrid_search_batch`: query q's answer
+        is `get_scores_for_router(q, ..., distinct_by=key)`."""
+        self._check_distinct(distinct_by, per_group, complete_scores, allowed_ids_each, "get_scores_for_router_batch")
         entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
         if entries is None:
-            return self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores)
-        return self._with_filters(entries, lambda each: self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, each))
+            return self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, None, distinct_by)
+        return self._with_filters(entries, lambda each: self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by))
 
-    def _scores_for_router_batch(self, queries: Sequence[str], num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None):
-        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores, each)
+    def _scores_for_router_batch(self, queries: Sequence[str], num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
+                                 distinct_by: Optional[str] = None):
+        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by)
         if fused is not None:
             ids, b, de, _, count = fused
             ids[np.arange(num_passages)[None, :] >= count[:, None]] = ""
@@ -1799,9 +1878,10 @@ class HybridRetriever:
             documents = self.documents                      # (texts are read from the store at call time, as the per-query path does)
             texts = [[documents[d].text if d else "" for d in row] for row in idl]
             return list(zip(b.tolist(), de.tolist(), idl, texts))
-        if each is not None:       # one side is not this module's own index class: the per-query calls
+        if each is not None or distinct_by is not None:       # one side is not this module's own index class: the per-query calls
             return [self.get_scores_for_router(q, num_passages, retrieval_pool_size=retrieval_pool_size, complete_scores=complete_scores,
-                                               allowed_ids=None if e is None else e.ids) for q, e in zip(queries, each)]
+                                               allowed_ids=None if e is None else e.ids, **_given(distinct_by=distinct_by))
+                    for q, e in zip(queries, each or [None] * len(queries))]
         if complete_scores:
             return [self.get_scores_for_router(q, num_passages, retrieval_pool_size=retrieval_pool_size, complete_scores=True) for q in queries]
         dense, sparse = self._pools_batch(queries, retrieval_pool_size)
@@ -1834,27 +1914,30 @@ class HybridRetriever:
             raise _native.RqError(f"router_backend='gpu': {reason}")
         return reason is None
 
-    def _router_columns(self, queries: Sequence[str], num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list]):
+    def _router_columns(self, queries: Sequence[str], num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list],
+                        distinct_by: Optional[str] = None):
         """The columns `get_scores_for_router_batch` hands the router, as arrays: ids [B][P] ("" = padding), b, d float64 [B][P]."""
-        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores, each)
+        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by)
         if fused is not None:
             ids, b, de, _, count = fused
             ids[np.arange(num_passages)[None, :] >= count[:, None]] = ""
             return ids, b, de
-        cols = self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, each)
+        cols = self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by)
         ids = np.empty((len(cols), num_passages), dtype=object)
         for q, c in enumerate(cols):
             ids[q, :] = c[2]
         return ids, np.array([c[0] for c in cols], np.float64).reshape(len(cols), num_passages), np.array([c[1] for c in cols], np.float64).reshape(len(cols), num_passages)
 
-    def _route_batch(self, queries: Sequence[str], router, top_k: int, num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None):
+    def _route_batch(self, queries: Sequence[str], router, top_k: int, num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
+                     distinct_by: Optional[str] = None):
         bm, dn = self.bm25_index, self.dense_index
         r = min(int(top_k), int(num_passages))
         usable = isinstance(bm, BM25Index) and isinstance(dn, DenseIndex)
         if self._route_on_device(router, num_passages, retrieval_pool_size, usable):
-            ids, b, de, w, h, count = self._fuse_batch_device(list(queries), num_passages, retrieval_pool_size, complete_scores, each, route=(router, r))
+            ids, b, de, w, h, count = self._fuse_batch_device(list(queries), num_passages, retrieval_pool_size, complete_scores, each, route=(router, r),
+                                                              distinct_by=distinct_by)
         else:
-            ids, cb, cd = self._router_columns(queries, num_passages, retrieval_pool_size, complete_scores, each)
+            ids, cb, cd = self._router_columns(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by)
             keys = np.where(ids != "", np.arange(num_passages, dtype=np.int32)[None, :], -1)
             _, b, de, w, h, pos, count = router.rerank(keys, cb, cd, np.full(len(queries), num_passages), r)
             ids = np.take_along_axis(ids, np.where(pos >= 0, pos, 0).astype(np.int64), 1)
@@ -1870,23 +1953,26 @@ class HybridRetriever:
         return out, w
 
     def route_batch(self, queries: Sequence[str], router, top_k: int = 10, *, num_passages: int = 20, retrieval_pool_size: int = 50, complete_scores: bool = False,
-                    allowed_ids=None, allowed_ids_each=None, return_weights: bool = False):
+                    allowed_ids=None, allowed_ids_each=None, return_weights: bool = False, distinct_by: Optional[str] = None, per_group: Optional[int] = None):
         """Retrieve, gate and rerank a batch: the loop of reference experiments/run_evaluation.py:165-184 as one call.  For every
         question the `num_passages` fused passages of `get_scores_for_router` are weighted by `router` (a `router.RouterGate`) and
         reordered by h = w*dense + (1 - w)*bm25; the first `top_k` real passages come back, best first, `hybrid_score` = h.  Question
         q's answer is the host gate's rerank of `get_scores_for_router(q, num_passages, ...)`'s columns, with the same filters and
         `complete_scores`.  `return_weights=True` adds the gate weights, float64 [B][top_k] (0.0 beyond a question's results).
-        Where it runs is `router_backend`'s choice."""
+        `distinct_by`: the fused passages are `get_scores_for_router(q, ..., distinct_by=key)`'s, one per value of that field; the
+        rerank is unchanged.  Where it runs is `router_backend`'s choice."""
         queries = list(queries)
+        self._check_distinct(distinct_by, per_group, complete_scores, allowed_ids_each, "route_batch")
         if int(num_passages) < 1 or int(top_k) < 1:
             raise ValueError(f"num_passages {num_passages} and top_k {top_k} must be at least 1")
         if not queries:
             return ([], np.zeros((0, min(int(top_k), int(num_passages))))) if return_weights else []
         entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
         if entries is None:
-            out, w = self._route_batch(queries, router, top_k, int(num_passages), retrieval_pool_size, complete_scores)
+            out, w = self._route_batch(queries, router, top_k, int(num_passages), retrieval_pool_size, complete_scores, None, distinct_by)
         else:
-            out, w = self._with_filters(entries, lambda each: self._route_batch(queries, router, top_k, int(num_passages), retrieval_pool_size, complete_scores, each))
+            out, w = self._with_filters(entries, lambda each: self._route_batch(queries, router, top_k, int(num_passages), retrieval_pool_size, complete_scores, each,
+                                                                                distinct_by))
         return (out, w) if return_weights else out
 
     def route(self, query: str, router, top_k: int = 10, **keywords):
@@ -1957,8 +2043,19 @@ class HybridRetriever:
             ks["map"] = _native.HybridMap(ks["nb"], ks["dense_key"], ks["known"], device=device)
         return ks["map"]
 
+    def _key_groups(self, ks, key: str) -> np.ndarray:
+        """One int32 per key of the key space for `distinct_by=key`: the group of the document `self.documents` holds under the key's id
+        (what `_fuse` reads), -1 for a group of its own and for ids the store does not know.  Cached per key with the key space."""
+        tables = ks.setdefault("groups", {})
+        if key not in tables:
+            ids: Dict[Any, int] = {}
+            docs = self.documents
+            values = (_group_value(docs[d], key) if d in docs else None for d in ks["ids"].tolist())
+            tables[key] = np.fromiter((_native.GROUP_NONE if v is None else ids.setdefault(v, len(ids)) for v in values), np.int32, len(ks["ids"]))
+        return tables[key]
+
     def _fuse_batch_device(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
-                           route: Optional[tuple] = None):
+                           route: Optional[tuple] = None, distinct_by: Optional[str] = None):
         """`_fuse_batch_rows` with both pools left where they are drawn: token ids and query vectors go down, rq_sparse_topk_device and
         rq_search_device (with its fixup) fill the pools in HBM, `complete_scores` adds rq_hybrid_missing_device and the two row-scoring
         calls, rq_hybrid_fuse_device ranks, and one copy brings [B][top_k] keys, scores and the counts back.  Same return value.
@@ -1967,7 +2064,11 @@ class HybridRetriever:
         are already filtered fuse as they are.
         `route` = (router.RouterGate, top_r): the fused block stays on the device, rq_router_rerank_device runs on the same stream
         over its keys, b, d and counts, and the one copy brings [B][top_r] up instead; the return value is then
-        (ids, b, d, w, h -- [B][top_r] -- and count [B])."""
+        (ids, b, d, w, h -- [B][top_r] -- and count [B]).
+        `distinct_by` (never with `complete_scores`, `each` then holds one filter for the whole batch): the sparse pool
+        comes from rq_sparse_topk_grouped_device, the dense pool from rq_search_grouped_device (with its fixup) under that one filter,
+        and rq_hybrid_fuse_grouped_device ranks all candidates and keeps the first of every group; the rest runs as it is.  Each stage
+        has a group table of its own: BM25 documents, dense rows (`_push_groups`), keys (`_key_groups`)."""
         import torch
         bm, dn = self.bm25_index, self.dense_index
         B, k, K1 = len(queries), int(top_k), max(int(retrieval_pool_size), 1)
@@ -1992,7 +2093,11 @@ class HybridRetriever:
                     # (torch has no arithmetic on uint32 and needs none: the words travel as int32)
                     masked = {"d_masks": None if masks is None else torch.from_numpy(masks.view(np.int32)).to(dev),
                               "n_masks": 0 if masks is None else len(masks), "d_mask_of": torch.from_numpy(mask_of).to(dev)}
-                sp.topk_device(d_ptr, d_tok, B, len(q_tok), K1, d_sp_rows, d_sp_scores, stream=s, **masked)
+                if distinct_by is not None:
+                    sp = bm._sparse_index_grouped(c, distinct_by)
+                    sp.topk_grouped_device(d_ptr, d_tok, B, len(q_tok), K1, d_sp_rows, d_sp_scores, torch.empty((B,), device=dev, dtype=torch.int32), stream=s, **masked)
+                else:
+                    sp.topk_device(d_ptr, d_tok, B, len(q_tok), K1, d_sp_rows, d_sp_scores, stream=s, **masked)
             else:
                 d_sp_rows.fill_(-1)
                 d_sp_scores.zero_()
@@ -2007,7 +2112,14 @@ class HybridRetriever:
                 d_de_rows = torch.empty((B, K2), device=dev, dtype=torch.int64)
                 d_de_scores = torch.empty((B, K2), device=dev, dtype=torch.float32)
                 d_status = torch.empty((B,), device=dev, dtype=torch.int32)
-                if each is not None:
+                if distinct_by is not None:
+                    dn._push_groups(distinct_by)
+                    flt = None if each is None or each[0] is None else each[0].dense
+                    d_groups = torch.empty((B, K2), device=dev, dtype=torch.int32)
+                    dn._index.search_grouped_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, d_groups, None, d_status, s, row_filter=flt)
+                    if bool(d_status.any()):                                   # fewer than K2 groups in the first rung, or no certificate
+                        dn._index.search_grouped_fixup_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, d_groups, None, d_status, s, row_filter=flt)
+                elif each is not None:
                     filters = [None if e is None else e.dense for e in each]
                     dn._index.search_filtered_each_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, filters, s)
                     if bool(d_status.any()):
@@ -2034,8 +2146,15 @@ class HybridRetriever:
             n = B * k
             block = torch.empty((7 * n + B,), device=dev, dtype=torch.int32)
             scores = block[: 6 * n].view(torch.float64)
-            hm.fuse_device(d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B, K1, K2, k, block[6 * n: 7 * n], scores[:n], scores[n: 2 * n], scores[2 * n:],
-                           None, block[7 * n:], s, **extra)
+            if distinct_by is not None:
+                if ks.get("map_group_key") != distinct_by:
+                    hm.set_groups(self._key_groups(ks, distinct_by))
+                    ks["map_group_key"] = distinct_by
+                hm.fuse_grouped_device(d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B, K1, K2, k, block[6 * n: 7 * n], scores[:n], scores[n: 2 * n],
+                                       scores[2 * n:], None, block[7 * n:], s)
+            else:
+                hm.fuse_device(d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B, K1, K2, k, block[6 * n: 7 * n], scores[:n], scores[n: 2 * n], scores[2 * n:],
+                               None, block[7 * n:], s, **extra)
             if route is not None:
                 gate, r = route
                 m = B * r
@@ -2054,7 +2173,8 @@ class HybridRetriever:
         return (ks["ids"][np.where(keys >= 0, keys, 0)], sc[:n].reshape(B, k), sc[n: 2 * n].reshape(B, k), sc[2 * n:].reshape(B, k),
                 host[7 * n:].astype(np.int64))
 
-    def _fuse_batch_rows(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool = False, each: Optional[list] = None):
+    def _fuse_batch_rows(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool = False, each: Optional[list] = None,
+                         distinct_by: Optional[str] = None):
         """`_fuse_columns` for every query of the batch at once, on integer keys: same candidates (union of both pools in first-seen
         order -- BM25 pool, then dense pool -- ids unknown to `self.documents` dropped), same float64 arithmetic (`max(...) or 1` over all
         candidates, hybrid = (b/max_b + d/max_d)/2), same stable descending sort, first top_k.  Returns (ids [B][top_k] object,
@@ -2066,13 +2186,29 @@ class HybridRetriever:
         `each` (one HybridFilter or None per query, from `_with_filters`): the sparse pool comes from the masked `search_batch_rows`,
         the dense pool from ONE per-query-filtered call (`DenseIndex._search_rows(each=...)`) over vectors embedded on the host, as the
         per-query filtered calls embed them; the rest is untouched -- a candidate comes from a filtered pool, its missing score is
-        the plain score of that pair."""
+        the plain score of that pair.
+        `distinct_by` (never with `complete_scores`; `each` then holds one filter for the whole batch): on the host route the sparse
+        pools come from `search_batch(distinct_by=)`, the dense pools from the grouped `search_batch(distinct_by=)`, and `_fuse(...,
+        distinct_by=)` runs per query -- the per-query call's own steps; the device route is `_fuse_batch_device`'s."""
         bm, dn = self.bm25_index, self.dense_index
         if not (isinstance(bm, BM25Index) and isinstance(dn, DenseIndex)) or len(queries) == 0 or top_k <= 0:
             return None
         if self._fuse_on_device(top_k, retrieval_pool_size):
-            return self._fuse_batch_device(list(queries), top_k, retrieval_pool_size, complete_scores, each)
+            return self._fuse_batch_device(list(queries), top_k, retrieval_pool_size, complete_scores, each, distinct_by=distinct_by)
         B = len(queries)
+        if distinct_by is not None:
+            e = None if each is None else each[0]
+            sparse = bm.search_batch(list(queries), retrieval_pool_size, **self._sparse_kw(), distinct_by=distinct_by, **_given(allowed_ids=None if e is None else e.sparse))
+            dense_allowed = None if e is None else (list(e.ids) if e.dense is None else e.dense)
+            dense = [[(d, sc) for d, sc, _ in r] for r in dn.search_batch(list(queries), retrieval_pool_size, distinct_by=distinct_by, **_given(allowed_ids=dense_allowed))]
+            ids = np.full((B, top_k), "", dtype=object)
+            b, de, hy, count = np.zeros((B, top_k)), np.zeros((B, top_k)), np.zeros((B, top_k)), np.zeros(B, np.int64)
+            for q in range(B):
+                res = self._fuse(sparse[q], dense[q], top_k, None, distinct_by)
+                count[q] = len(res)
+                ids[q, :len(res)] = [r.doc_id for r in res]
+                b[q, :len(res)], de[q, :len(res)], hy[q, :len(res)] = [r.bm25_score for r in res], [r.dense_score for r in res], [r.hybrid_score for r in res]
+            return ids, b, de, hy, count
         ks = self._key_space()
         sparse_each = {} if each is None else {"allowed_ids_each": [None if e is None else e.sparse for e in each]}
         sp_rows, sp_scores = bm.search_batch_rows(list(queries), retrieval_pool_size, **self._sparse_kw(), **sparse_each)

@@ -551,7 +551,38 @@ int rq_search_group_members(rq_index* idx, const rq_filter* f, const float* quer
  *   workspace, no synchronisation; complete in stream order.  RQ_EINVAL unless 1 <= B <= 65535, 1 <= m <= RQ_MAX_SCORE_ROWS and
  *   non-null pointers.  rq_sparse_score_rows: blocking, host buffers, staged on the handle's stream like rq_sparse_topk, with its
  *   checks of the queries.  Read-only option "score_calls" (both entry points).
- * Not extended: distinct_by (it stays on the host), multi-device handles. */
+ * rq_sparse_set_groups / rq_sparse_topk_grouped / rq_sparse_topk_grouped_device: one document per GROUP, the batch
+ *   form of BM25Index.search(..., distinct_by=): behind the `distinct_by` keyword of the batch calls.
+ *   Table: rq_sparse_set_groups copies one int32 per document to the device (4 B per document of HBM).  -1 = a group of its own;
+ *     any other non-negative int32 is a group id, ids need not be dense or small.  RQ_EINVAL for a negative value other than -1 and
+ *     for an n_docs that is not the handle's.  A second call replaces the table (it waits for the device once).  Read-only option
+ *     "grouped": 1 when a table is set.
+ *   Definition (BM25Index._search_distinct): scores are added exactly as above, a document outside the query's allowed set scores
+ *     0.0, the documents with score > 0 are ordered by score descending and equal scores by DESCENDING row, that order is walked
+ *     keeping the first document of every group -- a -1 document is never collapsed -- and the first k kept documents are returned:
+ *     out_rows / out_scores as above, out_count [B] the number of results, which may be below k although more than k documents
+ *     score > 0.  Every row, score bit and count is the host definition's.
+ *   Arguments: those of the masked calls and out_count; mask_of == NULL with n_masks == 0 = every query unrestricted.  RQ_EINVAL
+ *     without a group table and for a null out_count; limits, clamping rules (tokens, offsets, a mask_of entry outside
+ *     [-1, n_masks)), workspace rule and stream rule are those of rq_sparse_topk_masked*.
+ *   Tile kernel: the kernel above instantiated with an in-tile collapse after the accumulation and the mask zeroing and before the
+ *     positives are counted: of every group only the tile's best document -- the larger (score bits, row) -- keeps its score, the
+ *     others are set to 0.0 (an LDS open-addressing table keyed by group id, 2 x tile slots of 8 B; a slot is claimed by atomicCAS and
+ *     raised to the best document by a CAS loop that compares keys: a maximum, whatever the order of arrival).  This is exact: a
+ *     query's winner is the best document of its group everywhere, so it survives its own tile's collapse, and if k other
+ *     group-bests of that tile ranked above it, k distinct groups would beat it globally -- a tile's min(k, tile) best group-bests
+ *     hold every winner of that tile.  A grouped call runs in tiles of min("tile_docs", 4096): accumulators + table = 96 KiB of
+ *     LDS at the most; results never depend on it.
+ *   Final kernel: a kernel of its own.  The tiles' candidates hold a group at most once per tile; they are walked in ranked chunks
+ *     of at most RQ_SPARSE_MAX_K (the selection body with a key bound strictly below the previous chunk's threshold, then the
+ *     bitonic sort), a candidate is emitted when its group is -1 or has not been walked before (an LDS set of group ids with the
+ *     order index of each group's first candidate, lowered by atomicMin), until k are emitted or the candidates run out.
+ *   The ungrouped calls keep their code, counters and launch count.  Read-only options: "grouped_calls" (counted in "calls" too, and
+ *     in "masked_calls" when mask_of is given), "final_chunks_last" (the largest number of chunks one query's walk took in the last
+ *     grouped call; waits for the device; 0 after any other call).
+ *   The per-query BM25Index.search with distinct_by (it stays on the host) remains the definition these calls are tested against.
+ * Not extended: per_group > 1, a host-core rq_bm25_topk_grouped (the host route is the loop of BM25Index._search_distinct),
+ *   multi-device handles. */
 typedef struct rq_sparse rq_sparse;
 #define RQ_SPARSE_MAX_K 1024
 rq_sparse* rq_sparse_create(int device_id, const int64_t* indptr, const int32_t* rows, const double* contrib, int64_t n_tokens, int64_t n_docs);
@@ -564,6 +595,12 @@ int rq_sparse_topk_masked(rq_sparse* h, const int64_t* q_indptr, const int32_t* 
                           const int32_t* mask_of, int32_t* out_rows, double* out_scores);
 int rq_sparse_topk_masked_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
                                  const uint32_t* d_masks, int n_masks, const int32_t* d_mask_of, int32_t* d_rows, double* d_scores, void* stream);
+int rq_sparse_set_groups(rq_sparse* h, const int32_t* groups, int64_t n_docs);
+int rq_sparse_topk_grouped(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, int k, const uint32_t* masks, int n_masks,
+                           const int32_t* mask_of, int32_t* out_rows, double* out_scores, int32_t* out_count);
+int rq_sparse_topk_grouped_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, int k,
+                                  const uint32_t* d_masks, int n_masks, const int32_t* d_mask_of, int32_t* d_rows, double* d_scores, int32_t* d_count,
+                                  void* stream);
 int rq_sparse_score_rows_device(rq_sparse* h, const int64_t* d_q_indptr, const int32_t* d_q_tokens, int B, int64_t n_q_tokens, const int32_t* d_rows,
                                 int m, double* d_scores, void* stream);
 int rq_sparse_score_rows(rq_sparse* h, const int64_t* q_indptr, const int32_t* q_tokens, int B, const int32_t* rows, int m, double* out_scores);
@@ -611,7 +648,20 @@ double rq_sparse_get_option(const rq_sparse* h, const char* name);
  *   is used from one thread.  Read-only options (rq_hybrid_get_option, -1 with a message for an unknown name): "calls", "fuse_calls",
  *   "missing_calls" (both entry points each), "nb", "n_dense", "n_keys".
  *   Filtered pools (rq_sparse_topk_masked_device, rq_search_filtered_each_device) fuse as they are: the fusion needs no filter of its own.
- * Not extended: MMR and grouping over the fused pool, distinct_by (it stays on the host), multi-device handles. */
+ * rq_hybrid_set_groups / rq_hybrid_fuse_grouped_device / rq_hybrid_fuse_grouped: the fusion with one candidate per GROUP (DESIGN.md
+ *   4.23), HybridRetriever._fuse(..., distinct_by=) for a batch.  rq_hybrid_set_groups copies key_group [n_keys] int32 to the device
+ *   (4 B per key; the conventions of rq_sparse_set_groups: -1 = a group of its own, any other value >= 0, RQ_EINVAL otherwise and for
+ *   an n_keys that is not the handle's; a second call replaces the table).  The fuse calls take the pool arguments of rq_hybrid_fuse*
+ *   without the miss and extra arrays and give its outputs in its layout, so rq_router_rerank_device consumes them as they are.
+ *   Definition: validity, the merge of a key held by both pools, max_b, max_d and h are those above, taken over ALL valid
+ *   candidates -- the maxima before the collapse; the full ranking of the K1 + K2 candidates is computed (h descending, equal h by
+ *   ascending position, NaN as -inf), the first candidate of every group is kept, a -1 candidate always, and the first top_k kept
+ *   candidates are returned: count = min(kept, top_k).  One workgroup per query, the same instantiations; after the ranking the
+ *   (group, rank) pairs are sorted in the spent sort array, a pair whose predecessor has another group is its group's first rank, and
+ *   a prefix sum over the ranks' keep flags gives the output positions: no LDS beyond rq_hybrid_fuse_device's.  RQ_EINVAL without
+ *   a group table.  Read-only options "grouped" and "grouped_calls" (counted in "calls" and "fuse_calls" too).
+ *   The per-query HybridRetriever.hybrid_search with distinct_by (it stays on the host) remains the definition they are tested against.
+ * Not extended: MMR over the fused pool, grouping with the `complete_scores` rule, per_group > 1, multi-device handles. */
 typedef struct rq_hybrid rq_hybrid;
 #define RQ_HYBRID_MAX_CAND 2048
 rq_hybrid* rq_hybrid_create(int device_id, int64_t nb, int64_t n_dense, const int64_t* dense_key, const uint8_t* known, int64_t n_keys);
@@ -627,6 +677,12 @@ int rq_hybrid_fuse_device(rq_hybrid* h, const int32_t* d_sp_rows, const double* 
 int rq_hybrid_fuse(rq_hybrid* h, const int32_t* sp_rows, const double* sp_scores, const int64_t* de_rows, const float* de_scores, int B, int K1, int K2,
                    const int64_t* miss_dense, const float* extra_dense, const int32_t* miss_sparse, const double* extra_sparse, int top_k,
                    int32_t* out_keys, double* out_b, double* out_d, double* out_h, int32_t* out_pos, int32_t* out_count);
+int rq_hybrid_set_groups(rq_hybrid* h, const int32_t* key_group, int64_t n_keys);
+int rq_hybrid_fuse_grouped_device(rq_hybrid* h, const int32_t* d_sp_rows, const double* d_sp_scores, const int64_t* d_de_rows, const float* d_de_scores,
+                                  int B, int K1, int K2, int top_k, int32_t* d_keys, double* d_b, double* d_d, double* d_h, int32_t* d_pos, int32_t* d_count,
+                                  void* stream);
+int rq_hybrid_fuse_grouped(rq_hybrid* h, const int32_t* sp_rows, const double* sp_scores, const int64_t* de_rows, const float* de_scores, int B, int K1,
+                           int K2, int top_k, int32_t* out_keys, double* out_b, double* out_d, double* out_h, int32_t* out_pos, int32_t* out_count);
 
 /* ---- router gate: the learned gate and the rerank of the fused pool on the device (reference rag_uq/router.py:74-177 as the
  * evaluation loop applies it, experiments/run_evaluation.py:165-184) ------------------------------------------------
