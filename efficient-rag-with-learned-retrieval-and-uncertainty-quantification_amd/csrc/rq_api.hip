@@ -125,6 +125,7 @@ extern "C" void rq_index_destroy(rq_index* idx) {
         return;
     }
     DeviceGuard dg_(idx->device);
+    (void)flush_all(idx);   // calls gathered in an open bundle are scanned and finished: their results were promised
     (void)hipDeviceSynchronize();
     for (auto& kv : idx->ctx) free_ctx(kv.second);
     free_filters(idx);   // the filters nobody destroyed (include/rq.h rq_filter_destroy)
@@ -145,6 +146,10 @@ extern "C" int rq_index_set_row_offset(rq_index* idx, int64_t off) {
     if (!idx || off < 0) return set_err(RQ_EINVAL, "bad row offset");
     // keys carry the global row as a 32-bit field (0xffffffff is reserved): the whole shard must stay below it
     if ((uint64_t)off + (uint64_t)idx->n >= 0xffffffffull) return set_err(RQ_EUNSUPPORTED, "row_offset %lld + %lld rows reaches 2^32-1: row ids are 32-bit inside keys", (long long)off, (long long)idx->n);
+    if (idx->shards.empty() && bundles_open(idx)) {   // gathered calls return the row ids of the offset they were made under
+        RQ_ON_DEVICE(idx);
+        if (int r = flush_all(idx)) return r;
+    }
     idx->row_offset = off;
     return RQ_OK;
 }
@@ -253,6 +258,12 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
         return RQ_OK;
     }
     const std::string s(name);
+    // Calls gathered in an open bundle (rq_bundle_plan.h) are scanned late, by a plan made then: they are completed under the
+    // options they were made with before any option changes.
+    if (bundles_open(idx)) {
+        RQ_ON_DEVICE(idx);
+        if (int r = flush_all(idx)) return r;
+    }
     if (s == "row_pad") {   // stored row length: 384 (dim <= 384 only) or 768, while no row is stored
         if (v != 384 && v != RQ_DPAD) return set_err(RQ_EINVAL, "row_pad must be 384 or %d", RQ_DPAD);
         if (v == 384 && idx->dim > 384) return set_err(RQ_EINVAL, "row_pad 384 needs dim <= 384 (dim is %d)", idx->dim);
@@ -300,6 +311,8 @@ extern "C" int rq_set_option(rq_index* idx, const char* name, double v) {
     else if (s == "tail_local") idx->tail_local = (int)v != 0;   // A/B: 0 = every re-scored row's key goes to the query's global list
     else if (s == "use_hint") idx->use_hint = (int)v != 0;   // 0: rq_search_hint_next_device is ignored (A/B of the folded query preparation)
     else if (s == "scan_ahead") idx->scan_ahead = (int)v != 0;   // 0: a hinted batch is never scanned together with the call before it (A/B)
+    // bundles of scanned-ahead calls: 2 = pairs only, 4 = up to four calls per 256-query pass once a loop is steady
+    else if (s == "scan_bundle") { if (v != 2 && v != 4) return set_err(RQ_EINVAL, "scan_bundle must be 2 or 4"); if (int r = flush_all(idx)) return r; idx->scan_bundle = (int)v; }
     else if (s == "filter_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "filter_route must be -1 (rule), 1 (gather), 2 (scan) or 3 (exact)"); idx->filter_route = (int)v; }   // rq_filter_plan.h
     else if (s == "filter_each_key_cap") { if (!(v >= 0 && v <= (double)((int64_t)1 << 40))) return set_err(RQ_EINVAL, "filter_each_key_cap must be 0 (default) .. 2^40"); idx->each_key_cap = (int64_t)v; }   // test hook (rq_filter_each_plan.h: keys per ragged round)
     else if (s == "range_route") { if (v != -1 && v != 1 && v != 2 && v != 3) return set_err(RQ_EINVAL, "range_route must be -1 (rule), 1 (scan), 2 (gather) or 3 (exact)"); idx->range_route = (int)v; }   // rq_range_plan.h
@@ -320,7 +333,7 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
         double v = rq_get_option(idx->shards[0], name);
         if (o.rfind("max_", 0) == 0 || o.rfind("eps_", 0) == 0 || o == "scan8_row_err" || o == "scan8_suspended")
             for (rq_index* c : idx->shards) v = std::max(v, rq_get_option(c, name));
-        if (o == "scan8_used" || o == "hints_used") {   // counters: summed
+        if (o == "scan8_used" || o == "hints_used" || o == "bundles4") {   // counters: summed
             v = 0;
             for (rq_index* c : idx->shards) v += rq_get_option(c, name);
         }
@@ -339,6 +352,8 @@ extern "C" double rq_get_option(const rq_index* idx, const char* name) {
     if (s == "profile") return idx->profile;
     if (s == "fast_tail") return idx->fast_tail;
     if (s == "scan_ahead") return idx->scan_ahead;
+    if (s == "scan_bundle") return idx->scan_bundle;
+    if (s == "bundles4") return (double)idx->bundles4;   // 256-query passes of bundles of three or four calls
     if (s == "pipeline") return idx->pipeline;
     if (s == "profile_stride") return idx->profile_stride;
     if (s == "cu_count") return idx->cu_count;
@@ -559,6 +574,8 @@ extern "C" int rq_reset_timing(rq_index* idx) {
 extern "C" int rq_save(const rq_index* idx, const char* path) {
     if (!idx || !path) return set_err(RQ_EINVAL, "null argument");
     RQ_ON_DEVICE(idx);
+    if (idx->shards.empty())   // (open bundles are completed first, as before every call that touches the rows)
+        if (int r = flush_all(const_cast<rq_index*>(idx))) return r;
     const std::string meta = std::string(path) + ".meta", data = std::string(path) + ".f16";
     FILE* f = fopen(data.c_str(), "wb");
     if (!f) return set_err(RQ_EIO, "cannot write %s", data.c_str());

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/rq.h"
+#include "rq_bundle_plan.h"
 #include "rq_device.h"
 #include "rq_kernels.h"
 
@@ -94,23 +95,26 @@ struct StreamCtx {
     bool fused_pending = false;
     RqTailArgs fused_tail;
     int fused_B = 0;
-    // "pipeline" = 2 keeps the prepared queries of three consecutive calls apart (slot = call number mod 3): call i scans
-    // slot i, the tail of call i - 1 that rides with it reads slot i - 1, and the extra workgroups of the same launch prepare
-    // the hinted queries of call i + 1 into slot i + 1 (rq_search_hint_next_device)
-    QuerySet ring[3];                   // 64 slots each
+    // "pipeline" = 2 keeps the prepared queries of consecutive calls apart in a ring of RQ_RING_SLOTS slots of 64 queries, ONE
+    // allocation (rq_search.hip ring_slot): a lone call scans its slot while the tail that rides with it reads the slot before
+    // and the extra workgroups of the same launch prepare the hinted queries of the next call into the slot after
+    // (rq_search_hint_next_device); the members of a bundle take consecutive slots.  Which slot: rq_bundle_plan.h.
+    QuerySet ring;                      // RQ_RING_SLOTS x 64 slots
     const float* hint_q = nullptr;      // queries announced for the next fused call, not yet prepared
     int hint_B = 0;
     const float* prepped_q = nullptr;   // queries a launch has already prepared ...
     int prepped_B = 0, prepped_slot = -1;   // ... and the slot they are in
-    // option "scan_ahead": ONE 128-query pass has scanned this stream's last call (ring slot i) together with the batch it
-    // announced (slot i + 1), into the two halves of that call's workspace.  The first batch's tail waits in pair_tail; the
-    // second half's tail (pair_next, without k / m / outputs) belongs to the next call if it brings pair_q, pair_qB and
-    // pair_metric; anything else (another call, a flush) runs pair_tail alone and discards the second half.
-    bool pair_pending = false;
-    RqTailArgs pair_tail, pair_next;
-    int pair_B = 0;
-    const float* pair_q = nullptr;
-    int pair_qB = 0, pair_metric = -1;
+    // options "scan_ahead" / "scan_bundle": up to four consecutive calls of the stream are scanned by ONE pass into the quarters
+    // of workspace w[b_par] (rq_bundle_plan.h: state, roles, slots).  b_tail[j] / b_B[j]: member j's tail -- while members are
+    // only gathered, its k, m and outputs alone; once the pass is enqueued, complete.  The batch scanned ahead (member bs.n of an
+    // AHEAD bundle, b_tail without k / m / outputs) belongs to the next call if it brings await_q, await_B and await_metric;
+    // anything else (another call, a flush) completes the members that came and discards that quarter.
+    BundleState bs;
+    RqTailArgs b_tail[RQ_BUNDLE_MAX];
+    int b_B[RQ_BUNDLE_MAX] = {0, 0, 0, 0};
+    int b_par = 0, b_metric = -1;
+    const float* await_q = nullptr;
+    int await_B = 0, await_metric = -1;
     // where the stream's last call left its bin records (test hooks rq_debug_bin_records / rq_debug_pooled): query slot j of
     // that call is rec_bins + j * rec_stride; its passes covered rec_slots slots (rec_B of them valid, the rest pad).
     // rec_bins == nullptr: the last call ran no approximate scan (exact route, empty shard).
@@ -207,9 +211,10 @@ struct rq_index {
     int64_t wide1_checked[2] = {0, 0}, wide1_repaired[2] = {0, 0};
     int64_t repaired_total = 0;    // queries that came back uncertified and were repaired (any rung of the repair ladder)
     int64_t hints_used = 0;        // rq_search_hint_next_device: searches whose queries a launch before them prepared or scanned ahead
+    int64_t bundles4 = 0;          // 256-query passes of bundles of three or four calls ("scan_bundle")
     uint64_t scan_seq = 0;         // scan launches seen while profile = 1 (every profile_stride-th one is timed)
     // options
-    int ring = 3, prefetch = 1, kstage = 2, wide_batch = 1, wg_per_cu = 2, nt = -1, slack_bins = -1, profile = 0, profile_stride = 1, scan_nostore = 0, fast_tail = 1, pipeline = 0, tail_stop = 0, poison_cand = 0, poison_bins = 0, wide128 = 0, wide256 = 2, epi = 1, use_hint = 1, scan_ahead = 1, profile_legacy = 0, scan8 = 1, tail_local = 1, scan8_split = -1, wide8 = 1, wide256_8 = 31, bin_bound = 1, exact_mfma = 1, fused_nv = 0;
+    int ring = 3, prefetch = 1, kstage = 2, wide_batch = 1, wg_per_cu = 2, nt = -1, slack_bins = -1, profile = 0, profile_stride = 1, scan_nostore = 0, fast_tail = 1, pipeline = 0, tail_stop = 0, poison_cand = 0, poison_bins = 0, wide128 = 0, wide256 = 2, epi = 1, use_hint = 1, scan_ahead = 1, scan_bundle = 4, profile_legacy = 0, scan8 = 1, tail_local = 1, scan8_split = -1, wide8 = 1, wide256_8 = 31, bin_bound = 1, exact_mfma = 1, fused_nv = 0;
     double thr_mult8 = 1.25;       // int8 scan: threshold = P - thr_mult8 * bound (rq_tail_body.h)
     double eps = -1.0;
     std::map<hipStream_t, StreamCtx> ctx;
@@ -348,7 +353,8 @@ RQ_INTERNAL int ensure_filter_list(rq_filter* f);   // f->d_list: every allowed 
 RQ_INTERNAL int search_filtered_device(rq_index* idx, const rq_filter* f, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s);
 // one filter's queries down `route` (rq_filter_plan.h FilterRoute): what search_filtered_device does after its plan
 RQ_INTERNAL int run_filter_route(rq_index* idx, rq_filter* f, int route, const float* d_q, int B, int k, int metric, const SearchOut& out, hipStream_t s);
-RQ_INTERNAL int flush_all(rq_index* idx);   // launches every tail still waiting for a scan ("pipeline" = 2)
+RQ_INTERNAL int flush_all(rq_index* idx);   // completes every open bundle and launches every tail still waiting for a scan ("pipeline" = 2)
+RQ_INTERNAL bool bundles_open(const rq_index* idx);   // a stream holds calls whose scan is still to be enqueued (rq_bundle_plan.h GATHER)
 // rq_group.hip
 struct GroupOut {   // a grouped call's device outputs (keys may be null)
     float* scores; int64_t* rows; int32_t* groups; uint64_t* keys; int* status;

@@ -22,7 +22,8 @@ struct RqScanArgs {
     const float* qscale;
     const void* qlo;
     // fp16 128-query passes of rq_scan_wide.hip only: queries 64..127 of the block come from here instead of qh + 64 rows
-    // (the two 64-slot query buffers of a scanned-ahead pair, rq_api.hip "scan_ahead"); null = qh holds the whole block
+    // (the two ring slots of a scanned-ahead pair, which need not be neighbours in memory: rq_search.hip "scan_ahead"); null = qh
+    // holds the whole block, as it does for the 256-query pass of a bundle (an aligned quarter of the ring, rq_bundle_plan.h)
     const _Float16* qh_hi;
 };
 #define RQ_WGMAX_STRIDE 1024   // scan grids never exceed this many workgroups
@@ -176,10 +177,13 @@ hipError_t rq_scan_tail_launch(const RqScanArgs& sa, const RqTailArgs& ta, int t
 hipError_t rq_scan_narrow_tail_launch(const RqScanArgs& sa, const RqTailArgs& ta, int tail_B, const RqPrepArgs& pa, bool nt, int scan_grid, hipStream_t stream,
                                       hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 hipError_t rq_tail_launch(const RqTailArgs& a, int B, hipStream_t stream);
-// Tails of the two batches of a scanned-ahead pair (one 128-query pass, rq_api.hip "scan_ahead") in ONE launch, plus pa.nslots
-// workgroups that prepare the queries of the batch announced after them: grid = chunks x (B0 + B1) tail workgroups, then pa.
-// t0 / t1 must not share cand / rowcount / done / ovf.
-hipError_t rq_pair_tail_launch(const RqTailArgs& t0, int B0, const RqTailArgs& t1, int B1, const RqPrepArgs& pa, hipStream_t stream);
+// Tails of the n = 1..4 batches of a bundle (one 128- or 256-query pass, rq_bundle_plan.h) in ONE launch, each with its own k and
+// outputs, plus pa.nslots workgroups that prepare the queries of the batch announced after them: grid = chunks x (B[0] + .. +
+// B[n - 1]) tail workgroups, then pa.  No two of the tails may share cand / rowcount / done / ovf.
+#define RQ_BUNDLE_TAILS 4
+hipError_t rq_bundle_tail_launch(const RqTailArgs* t, const int* B, int n, const RqPrepArgs& pa, hipStream_t stream);
+// Two query preparations in ONE launch (a.nslots + b.nslots workgroups): a bundle member's own batch and the one it announces.
+hipError_t rq_prep2_queries_launch(const RqPrepArgs& a, const RqPrepArgs& b, hipStream_t stream);
 // chunk size rule shared by both launchers: 512-bin chunks while that keeps the grid around a thousand workgroups
 // (enough to spread the hits, few enough to be one dispatch round), else 2048-bin chunks
 static inline bool rq_tail_small_chunks(int64_t nbins, int B) { return ((nbins + 511) / 512) * B <= 1536; }

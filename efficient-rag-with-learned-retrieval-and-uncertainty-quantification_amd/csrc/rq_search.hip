@@ -1,10 +1,12 @@
 // rq_search.hip -- search orchestration of the single-device index: per-stream workspaces, the pipeline of one call
-// (run_pipeline: plan -> prepare -> scan passes -> tail), deferred tails and scanned-ahead pairs, the repair ladder, the
-// blocking host-buffer search.  What a call will do is decided by rq_plan.h; the kernels are rq_kernels.h's launchers.
+// (run_pipeline: plan -> prepare -> scan passes -> tail), deferred tails and bundles of scanned-ahead calls, the repair ladder,
+// the blocking host-buffer search.  What a call will do is decided by rq_plan.h, what it is to the calls before it on its stream by
+// rq_bundle_plan.h; the kernels are rq_kernels.h's launchers.
 #include "rq_plan.h"
 #include "rq_repair.h"
 
 static const size_t RQ_MAX_STREAM_CTX = 8;
+static_assert(RQ_BUNDLE_MAX == RQ_BUNDLE_TAILS, "a bundle's tails run in one rq_bundle_tail_launch");
 
 // ---- workspaces --------------------------------------------------------------------------------
 // (Re)allocate a device buffer of want_elems elements; the old contents are dropped.  hipFree waits for the
@@ -43,6 +45,13 @@ RqPrepArgs prep_args(const QuerySet& qs, const float* q, int dim, int B, int nsl
     pa.qh = qs.qh; pa.q32pad = qs.q32; pa.qnorm64 = qs.qn;
     if (with_int8) { pa.q8 = qs.q8; pa.qscale8 = qs.qscale8; pa.qeps8 = qs.qeps8; pa.q8lo = qs.q8lo; pa.qeps8s = qs.qeps8s; }
     return pa;
+}
+
+// Slot i of the stream's ring: 64 prepared queries.
+static QuerySet ring_slot(const StreamCtx& cx, int i) {
+    const QuerySet& r = cx.ring;
+    const size_t q = (size_t)i * 64, e = q * RQ_DPAD;
+    return QuerySet{r.qh + e, r.q32 + e, r.qn + q, r.q8 + e, r.qscale8 + q, r.qeps8 + q, r.q8lo + e, r.qeps8s + q};
 }
 
 static int ensure_ws(Workspace& w, int bpad, int64_t stride, int64_t m, size_t cand_elems) {
@@ -110,7 +119,7 @@ static void free_ws(Workspace& w) {
 void free_ctx(StreamCtx& c) {
     free_ws(c.w[0]);
     free_ws(c.w[1]);
-    for (QuerySet& r : c.ring) free_queries(r);
+    free_queries(c.ring);
     free_dev(c.grp_scores, c.grp_rows, c.grp_status, c.gm_scores, c.gm_rows);
     free_dev(c.each_tab, c.each_q, c.each_scores, c.each_rows, c.each_keys, c.each_status);
     if (c.each_pin) (void)hipHostFree(c.each_pin);
@@ -169,13 +178,14 @@ static int poison_bins(const rq_index* idx, uint2* bins, int64_t stride, int slo
     return RQ_OK;
 }
 
-// "scan_ahead": the half of a pair that was scanned ahead is not claimed (another call came, or a flush).  The first batch's
-// tail becomes an ordinary pending tail -- it rides with the next fused launch of the stream or runs at the flush -- and the
-// second half's records are never read.
-static void drop_pair(StreamCtx& c) {
-    if (!c.pair_pending) return;
-    c.pair_pending = false;
-    c.fused_tail = c.pair_tail; c.fused_B = c.pair_B; c.fused_pending = true;
+// What becomes of a bundle that an event does not continue (rq_bundle_plan.h BundleStep::brk; defined below, behind the pieces
+// of a call it is made of).  The ONE place where gathered calls are scanned late and unclaimed tails complete: flush_tails and
+// flush_all, which every other route and every mutation of the index goes through, and run_pipeline call it.
+static int break_bundle(rq_index* idx, StreamCtx& c, const BundleStep& st, hipStream_t s);
+
+static int ensure_ring(StreamCtx& cx) {
+    if (!cx.ring.qh) HIPCHK(alloc_queries(cx.ring, (size_t)RQ_RING_SLOTS * 64, nullptr));
+    return RQ_OK;
 }
 
 // The tail that is waiting for the stream's next scan launch ("pipeline" = 2) runs on its own instead, on `s`.
@@ -194,7 +204,7 @@ int flush_tails(rq_index* idx, hipStream_t s) {
     if (it == idx->ctx.end()) return RQ_OK;
     StreamCtx& c = it->second;
     c.hint_q = nullptr;   // a flush ends the loop the hint belonged to (queries already prepared stay usable)
-    drop_pair(c);
+    if (int r = break_bundle(idx, c, bundle_end(c.bs), s)) return r;
     if (int r = launch_waiting_tail(idx, c, s)) return r;
     for (int p = 0; p < 2; ++p)
         if (c.tail_pending[p]) {
@@ -204,12 +214,18 @@ int flush_tails(rq_index* idx, hipStream_t s) {
     return RQ_OK;
 }
 
-// Every tail still waiting for a scan ("pipeline" = 2), of every stream the index remembers.  The callers' stream handles are
+bool bundles_open(const rq_index* idx) {
+    for (auto& kv : idx->ctx)
+        if (kv.second.bs.phase == BUNDLE_GATHER) return true;
+    return false;
+}
+
+// Every bundle still open and every tail still waiting for a scan ("pipeline" = 2), of every stream the index remembers.  The callers' stream handles are
 // NOT used for it (a caller may have destroyed a stream it no longer searches on; only rq_stream_release tells us): the device
 // is drained first -- every scan those tails depend on has then finished -- and the tails run on the index's own stream.
 int flush_all(rq_index* idx) {
     bool any = false;
-    for (auto& kv : idx->ctx) any = any || kv.second.fused_pending || kv.second.pair_pending || kv.second.tail_pending[0] || kv.second.tail_pending[1];
+    for (auto& kv : idx->ctx) any = any || kv.second.fused_pending || kv.second.bs.phase != BUNDLE_IDLE || kv.second.tail_pending[0] || kv.second.tail_pending[1];
     if (!any) return RQ_OK;
     RQ_ON_DEVICE(idx);
     HIPCHK(hipDeviceSynchronize());
@@ -217,7 +233,8 @@ int flush_all(rq_index* idx) {
         StreamCtx& c = kv.second;
         c.hint_q = nullptr;
         c.tail_pending[0] = c.tail_pending[1] = false;   // (their events have fired: the device is idle)
-        drop_pair(c);
+        // (gathered calls are scanned here, on the index's own stream: their queries were prepared by launches that have drained)
+        if (int r = break_bundle(idx, c, bundle_end(c.bs), idx->own_stream)) return r;
         if (int r = launch_waiting_tail(idx, c, idx->own_stream)) return r;
     }
     HIPCHK(hipStreamSynchronize(idx->own_stream));
@@ -244,29 +261,6 @@ extern "C" int rq_stream_release(rq_index* idx, void* stream) {
     return release_contexts(idx, &s);
 }
 
-// Second call of a scanned-ahead pair (option "scan_ahead", see run_pipeline): the previous call's 128-query pass has written
-// this batch's records, so no scan is enqueued.  ONE launch runs the tails of both batches -- the previous call's outputs and
-// this call's, each with its own k -- and prepares the batch this call announces into the next ring slot.
-static int pair_second(rq_index* idx, StreamCtx& cx, int B, int k, const SearchOut& out, hipStream_t s) {
-    const int slot = (int)(cx.calls++ % 3);   // the slot the pass read this batch from
-    cx.pair_pending = false;
-    cx.prepped_q = nullptr;
-    idx->hints_used++;
-    idx->last_use8 = false; idx->last_wide1 = false;
-    RqTailArgs t1 = cx.pair_next;
-    set_records(cx, t1.bins, t1.bins_stride, B, 64);   // this call's records: the upper half of the previous call's pass
-    t1.k = k; t1.m = (int)std::min<int64_t>(k, idx->n);
-    t1.out_scores = out.scores; t1.out_rows = out.rows; t1.out_keys = out.keys; t1.out_status = out.status;
-    RqPrepArgs pa{};
-    if (cx.hint_q) pa = prep_args(cx.ring[(slot + 1) % 3], cx.hint_q, idx->dim, cx.hint_B, 64, true);
-    if (int r = poison_cand(idx, cx.pair_tail, cx.pair_B, s)) return r;
-    if (int r = poison_cand(idx, t1, B, s)) return r;
-    HIPCHK(rq_pair_tail_launch(cx.pair_tail, cx.pair_B, t1, B, pa, s));
-    if (pa.nslots) { cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = (slot + 1) % 3; }
-    cx.hint_q = nullptr;
-    return RQ_OK;
-}
-
 // How a call's tail runs: right behind its scan, on the stream's internal tail stream ("pipeline" = 1), or with the stream's
 // next scan launch ("pipeline" = 2, fused: one scan launch per call of <= 64 queries, which carries the tail of the previous call).
 enum CallMode { CALL_PLAIN, CALL_PIPED, CALL_FUSED };
@@ -278,6 +272,7 @@ struct Call {
     CallMode mode = CALL_PLAIN;
     bool pair = false;               // this call's pass also scans the batch its stream announced ("scan_ahead")
     int par = 0, slot = -1;          // workspace of the stream, ring slot of the queries (fused)
+    int next_slot = -1;              // ring slot of the batch the stream announced (fused; rq_bundle_plan.h)
     const float* scale = nullptr;    // row scales of the metric (a filtered call: the filter's masked copy)
     const rq_filter* filt = nullptr; // the call ranks these rows only (include/rq.h rq_search_filtered)
     int grid_narrow = 0, nwg_split = 0;
@@ -288,10 +283,8 @@ struct Call {
 static int enter_stream(rq_index* idx, StreamCtx& cx, Call& c) {
     hipStream_t s = c.s;
     if (c.mode == CALL_FUSED) {
-        c.slot = (int)(cx.calls % 3);
-        c.par = (int)(cx.calls++ & 1);
-        for (QuerySet& r : cx.ring)
-            if (!r.qh) HIPCHK(alloc_queries(r, 64, nullptr));
+        c.par = (int)(cx.calls++ & 1);   // (c.slot: the bundle plan's)
+        if (int r = ensure_ring(cx)) return r;
     } else if (c.mode == CALL_PIPED) {
         if (cx.fused_pending) { if (int r = flush_tails(idx, s)) return r; }
         if (!cx.tail) {
@@ -365,8 +358,8 @@ static int scan_passes(rq_index* idx, StreamCtx& cx, const Workspace& w, const Q
         const int grid = q0 >= c.nwg_split ? c.grid_narrow : p.grid_wide;
         RqScanArgs a = scan_args(idx, c, w, qs, q0, qb);
         if (c.pair) {   // queries 64..127 of the pass: the announced batch, from the next ring slot
-            a.qh_hi = cx.ring[(c.slot + 1) % 3].qh;
-            if (idx->scan_nostore != 1) a.nq_valid = 64 + cx.pair_qB;
+            a.qh_hi = ring_slot(cx, c.next_slot).qh;
+            if (idx->scan_nostore != 1) a.nq_valid = 64 + cx.await_B;
         }
         hipEvent_t t0 = nullptr, t1 = nullptr;   // "profile" = 1: every profile_stride-th scan is timed
         if (idx->profile == 1) {
@@ -400,7 +393,7 @@ static int scan_passes(rq_index* idx, StreamCtx& cx, const Workspace& w, const Q
         else if (qb == 128) HIPCHK(rq_scan_wide_launch(a, idx->wide128, 128, nt, grid, s, e0, e1));
         else HIPCHK(rq_scan_launch(a, idx->ring, idx->prefetch, idx->kstage, 4, nt, grid, epi, s, e0, e1));
         if (fused && pa.nslots) {
-            cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = (c.slot + 1) % 3;
+            cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = c.next_slot;
             cx.hint_q = nullptr;
         }
         if (legacy) HIPCHK(hipEventRecord(t1, s));
@@ -438,17 +431,155 @@ static RqTailArgs tail_args(const rq_index* idx, const Call& c, const Workspace&
     return ta;
 }
 
+// Member j of a bundle whose pass wrote workspace w: the tail `ta` of the pass moved to the member's quarter -- query slots
+// 64 j .. 64 j + 63 of the records, maxima, candidates and counters -- and to the ring's own copy of the member's queries.
+static RqTailArgs member_tail(const StreamCtx& cx, const Workspace& w, RqTailArgs ta, int j, int slot) {
+    const size_t q0 = (size_t)64 * j;
+    ta.q = ring_slot(cx, slot).q32; ta.dim = RQ_DPAD;
+    ta.bins = w.bins + q0 * w.bins_stride; ta.wgmax = w.wgmax + q0 * RQ_WGMAX_STRIDE;
+    ta.cand = w.cand + q0 * RQ_CAND_CAP; ta.rowcount = w.rowcount + q0; ta.done = w.done + q0; ta.ovf = w.ovf + q0;
+    return ta;
+}
+// What a member's own call says of its tail: k and the outputs.
+static void member_call(const rq_index* idx, RqTailArgs& t, int k, const SearchOut& out) {
+    t.k = k; t.m = (int)std::min<int64_t>(k, idx->n);
+    t.out_scores = out.scores; t.out_rows = out.rows; t.out_keys = out.keys; t.out_status = out.status;
+}
+
 // Fused: the tail runs with the NEXT scan launch of the stream (or at the flush).  It reads the ring's own copy of the
 // queries, so the caller's buffer is free as soon as this call's work has run.
 static void defer_tail(StreamCtx& cx, const Workspace& w, const QuerySet& qs, const Call& c, RqTailArgs ta) {
     ta.q = qs.q32; ta.dim = RQ_DPAD;
     if (!c.pair) { cx.fused_tail = ta; cx.fused_B = c.B; cx.fused_pending = true; return; }
-    // the announced batch: slots 64..127 of the pass and of the workspace, its own queries' copy
-    RqTailArgs t1 = ta;
-    t1.q = cx.ring[(c.slot + 1) % 3].q32;
-    t1.bins = w.bins + 64 * w.bins_stride; t1.wgmax = w.wgmax + 64 * RQ_WGMAX_STRIDE;
-    t1.cand = w.cand + (size_t)64 * RQ_CAND_CAP; t1.rowcount = w.rowcount + 64; t1.done = w.done + 64; t1.ovf = w.ovf + 64;
-    cx.pair_tail = ta; cx.pair_B = c.B; cx.pair_next = t1; cx.pair_pending = true;
+    // a pair: this call is member 0; the announced batch took slots 64..127 of the pass and of the workspace (member 1, whose k
+    // and outputs its own call brings: bundle_member, ROLE_CLAIM)
+    cx.b_tail[0] = ta; cx.b_B[0] = c.B;
+    cx.b_tail[1] = member_tail(cx, w, ta, 1, c.next_slot);
+    cx.b_par = c.par; cx.b_metric = c.metric;
+}
+
+// The tails of the first n members of the stream's bundle in ONE launch, with the preparation pa (nslots 0: none).
+static int launch_bundle_tails(const rq_index* idx, StreamCtx& cx, int n, const RqPrepArgs& pa, hipStream_t s) {
+    for (int j = 0; j < n; ++j)
+        if (int r = poison_cand(idx, cx.b_tail[j], cx.b_B[j], s)) return r;
+    HIPCHK(rq_bundle_tail_launch(cx.b_tail, cx.b_B, n, pa, s));
+    return RQ_OK;
+}
+
+// ONE pass over the first n members of the stream's bundle (ring slots base ..; nq_valid queries in all) into the quarters of
+// workspace cx.w[c.par], by the narrowest form: 64 queries (the plain pass), 128 (rq_scan_wide.hip variant 0, as a pair's) or 256
+// (variant 2: compiler-scheduled LDS reads only; three members leave the last quarter invalid).  c: the plan, metric and
+// row scales of a 64-query call on this shard.  Afterwards b_tail[0 .. n) are complete but for the k and outputs of members whose
+// own call is still to come.
+static int bundle_scan(rq_index* idx, StreamCtx& cx, Call& c, int n, int base, int nq_valid) {
+    const CallPlan& p = c.p;
+    hipStream_t s = c.s;
+    Workspace& w = cx.w[c.par];
+    const int slots = n == 1 ? 64 : (n == 2 ? 128 : 256);
+    // a tail still waiting for a scan (the call before the bundle was on its own) runs first: the wide passes carry none
+    if (int r = launch_waiting_tail(idx, cx, s)) return r;
+    set_records(cx, w.bins, w.bins_stride, nq_valid, slots);
+    if (int r = poison_bins(idx, w.bins, w.bins_stride, slots, s)) return r;
+    c.grid_narrow = scan_grid(idx, p.nquads, idx->wg_per_cu);
+    c.nwg_split = n == 1 ? 0 : 64;   // (every member's tail counts its queries from 0: all of them on the wide grid)
+    RqScanArgs a = scan_args(idx, c, w, ring_slot(cx, base), 0, slots);
+    a.nq_valid = idx->scan_nostore == 1 ? 0 : nq_valid;
+    if (n == 2) a.qh_hi = ring_slot(cx, bundle_slot_after(base)).qh;   // (three and four members: an aligned quarter of the ring, one block)
+    hipEvent_t t0 = nullptr, t1 = nullptr;   // "profile" = 1, as scan_passes
+    if (idx->profile == 1) {
+        if (int r = next_event_pair(idx, t0, t1)) return r;
+        if (t0 && (idx->scan_seq++ % (uint64_t)idx->profile_stride) != 0) t0 = t1 = nullptr;
+    }
+    const bool legacy = t0 && idx->profile_legacy;
+    const hipEvent_t e0 = legacy ? nullptr : t0, e1 = legacy ? nullptr : t1;
+    if (legacy) HIPCHK(hipEventRecord(t0, s));
+    if (n == 1) HIPCHK(rq_scan_launch(a, 3, 1, 2, 4, p.nt, c.grid_narrow, idx->epi, s, e0, e1));
+    else if (n == 2) HIPCHK(rq_scan_wide_launch(a, 0, 128, p.nt, p.grid_wide, s, e0, e1));
+    else { HIPCHK(rq_scan_wide_launch(a, 2, 256, p.nt, p.grid_wide, s, e0, e1)); idx->bundles4++; }
+    if (legacy) HIPCHK(hipEventRecord(t1, s));
+    if (t0) { idx->ev_used++; idx->ev_bytes += idx->n * p.scan_rowb; }
+    const RqTailArgs ta = tail_args(idx, c, w, ring_slot(cx, base));
+    for (int j = 0; j < n; ++j) {
+        RqTailArgs t = member_tail(cx, w, ta, j, (base + j) % RQ_RING_SLOTS);
+        const RqTailArgs& own = cx.b_tail[j];
+        t.k = own.k; t.m = own.m; t.out_scores = own.out_scores; t.out_rows = own.out_rows; t.out_keys = own.out_keys; t.out_status = own.out_status;
+        cx.b_tail[j] = t;
+    }
+    return RQ_OK;
+}
+
+static int break_bundle(rq_index* idx, StreamCtx& cx, const BundleStep& st, hipStream_t s) {
+    if (st.brk == BREAK_NONE) return RQ_OK;
+    cx.await_q = nullptr;
+    if (st.brk == BREAK_SCAN) {   // gathered, not scanned: the plan of a 64-query call on the shard as it is (every mutation completes bundles first)
+        Call c{nullptr, 64, cx.b_tail[0].k, cx.b_metric, SearchOut{}, s};
+        if (int r = plan_call(idx, 64, c.k, c.metric, nb_default(idx, c.k), false, CALL_MAY_DEFER, &c.p)) return r;
+        c.mode = CALL_FUSED; c.par = cx.b_par;
+        c.scale = c.metric == RQ_METRIC_IP ? idx->ones : idx->inv_norm;
+        if (int r = bundle_scan(idx, cx, c, st.brk_n, st.brk_base, 64 * st.brk_n)) return r;
+    }
+    // one tail: it rides with the next fused launch of the stream or runs at the flush, as a lone call's; several run now
+    if (st.brk_n == 1) { cx.fused_tail = cx.b_tail[0]; cx.fused_B = cx.b_B[0]; cx.fused_pending = true; return RQ_OK; }
+    return launch_bundle_tails(idx, cx, st.brk_n, RqPrepArgs{}, s);
+}
+
+// A call that the plan made a member of a bundle of four (ROLE_OPEN .. ROLE_JOIN_PASS), the last member of one cut short
+// (ROLE_CLOSE) or the claim of a batch that was scanned ahead (ROLE_CLAIM: a pair's second call, a bundle's fourth).
+static int bundle_member(rq_index* idx, StreamCtx& cx, Call& c, const BundleStep& st) {
+    hipStream_t s = c.s;
+    const CallPlan& p = c.p;
+    const int j = (st.slot - st.base + RQ_RING_SLOTS) % RQ_RING_SLOTS;   // member number
+    if (st.role == ROLE_OPEN) { cx.b_par = (int)(cx.calls & 1); cx.b_metric = c.metric; }
+    cx.calls++;
+    c.mode = CALL_FUSED; c.par = cx.b_par; c.slot = st.slot; c.next_slot = st.next_slot;
+    idx->last_use8 = false; idx->last_wide1 = false;
+    if (st.role != ROLE_OPEN || !st.prep_self) idx->hints_used++;
+    if (int r = ensure_ring(cx)) return r;
+    Workspace& w = cx.w[c.par];
+    if (st.role == ROLE_OPEN) {
+        // the workspace holds the four quarters before any member's tail is planned; a tail that still waits reads the old one
+        if (int r = launch_waiting_tail(idx, cx, s)) return r;
+        if (int r = ensure_ws(w, 64 * RQ_BUNDLE_MAX, p.stride, p.m, (size_t)64 * RQ_BUNDLE_MAX * (size_t)p.ncand)) return r;
+        if (!w.counters_zero) {
+            HIPCHK(hipMemsetAsync(w.rowcount, 0, (size_t)w.bcap * sizeof(int), s));
+            HIPCHK(hipMemsetAsync(w.done, 0, (size_t)w.bcap * sizeof(int), s));
+            HIPCHK(hipMemsetAsync(w.ovf, 0, (size_t)w.bcap * sizeof(int), s));
+            w.counters_zero = true;
+        }
+    }
+    c.scale = idx->inv_norm;
+    if (c.metric == RQ_METRIC_IP) { if (int r = ensure_ones(idx, s)) return r; c.scale = idx->ones; }
+    member_call(idx, cx.b_tail[j], c.k, c.out);
+    cx.b_B[j] = c.B;
+    // preparations: the member's own queries unless an earlier launch made them, and the batch it announces -- with the tail
+    // launch where this call makes one, else now, both in ONE launch
+    const bool tails_now = st.role == ROLE_CLOSE || st.role == ROLE_CLAIM;
+    RqPrepArgs self{}, next{};
+    if (st.prep_self) self = prep_args(ring_slot(cx, st.slot), c.d_q, idx->dim, c.B, 64, true);
+    if (st.next_slot >= 0) next = prep_args(ring_slot(cx, st.next_slot), cx.hint_q, idx->dim, cx.hint_B, 64, true);
+    if (self.nslots && next.nslots && !tails_now) HIPCHK(rq_prep2_queries_launch(self, next, s));
+    else {
+        if (self.nslots) HIPCHK(rq_prep_queries_launch(self, s));
+        if (next.nslots && !tails_now) HIPCHK(rq_prep_queries_launch(next, s));
+    }
+    cx.prepped_q = nullptr;
+    if (next.nslots) { cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = st.next_slot; }
+    cx.await_q = nullptr;
+    if (!tails_now) { cx.await_q = cx.hint_q; cx.await_B = cx.hint_B; cx.await_metric = c.metric; }   // (these roles need an announcement)
+    cx.hint_q = nullptr;
+    switch (st.role) {
+    case ROLE_OPEN: case ROLE_JOIN:
+        set_records(cx, nullptr, 0, 0, 0);   // gathered: nothing of this call has been scanned yet
+        return RQ_OK;
+    case ROLE_JOIN_PASS:
+        return bundle_scan(idx, cx, c, st.n, st.base, 64 * (st.n - 1) + cx.await_B);
+    case ROLE_CLOSE:
+        if (int r = bundle_scan(idx, cx, c, st.n, st.base, 64 * (st.n - 1) + c.B)) return r;
+        return launch_bundle_tails(idx, cx, st.n, next, s);
+    default:   // ROLE_CLAIM: this call's records are its quarter of the pass made ahead
+        set_records(cx, cx.b_tail[j].bins, cx.b_tail[j].bins_stride, c.B, 64);
+        return launch_bundle_tails(idx, cx, st.n, next, s);
+    }
 }
 
 // Plain and piped: the tail runs now, behind the scan (piped: on the stream's tail stream).
@@ -535,20 +666,31 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
     if (p.fast && may_defer && idx->pipeline == 1) c.mode = CALL_PIPED;
     if (p.fast && may_defer && idx->pipeline == 2 && p.bpad == 64) c.mode = CALL_FUSED;
     const bool fused = c.mode == CALL_FUSED;
-    if (cx.pair_pending) {   // the previous call scanned this stream's announced batch ahead (below)
-        if (fused && !use8 && d_q == cx.pair_q && B == cx.pair_qB && metric == cx.pair_metric)
-            return pair_second(idx, cx, B, k, out, s);
-        drop_pair(cx);
-    }
-    // Option "scan_ahead": a fused call over the fp16 rows whose stream has announced its next batch (rq_search_hint_next_device)
-    // scans BOTH in one 128-query pass (rq_scan_wide.hip variant 0: 266-268 us at 1M rows against 237 us for 64 queries); the
-    // next call, if it brings the announced batch, only runs the two tails (pair_second).  Only on shards the Infinity Cache
-    // cannot hold (the rule of the non-temporal loads): smaller shards are not bound by HBM bytes.
-    c.pair = fused && !use8 && !p.narrow && idx->scan_ahead && cx.hint_q && cx.hint_B <= 64 && beyond_cache(idx->n, (int64_t)idx->rowb());
+    // Options "scan_ahead" / "scan_bundle": a fused call over the fp16 rows whose stream has announced its next batch
+    // (rq_search_hint_next_device) is scanned together with it in one 128-query pass (rq_scan_wide.hip variant 0: 266-268 us at 1M
+    // rows against 237 us for 64 queries) and, once the loop has proven steady, four consecutive calls in one 256-query pass; the
+    // call that brings a batch scanned ahead only runs the tails.  Only on shards the Infinity Cache cannot hold (the rule of the
+    // non-temporal loads): smaller shards are not bound by HBM bytes.  What this call is to the calls before it: rq_bundle_plan.h.
+    BundleCall bc;
+    bc.fused = fused;
+    bc.eligible = fused && !use8 && !p.narrow && !filt && !scan_only && idx->scan_ahead && beyond_cache(idx->n, (int64_t)idx->rowb());
+    bc.matches = cx.await_q && d_q == cx.await_q && B == cx.await_B && metric == cx.await_metric;
+    bc.announces = fused && cx.hint_q && cx.hint_B <= 64;
+    bc.full = B == 64;
+    bc.next_full = cx.hint_B == 64;
+    bc.prepped_slot = fused && cx.prepped_q == d_q && cx.prepped_B == B ? cx.prepped_slot : -1;
+    bc.other = (cx.await_q || cx.prepped_q) && !bc.matches && bc.prepped_slot < 0;
+    const BundleStep step = bundle_call(cx.bs, bc, idx->scan_bundle);
+    if (int r = break_bundle(idx, cx, step, s)) return r;
+    if (step.role >= ROLE_OPEN) return bundle_member(idx, cx, c, step);
+    c.pair = step.role == ROLE_PAIR_FIRST;
+    c.slot = step.slot; c.next_slot = step.next_slot;
     if (int r = enter_stream(idx, cx, c)) return r;
     Workspace& w = cx.w[c.par];
     // (a pair: the announced batch's records, candidates and counters take query slots 64..127 of the same workspace)
-    if (int r = ensure_ws(w, c.pair ? 128 : p.bpad, p.exact ? 64 : p.stride, p.exact ? 1 : p.m, std::max((size_t)(c.pair ? 128 : B) * (size_t)p.ncand, scan_only ? scan_only->cand_elems : (size_t)0))) return r;
+    // (... sized at once for the widest bundle the stream may come to, so that a steady loop never regrows it)
+    const int ws_slots = c.pair ? 64 * std::max(2, idx->scan_bundle) : p.bpad;
+    if (int r = ensure_ws(w, ws_slots, p.exact ? 64 : p.stride, p.exact ? 1 : p.m, std::max((size_t)(c.pair ? ws_slots : B) * (size_t)p.ncand, scan_only ? scan_only->cand_elems : (size_t)0))) return r;
     c.scale = idx->inv_norm;
     if (metric == RQ_METRIC_IP) { if (int r = ensure_ones(idx, s)) return r; c.scale = idx->ones; }
     if (filt) {   // excluded rows get a NaN scale, like pad rows: no scan form tests a row's validity
@@ -567,20 +709,20 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
     if (may_defer) { idx->last_use8 = use8; idx->last_wide1 = use8 && B > 64 && idx->scan8_level[p.kclass] == 1; }   // (may_defer: the caller's own search, not a repair pass of rq_search_fixup_device)
     // unit-norm fp16 query fragments for the scan (+ padded fp32 queries / fp64 norms for the generic tail)
     // ... unless the previous launch of this stream has already prepared exactly these queries (rq_search_hint_next_device)
-    const QuerySet& qs = fused ? cx.ring[c.slot] : w.qs;
-    const bool prepared = fused && cx.prepped_q == d_q && cx.prepped_B == B && cx.prepped_slot == c.slot;
+    const QuerySet qs = fused ? ring_slot(cx, c.slot) : w.qs;
+    const bool prepared = fused && !step.prep_self;
     cx.prepped_q = nullptr;
     if (prepared) idx->hints_used++;
     else HIPCHK(rq_prep_queries_launch(prep_args(qs, d_q, idx->dim, B, p.bpad, true), s));
     // the queries announced for the NEXT call are prepared by extra workgroups of this call's fused launch
     RqPrepArgs pa{};
-    if (fused && cx.hint_q) pa = prep_args(cx.ring[(c.slot + 1) % 3], cx.hint_q, idx->dim, cx.hint_B, 64, true);
+    if (fused && cx.hint_q) pa = prep_args(ring_slot(cx, c.next_slot), cx.hint_q, idx->dim, cx.hint_B, 64, true);
     if (c.pair) {
         // the pass reads the announced batch from the next ring slot: it is prepared first, by a launch of its own; and a tail
         // still waiting for a scan (the call before this one was not paired) runs on its own, as the wide pass carries none
         HIPCHK(rq_prep_queries_launch(pa, s));
-        cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = (c.slot + 1) % 3;
-        cx.pair_q = cx.hint_q; cx.pair_qB = cx.hint_B; cx.pair_metric = metric;
+        cx.prepped_q = cx.hint_q; cx.prepped_B = cx.hint_B; cx.prepped_slot = c.next_slot;
+        cx.await_q = cx.hint_q; cx.await_B = cx.hint_B; cx.await_metric = metric;
         cx.hint_q = nullptr;
         pa.nslots = 0;
         if (int r = launch_waiting_tail(idx, cx, s)) return r;
@@ -592,8 +734,8 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
         set_records(cx, nullptr, 0, 0, 0);
         return generic_tail(idx, c, w);
     }
-    const int slots = c.pair ? 128 : p.bpad;   // (a pair: both halves; the upper one is the next call's, pair_second)
-    set_records(cx, w.bins, w.bins_stride, c.pair ? 64 + cx.pair_qB : B, slots);
+    const int slots = c.pair ? 128 : p.bpad;   // (a pair: both halves; the upper one is the next call's, bundle_member)
+    set_records(cx, w.bins, w.bins_stride, c.pair ? 64 + cx.await_B : B, slots);
     if (int r = poison_bins(idx, w.bins, w.bins_stride, slots, s)) return r;
     if (int r = scan_passes(idx, cx, w, qs, c, pa)) return r;
     if (scan_only) { scan_only->w = &w; return RQ_OK; }   // a range search: its own tail reads the records (rq_range.hip)

@@ -65,36 +65,61 @@ hipError_t rq_tail_filtered_launch(const RqTailArgs& a, const RqFilterArgs& f, i
     return small ? rq_tail_filtered_launch_nv<1, RQ_DPAD>(a, f, B, stream) : rq_tail_filtered_launch_nv<4, RQ_DPAD>(a, f, B, stream);
 }
 
-// Tails of a scanned-ahead pair (both batches' records come from one 128-query pass) + the preparation of the next batch.
-// Block ids: [0, chunks * B0) tail t0 | [.., + chunks * B1) tail t1 | pa.nslots workgroups of rq_prep_body.
+// Tails of a bundle (the records of all its batches come from one 128- or 256-query pass) + the preparation of the next batch.
+// Block ids: [0, end[0]) tail t0 | [end[0], end[1]) tail t1 | [end[1], end[2]) t2 | [end[2], end[3]) t3 | pa.nslots workgroups of
+// rq_prep_body; end[j] = chunks * (B[0] + .. + B[j]), a tail that is not there has end[j] = end[j - 1].  (The name is the pair's,
+// which profiles and DESIGN.md know the launch by; a pair is a bundle of two.)
 union RqPairLds {
     RqTailLds tail;
     double prep[16];
 };
+struct RqBundleEnds { int e0, e1, e2, e3; };
 template <int NV>
-__global__ __launch_bounds__(256) void rq_pair_tail_kernel(RqTailArgs t0, int B0, RqTailArgs t1, int B1, RqPrepArgs pa, int chunks) {
+__global__ __launch_bounds__(256) void rq_pair_tail_kernel(RqTailArgs t0, RqTailArgs t1, RqTailArgs t2, RqTailArgs t3, RqBundleEnds end, RqPrepArgs pa, int chunks) {
     __shared__ RqPairLds lds;
     const int bid = (int)blockIdx.x;
-    const int n0 = chunks * B0, n1 = chunks * B1;
-    if (bid < n0) rq_tail_body<NV>(t0, bid % chunks, bid / chunks, chunks, lds.tail);
-    else if (bid < n0 + n1) rq_tail_body<NV>(t1, (bid - n0) % chunks, (bid - n0) / chunks, chunks, lds.tail);
-    else rq_prep_body(pa, bid - n0 - n1, lds.prep);
+    if (bid < end.e0) rq_tail_body<NV>(t0, bid % chunks, bid / chunks, chunks, lds.tail);
+    else if (bid < end.e1) rq_tail_body<NV>(t1, (bid - end.e0) % chunks, (bid - end.e0) / chunks, chunks, lds.tail);
+    else if (bid < end.e2) rq_tail_body<NV>(t2, (bid - end.e1) % chunks, (bid - end.e1) / chunks, chunks, lds.tail);
+    else if (bid < end.e3) rq_tail_body<NV>(t3, (bid - end.e2) % chunks, (bid - end.e2) / chunks, chunks, lds.tail);
+    else rq_prep_body(pa, bid - end.e3, lds.prep);
 }
 
 template <int NV>
-static hipError_t rq_pair_tail_launch_nv(const RqTailArgs& t0, int B0, const RqTailArgs& t1, int B1, const RqPrepArgs& pa, hipStream_t stream) {
-    const int64_t chunks = (t0.nbins + 512 * NV - 1) / (512 * NV);
-    const int64_t grid = chunks * (B0 + B1) + pa.nslots;
+static hipError_t rq_bundle_tail_launch_nv(const RqTailArgs* t, const int* B, int n, const RqPrepArgs& pa, hipStream_t stream) {
+    const int64_t chunks = (t[0].nbins + 512 * NV - 1) / (512 * NV);
+    int64_t e[RQ_BUNDLE_TAILS], sum = 0;
+    for (int j = 0; j < RQ_BUNDLE_TAILS; ++j) e[j] = (sum += j < n ? chunks * B[j] : 0);
+    const int64_t grid = sum + pa.nslots;
     if (chunks < 1 || grid > INT32_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((rq_pair_tail_kernel<NV>), dim3((unsigned)grid), dim3(256), 0, stream, t0, B0, t1, B1, pa, (int)chunks);
+    const RqTailArgs& last = t[n - 1];   // (an absent tail's workgroup range is empty: its arguments are never read)
+    hipLaunchKernelGGL((rq_pair_tail_kernel<NV>), dim3((unsigned)grid), dim3(256), 0, stream, t[0], n > 1 ? t[1] : last, n > 2 ? t[2] : last, n > 3 ? t[3] : last,
+                       RqBundleEnds{(int)e[0], (int)e[1], (int)e[2], (int)e[3]}, pa, (int)chunks);
     return hipGetLastError();
 }
 
-hipError_t rq_pair_tail_launch(const RqTailArgs& t0, int B0, const RqTailArgs& t1, int B1, const RqPrepArgs& pa, hipStream_t stream) {
-    for (const RqTailArgs* t : {&t0, &t1})
-        if (t->m < 1 || t->m > RQ_FAST_MAX_M || t->k < 1 || t->k > RQ_FAST_MAX_K) return hipErrorInvalidValue;
-    if (t0.dpad != RQ_DPAD || t1.dpad != RQ_DPAD) return hipErrorInvalidValue;   // (pairs are scanned over rows of 768 elements only)
-    if (B0 < 1 || B1 < 1 || t0.nbins != t1.nbins || pa.nslots < 0 || pa.nslots > 64) return hipErrorInvalidValue;
-    return rq_tail_small_chunks(t0.nbins, B0 + B1) ? rq_pair_tail_launch_nv<1>(t0, B0, t1, B1, pa, stream)
-                                                   : rq_pair_tail_launch_nv<4>(t0, B0, t1, B1, pa, stream);
+hipError_t rq_bundle_tail_launch(const RqTailArgs* t, const int* B, int n, const RqPrepArgs& pa, hipStream_t stream) {
+    if (!t || !B || n < 1 || n > RQ_BUNDLE_TAILS || pa.nslots < 0 || pa.nslots > 64) return hipErrorInvalidValue;
+    int sumB = 0;
+    for (int j = 0; j < n; ++j) {
+        if (t[j].m < 1 || t[j].m > RQ_FAST_MAX_M || t[j].k < 1 || t[j].k > RQ_FAST_MAX_K) return hipErrorInvalidValue;
+        if (t[j].dpad != RQ_DPAD || t[j].nbins != t[0].nbins) return hipErrorInvalidValue;   // (bundles are scanned over rows of 768 elements only)
+        if (B[j] < 1 || B[j] > 64) return hipErrorInvalidValue;
+        for (int i = 0; i < j; ++i)
+            if (t[i].cand == t[j].cand || t[i].rowcount == t[j].rowcount || t[i].done == t[j].done || t[i].ovf == t[j].ovf) return hipErrorInvalidValue;
+        sumB += B[j];
+    }
+    return rq_tail_small_chunks(t[0].nbins, sumB) ? rq_bundle_tail_launch_nv<1>(t, B, n, pa, stream) : rq_bundle_tail_launch_nv<4>(t, B, n, pa, stream);
+}
+
+__global__ __launch_bounds__(256) void rq_prep2_queries_kernel(RqPrepArgs a, RqPrepArgs b) {
+    __shared__ double part[16];
+    const int bid = (int)blockIdx.x;
+    if (bid < a.nslots) rq_prep_body(a, bid, part);
+    else rq_prep_body(b, bid - a.nslots, part);
+}
+hipError_t rq_prep2_queries_launch(const RqPrepArgs& a, const RqPrepArgs& b, hipStream_t stream) {
+    if (a.nslots <= 0 || b.nslots <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rq_prep2_queries_kernel, dim3(a.nslots + b.nslots), dim3(256), 0, stream, a, b);
+    return hipGetLastError();
 }

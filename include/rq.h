@@ -114,7 +114,14 @@ int rq_search_device(rq_index* idx, const float* d_queries, int B, int k, int me
  *      events, scans never overlap each other; calls of <= 64 queries, k <= 128).
  * In both modes the outputs of rq_search_device calls are complete on `stream` only after this call
  * (rq_search_fixup_device implies it); output buffers must stay valid until then.  Mode 1 also reads d_queries
- * until then, mode 2 keeps its own copy. */
+ * until then, mode 2 keeps its own copy.
+ * Mode 2 with announced batches (rq_search_hint_next_device, options "scan_ahead" / "scan_bundle") defers more than the tail:
+ * a call may be held back WHOLE -- scan and tail -- until up to three calls after it have been made, so that one corpus pass
+ * serves them all.  Nothing is enqueued for such a call beyond the copy of its queries; its outputs are written only by work
+ * of a later call of the stream or of this flush.  The contract above holds as written: complete after this call, output
+ * buffers valid until then.  Every other route on the stream and every change of the index (appends, a reserve that
+ * reallocates, options, rq_save, rq_stream_release, rq_index_destroy) completes what is held back first: a held-back call
+ * returns the rows the index held when it was made. */
 int rq_search_flush_device(rq_index* idx, void* stream);
 /* "pipeline" = 2 loops that know their next batch: announce the queries of the NEXT rq_search_device call on `stream`
  * before making the current one.  The current call's launch then prepares them (norms, unit-norm fp16 fragments) with 64
@@ -126,7 +133,15 @@ int rq_search_flush_device(rq_index* idx, void* stream);
  * Option "scan_ahead" (default 1): on shards the Infinity Cache cannot hold (rows x 1536 B > 208 MiB), a call over the fp16
  * rows that has an announced successor scans BOTH batches in one 128-query pass; the next call, when it brings exactly
  * d_next_queries, B and the same metric (any k), enqueues no scan of its own and runs the two batches' tails.  Anything else
- * (another call, a flush, rq_stream_release) completes the first batch as usual and discards the half scanned ahead. */
+ * (another call, a flush, rq_stream_release) completes the first batch as usual and discards the half scanned ahead.
+ * Option "scan_bundle" (default 4; 2 = pairs only): once a stream has completed three such pairs back to back -- since its
+ * workspace was created, or since its last flush, unmatched call, release or call of another kind --, up to FOUR consecutive
+ * announced 64-query calls are scanned by ONE 256-query pass: the first two only copy their queries, the third launches the
+ * pass (over itself, the two before it and the batch it announces), the fourth runs all four tails in one launch, each with
+ * its own k and outputs.  Only the last call of such a bundle may have fewer than 64 queries.  A call that does not bring
+ * the announced batch, or announces nothing, ends the bundle: the calls held back are scanned then by the narrowest pass
+ * (64, 128 or 256 queries) and nothing is lost; a batch scanned ahead that never comes is discarded.  Results are later by
+ * up to three calls, never different.  Read-only option "bundles4" counts the 256-query passes made this way. */
 int rq_search_hint_next_device(rq_index* idx, const float* d_next_queries, int B, void* stream);
 /* A TRAIN of searches enqueued by one call (serving loops, the multi-GPU bench: a 125 k-row shard answers a 64-query batch in
  * ~25 us, which a host loop that crosses the language boundary twice per batch cannot feed): batch i = B queries at
@@ -139,9 +154,12 @@ int rq_search_hint_next_device(rq_index* idx, const float* d_next_queries, int B
 int rq_search_train_device(rq_index* idx, int n_batches, const float* const* d_queries, int B, int k, int metric,
                            float* const* d_scores, int64_t* const* d_rows, uint64_t* const* d_keys, int* const* d_status,
                            void* const* streams, int n_streams);
-/* The library keeps one search workspace per caller stream (about 11 MB at 1M rows and 64 queries).  Call this before a
- * stream that has been used for searches is destroyed, or when it will not be used again: waits for the device, runs
- * any deferred tail, frees the stream's workspace.  (Beyond 8 streams the library drops idle workspaces by itself.) */
+/* The library keeps one search workspace per caller stream: about 11 MB at 1M rows per 64 query slots, two of them for
+ * alternating calls.  A stream that scans announced batches ahead holds one workspace of 256 slots ("scan_bundle" = 4: about
+ * 44 MB at 1M rows; 128 slots, 22 MB, with "scan_bundle" = 2), sized once by its first such call, beside one of 64 slots and
+ * 3 MB of prepared queries (8 slots of 64).  Call this before a
+ * stream that has been used for searches is destroyed, or when it will not be used again: waits for the device, scans
+ * the calls an open bundle still holds back, runs any deferred tail, frees the stream's workspace.  (Beyond 8 streams the library drops idle workspaces by itself.) */
 int rq_stream_release(rq_index* idx, void* stream);
 /* Synchronises `stream`, re-runs the queries whose d_status is non-zero with wider candidate sets /
  * the exact scan, patches d_scores/d_rows/d_keys/d_status in place.  Returns the number repaired. */
@@ -747,7 +765,8 @@ int rq_router_rerank(rq_router* r, const int32_t* keys, const double* b, const d
  * 256 / 128 / 64, 3 = 128 / 64, 2 = round 1's 8-wave 128-query pass), "wide128" / "wide256" (variant of csrc/rq_scan_wide.hip),
  * "epi" (selection form of the 64-query scan: 1 = row positions inside the scores, 0 = compare / select),
  * "use_hint" (0: rq_search_hint_next_device is ignored), "scan_ahead" (1 = default: an announced batch is scanned together with
- *   the call before it on shards beyond 208 MiB of fp16 rows, see rq_search_hint_next_device; 0 = never),
+ *   the call before it on shards beyond 208 MiB of fp16 rows, see rq_search_hint_next_device; 0 = never), "scan_bundle" (4 =
+ *   default: in a steady announced loop four calls share one 256-query pass; 2 = pairs only; read-only "bundles4" counts those passes),
  * "scan8" (searches may scan an int8 image of the shard instead of its fp16 rows -- half the bytes per pass;
  *   candidates are still re-scored from the fp16 rows in fp64, so results do not change: 0 = never, 1 = for k <= 128 on shards of
  *   200 000 rows and more (default), 2 = always.  The image (+768 B per row) is built by the first search that wants it (no room for it: the fp16 rows stay the operand); a shard whose
