@@ -133,6 +133,24 @@ def _given(**keywords) -> Dict[str, Any]:
     return {name: value for name, value in keywords.items() if value is not None}
 
 
+def _with_made_filters(entries, passes, make, call):
+    """`call(filters)`, one filter per entry: an entry that `passes` stays as it is; any other becomes `make(entry)` -- made once per distinct
+    OBJECT, in the order of the entries -- and is closed once the call has returned or raised (the `_with_filters` of both classes)."""
+    made = {}
+    try:
+        filters = []
+        for e in entries:
+            if not passes(e):
+                if id(e) not in made:
+                    made[id(e)] = make(e)
+                e = made[id(e)]
+            filters.append(e)
+        return call(filters)
+    finally:
+        for flt in made.values():
+            flt.close()
+
+
 def _group_value(doc: "Document", key: str):
     """... of a Document: the metadata DenseIndex.add_documents stores for it, {"title": title, **metadata}."""
     return _meta_group_value({"title": doc.title or "", **(doc.metadata or {})}, key)
@@ -1084,23 +1102,10 @@ class DenseIndex:
         return index.make_filter(np.asarray(rows, dtype=np.int64))
 
     def _with_filters(self, entries, call):
-        """`call(filters)` with every entry as the native calls take it: None (unrestricted) and a caller's own filter pass through
-        untouched; ids become a filter made now -- one per distinct OBJECT -- and closed once the call has returned or raised.  Ids
-        cost a filter's whole set-up and tear-down per call (O(rows) on the host, two device allocations, the masked scale, a device
-        synchronisation): reuse a `make_filter` result for repeated questions."""
-        made = {}
-        try:
-            filters = []
-            for e in entries:
-                if e is not None and not isinstance(e, _native.RowFilter):
-                    if id(e) not in made:
-                        made[id(e)] = self.make_filter(e)
-                    e = made[id(e)]
-                filters.append(e)
-            return call(filters)
-        finally:
-            for flt in made.values():
-                flt.close()
+        """`call(filters)` with every entry as the native calls take it: None (unrestricted) and a caller's own filter pass through untouched;
+        ids become a filter made now and closed behind the call (`_with_made_filters`) -- a filter's whole set-up and tear-down per call (O(rows)
+        on the host, two device allocations, the masked scale, a device synchronisation): reuse a `make_filter` result for repeated questions."""
+        return _with_made_filters(entries, lambda e: e is None or isinstance(e, _native.RowFilter), self.make_filter, call)
 
     def _with_filter(self, allowed_ids, call):
         """`call(row_filter)` for one `allowed_ids`; free when there is no filter to make."""
@@ -1494,6 +1499,17 @@ class HybridFilter:
         return len(self.ids)
 
 
+@dataclass(frozen=True)
+class _BatchRequest:
+    """One hybrid batch call after its keywords were checked (`HybridRetriever._batch_call`): what the private functions pass on."""
+    queries: Sequence[str]
+    n: int                                  # top_k of hybrid_search_batch, num_passages of the router calls
+    pool: int                               # retrieval_pool_size
+    complete_scores: bool = False
+    each: Optional[list] = None             # one checked HybridFilter or None per query (`_with_filters`); None: no filter keyword was given
+    distinct_by: Optional[str] = None
+
+
 class HybridRetriever:
     """Unified hybrid retrieval combining BM25 and dense retrieval (reference :376-560).
 
@@ -1514,15 +1530,12 @@ class HybridRetriever:
                  chroma_host: Optional[str] = None, embedding_model: str = "nomic-embed-text",
                  *, dense_index=None, embedder=None, device: int = 0, sparse_backend: str = "host", fusion_backend: str = "host",
                  router_backend: str = "host"):
-        if sparse_backend not in ("host", "gpu", "auto"):
-            raise ValueError(f"sparse_backend must be 'host', 'gpu' or 'auto', not {sparse_backend!r}")
-        if fusion_backend not in ("host", "gpu", "auto"):
-            raise ValueError(f"fusion_backend must be 'host', 'gpu' or 'auto', not {fusion_backend!r}")
-        if router_backend not in ("host", "gpu", "auto"):
-            raise ValueError(f"router_backend must be 'host', 'gpu' or 'auto', not {router_backend!r}")
+        for name, backend in (("sparse_backend", sparse_backend), ("fusion_backend", fusion_backend), ("router_backend", router_backend)):
+            if backend not in ("host", "gpu", "auto"):
+                raise ValueError(f"{name} must be 'host', 'gpu' or 'auto', not {backend!r}")
         self.router_backend = router_backend   # where `route_batch` gates and reranks the fused pool
         self.sparse_backend = sparse_backend   # where the BATCH calls score BM25 (BM25Index.search_batch_rows `backend`); per-query calls stay on the host
-        self.fusion_backend = fusion_backend   # where the BATCH calls fuse the two pools (`_fuse_batch_rows`)
+        self.fusion_backend = fusion_backend   # where the BATCH calls fuse the two pools (`_fused_rows`)
         self.bm25_index = BM25Index(persist_path=bm25_persist_path)
         if dense_index is not None:
             self.dense_index = dense_index
@@ -1602,25 +1615,23 @@ class HybridRetriever:
         if self.dense_index is None:
             return [[] for _ in queries]
         if distinct_by is not None:
-            e = None if entries is None else entries[0]
-            if isinstance(e, HybridFilter):
-                e = list(e.ids) if self._checked(e).dense is None else e.dense
-            if hasattr(self.dense_index, "search_batch"):
-                res = self.dense_index.search_batch(list(queries), top_k, distinct_by=distinct_by, **_given(allowed_ids=e))
-            else:
-                res = [self.dense_index.search(q, top_k, distinct_by=distinct_by, **_given(allowed_ids=e)) for q in queries]
-        elif entries is not None:
-            # the dense half of a hybrid filter, or the entry as it came (DenseIndex makes one filter per distinct object of ids)
-            each = [e if not isinstance(e, HybridFilter) else (list(e.ids) if self._checked(e).dense is None else e.dense) for e in entries]
-            if hasattr(self.dense_index, "search_batch"):
-                res = self.dense_index.search_batch(list(queries), top_k, allowed_ids_each=each)
-            else:
-                res = [self.dense_index.search(q, top_k, **_given(allowed_ids=e)) for q, e in zip(queries, each)]
-        elif hasattr(self.dense_index, "search_batch"):
-            res = self.dense_index.search_batch(list(queries), top_k)
+            res = self._dense_batch(queries, top_k, distinct_by=distinct_by, **_given(allowed_ids=None if entries is None else self._dense_half(entries[0])))
         else:
-            res = [self.dense_index.search(q, top_k) for q in queries]
+            res = self._dense_batch(queries, top_k, None if entries is None else [self._dense_half(e) for e in entries])
         return [[(d, s) for d, s, _ in r] for r in res]
+
+    def _dense_half(self, entry):
+        """What the dense side takes for one filter entry: of a `make_filter` result -- refused when stale -- its RowFilter, or its ids
+        where the dense index gave it none; anything else as it came (DenseIndex makes one filter per distinct object of ids)."""
+        if not isinstance(entry, HybridFilter):
+            return entry
+        return list(entry.ids) if self._checked(entry).dense is None else entry.dense
+
+    def _dense_batch(self, queries: Sequence[str], top_k: int, each: Optional[list] = None, **shared):
+        """The dense index's `search_batch`, or its `search` query by query where it has none; `each`: one allowed set per query."""
+        if hasattr(self.dense_index, "search_batch"):
+            return self.dense_index.search_batch(list(queries), top_k, **shared, **_given(allowed_ids_each=each))
+        return [self.dense_index.search(q, top_k, **shared, **_given(allowed_ids=e)) for q, e in zip(queries, each or [None] * len(queries))]
 
     @staticmethod
     def _check_distinct(distinct_by: Optional[str], per_group: Optional[int], complete_scores: bool, allowed_ids_each, what: str) -> None:
@@ -1668,24 +1679,22 @@ class HybridRetriever:
         return entries
 
     def _with_filters(self, entries: list, call):
-        """`call(filters)` with every entry a checked HybridFilter or None: a caller's own filter passes through; ids become a filter
-        made now -- one per distinct OBJECT -- and closed once the call has returned or raised (a filter's whole set-up and tear-down
-        per call: reuse a `make_filter` result for repeated questions)."""
-        made: Dict[int, HybridFilter] = {}
-        try:
-            filters = []
-            for e in entries:
-                if isinstance(e, HybridFilter):
-                    e = self._checked(e)
-                elif e is not None:
-                    if id(e) not in made:
-                        made[id(e)] = self.make_filter(e)
-                    e = made[id(e)]
-                filters.append(e)
-            return call(filters)
-        finally:
-            for flt in made.values():
-                flt.close()
+        """`call(filters)` with every entry a checked HybridFilter or None: a caller's own filter passes through; ids become a filter made now
+        and closed behind the call (`_with_made_filters`; a filter's whole set-up and tear-down: reuse a `make_filter` result for repeated questions)."""
+        return _with_made_filters(entries, lambda e: e is None or (isinstance(e, HybridFilter) and self._checked(e) is e), self.make_filter, call)
+
+    def _batch_call(self, what: str, body, queries: Sequence[str], n: int, pool: int, *, complete_scores: bool, allowed_ids, allowed_ids_each,
+                    distinct_by: Optional[str], per_group: Optional[int], early=None):
+        """The one way into the hybrid batch calls: the refusals around `distinct_by=` (`what` names the call in them), the call's own checks
+        (`early()`; an answer it gives is the call's), the filter keywords as one entry per query, then `body(request)` inside `_with_filters`."""
+        self._check_distinct(distinct_by, per_group, complete_scores, allowed_ids_each, what)
+        answer = None if early is None else early()
+        if answer is not None:
+            return answer
+        entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
+        if entries is None:
+            return body(_BatchRequest(queries, n, pool, complete_scores, None, distinct_by))
+        return self._with_filters(entries, lambda each: body(_BatchRequest(queries, n, pool, complete_scores, each, distinct_by)))
 
     def _fuse_columns(self, bm25_list: List[Tuple[str, float]], dense_list: List[Tuple[str, float]], top_k: int, extra=None):
         """Reference :485-523 on parallel lists: union of both pools, ids unknown to `self.documents` dropped, missing score 0.0,
@@ -1728,11 +1737,18 @@ class HybridRetriever:
                 keep.append(i)
             keep = keep[:max(int(top_k), 0)]
             ids, b, de, h = [ids[i] for i in keep], [b[i] for i in keep], [de[i] for i in keep], [h[i] for i in keep]
-        out = []
-        for doc_id, bs, ds, hs in zip(ids, b, de, h):
-            doc = self.documents[doc_id]
-            out.append(RetrievalResult(doc_id=doc_id, text=doc.text, bm25_score=bs, dense_score=ds, hybrid_score=hs, title=doc.title, metadata=doc.metadata))
-        return out
+        return self._results([ids], [b], [de], [h], [len(ids)])[0]
+
+    def _results(self, ids, b, d, h, count) -> List[List[RetrievalResult]]:
+        """The RetrievalResult lists of fused columns: [B][n] ids, bm25, dense and hybrid scores (arrays or lists), the first count[q]
+        of row q; text, title and metadata are read from `self.documents` now."""
+        documents = self.documents
+
+        def result(doc_id, bs, ds, hs):
+            doc = documents[doc_id]
+            return RetrievalResult(doc_id=doc_id, text=doc.text, bm25_score=bs, dense_score=ds, hybrid_score=hs, title=doc.title, metadata=doc.metadata)
+        rows = [x.tolist() if isinstance(x, np.ndarray) else x for x in (ids, b, d, h)]
+        return [[result(*c) for c in zip(row_ids[:int(n)], row_b, row_d, row_h)] for n, row_ids, row_b, row_d, row_h in zip(count, *rows)]
 
     # `complete_scores` (keyword-only extension on the four fusion calls): the reference's fusion writes 0.0 for the score a passage
     # did not get from the other retriever (:498-499) -- an artefact of the pool size that goes straight into the router's features.
@@ -1792,34 +1808,23 @@ class HybridRetriever:
         field in both pools and in the fused list, `hybrid_search(q, ..., distinct_by=key, allowed_ids=...)` value for value -- on the
         device route one grouped BM25 call, one grouped dense search and the grouped fusion (include/rq.h rq_sparse_topk_grouped_device,
         rq_search_grouped_device, rq_hybrid_fuse_grouped_device)."""
-        self._check_distinct(distinct_by, per_group, complete_scores, allowed_ids_each, "hybrid_search_batch")
-        entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
-        if entries is None:
-            return self._hybrid_search_batch(queries, top_k, retrieval_pool_size, complete_scores, None, distinct_by)
-        return self._with_filters(entries, lambda each: self._hybrid_search_batch(queries, top_k, retrieval_pool_size, complete_scores, each, distinct_by))
+        return self._batch_call("hybrid_search_batch", self._hybrid_search_batch, queries, top_k, retrieval_pool_size, complete_scores=complete_scores,
+                                allowed_ids=allowed_ids, allowed_ids_each=allowed_ids_each, distinct_by=distinct_by, per_group=per_group)
 
-    def _hybrid_search_batch(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
-                             distinct_by: Optional[str] = None):
-        fused = self._fuse_batch_rows(queries, top_k, retrieval_pool_size, complete_scores, each, distinct_by)
+    def _hybrid_search_batch(self, req: _BatchRequest) -> List[List[RetrievalResult]]:
+        fused = self._fused_rows(req)
         if fused is not None:
-            ids, b, de, hy, count = fused
-            idl, bl, dl, hl = ids.tolist(), b.tolist(), de.tolist(), hy.tolist()
-            out = []
-            for q in range(len(queries)):
-                res = []
-                for i in range(int(count[q])):
-                    doc = self.documents[idl[q][i]]
-                    res.append(RetrievalResult(doc_id=doc.id, text=doc.text, bm25_score=bl[q][i], dense_score=dl[q][i], hybrid_score=hl[q][i],
-                                               title=doc.title, metadata=doc.metadata))
-                out.append(res)
-            return out
-        if each is not None or distinct_by is not None:       # one side is not this module's own index class: the per-query calls
-            return [self.hybrid_search(q, top_k, retrieval_pool_size, complete_scores=complete_scores, allowed_ids=None if e is None else e.ids,
-                                       **_given(distinct_by=distinct_by)) for q, e in zip(queries, each or [None] * len(queries))]
-        if complete_scores:
-            return [self.hybrid_search(q, top_k, retrieval_pool_size, complete_scores=True) for q in queries]
-        dense, sparse = self._pools_batch(queries, retrieval_pool_size)
-        return [self._fuse(sparse[i], dense[i], top_k) for i in range(len(queries))]
+            return self._results(*fused)
+        return self._per_query_fallback(req, lambda q, **kw: self.hybrid_search(q, req.n, req.pool, **kw), lambda sparse, dense: self._fuse(sparse, dense, req.n))
+
+    def _per_query_fallback(self, req: _BatchRequest, per_query, fuse_pools) -> list:
+        """A batch call when one side is not this module's own index class (`_fused_rows` gave None): with filters, `distinct_by` or `complete_scores`
+        the per-query call, `per_query(query, **the keywords that were given)`; else `fuse_pools(sparse pool, dense pool)` over `_pools_batch`'s."""
+        if req.each is not None or req.distinct_by is not None or req.complete_scores:
+            shared = _given(complete_scores=True if req.complete_scores else None, distinct_by=req.distinct_by)
+            return [per_query(q, **shared, **_given(allowed_ids=None if e is None else e.ids)) for q, e in zip(req.queries, req.each or [None] * len(req.queries))]
+        dense, sparse = self._pools_batch(req.queries, req.pool)
+        return [fuse_pools(sparse[i], dense[i]) for i in range(len(req.queries))]
 
     def _pools_batch(self, queries: Sequence[str], retrieval_pool_size: int):
         dense = self.dense_search_batch(queries, retrieval_pool_size)
@@ -1862,95 +1867,59 @@ class HybridRetriever:
         fused columns (no RetrievalResult objects in between).  `allowed_ids` / `allowed_ids_each` as in `hybrid_search_batch`: query
         q's answer is `get_scores_for_router(q, ..., allowed_ids=entry_q)`.  `distinct_by` as in `hybrid_search_batch`: query q's answer
         is `get_scores_for_router(q, ..., distinct_by=key)`."""
-        self._check_distinct(distinct_by, per_group, complete_scores, allowed_ids_each, "get_scores_for_router_batch")
-        entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
-        if entries is None:
-            return self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, None, distinct_by)
-        return self._with_filters(entries, lambda each: self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by))
+        return self._batch_call("get_scores_for_router_batch", self._scores_for_router_batch, queries, num_passages, retrieval_pool_size,
+                                complete_scores=complete_scores, allowed_ids=allowed_ids, allowed_ids_each=allowed_ids_each, distinct_by=distinct_by, per_group=per_group)
 
-    def _scores_for_router_batch(self, queries: Sequence[str], num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
-                                 distinct_by: Optional[str] = None):
-        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by)
+    def _scores_for_router_batch(self, req: _BatchRequest) -> List[tuple]:
+        """`_router_columns` as `get_scores_for_router` returns them: per query (b, d, ids, texts), Python lists."""
+        ids, b, de = self._router_columns(req)
+        idl, documents = ids.tolist(), self.documents      # (texts are read from the store at call time, as the per-query path does)
+        texts = [[documents[d].text if d else "" for d in row] for row in idl]
+        return list(zip(b.tolist(), de.tolist(), idl, texts))
+
+    def _router_columns(self, req: _BatchRequest):
+        """The columns `get_scores_for_router_batch` hands the router, as arrays: ids [B][P] ("" = padding), b, d float64 [B][P] -- of
+        the fused rows of the whole batch, or, where `_fused_rows` gives none, of the per-query path."""
+        P = req.n
+        fused = self._fused_rows(req)
         if fused is not None:
             ids, b, de, _, count = fused
-            ids[np.arange(num_passages)[None, :] >= count[:, None]] = ""
-            idl = ids.tolist()
-            documents = self.documents                      # (texts are read from the store at call time, as the per-query path does)
-            texts = [[documents[d].text if d else "" for d in row] for row in idl]
-            return list(zip(b.tolist(), de.tolist(), idl, texts))
-        if each is not None or distinct_by is not None:       # one side is not this module's own index class: the per-query calls
-            return [self.get_scores_for_router(q, num_passages, retrieval_pool_size=retrieval_pool_size, complete_scores=complete_scores,
-                                               allowed_ids=None if e is None else e.ids, **_given(distinct_by=distinct_by))
-                    for q, e in zip(queries, each or [None] * len(queries))]
-        if complete_scores:
-            return [self.get_scores_for_router(q, num_passages, retrieval_pool_size=retrieval_pool_size, complete_scores=True) for q in queries]
-        dense, sparse = self._pools_batch(queries, retrieval_pool_size)
-        documents = self.documents
-        out = []
-        for i in range(len(queries)):
-            ids, b, de, _ = self._fuse_columns(sparse[i], dense[i], num_passages)
-            texts = [documents[d].text for d in ids]
-            pad = num_passages - len(ids)
-            if pad > 0:
-                b = b + [0.0] * pad; de = de + [0.0] * pad; ids = ids + [""] * pad; texts = texts + [""] * pad
-            out.append((b, de, ids, texts))
-        return out
-
-    # ---- the learned router over the fused pool (extension; include/rq.h "router gate", DESIGN.md 4.22) ------------------------------
-    def _route_on_device(self, router, num_passages: int, retrieval_pool_size: int, usable: bool) -> bool:
-        backend = getattr(self, "router_backend", "host")
-        if backend == "host":
-            return False
-        reason = None if usable else "one of the two indexes is not this module's own index class"
-        if reason is None:
-            reason = self._device_fusion_refusal(num_passages, retrieval_pool_size)
-        if reason is None:
-            try:
-                dn, bm = self.dense_index, self.bm25_index
-                router.native(dn._index.device if dn._index is not None else bm.__dict__.get("sparse_device", 0))
-            except _native.RqError as e:
-                reason = f"the gate cannot be placed on the device: {e}"
-        if reason is not None and backend == "gpu":
-            raise _native.RqError(f"router_backend='gpu': {reason}")
-        return reason is None
-
-    def _router_columns(self, queries: Sequence[str], num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list],
-                        distinct_by: Optional[str] = None):
-        """The columns `get_scores_for_router_batch` hands the router, as arrays: ids [B][P] ("" = padding), b, d float64 [B][P]."""
-        fused = self._fuse_batch_rows(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by)
-        if fused is not None:
-            ids, b, de, _, count = fused
-            ids[np.arange(num_passages)[None, :] >= count[:, None]] = ""
+            ids[np.arange(P)[None, :] >= count[:, None]] = ""
             return ids, b, de
-        cols = self._scores_for_router_batch(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by)
-        ids = np.empty((len(cols), num_passages), dtype=object)
+
+        def padded(sparse, dense):
+            ids, b, de, _ = self._fuse_columns(sparse, dense, P)
+            pad = max(P - len(ids), 0)
+            return b + [0.0] * pad, de + [0.0] * pad, ids + [""] * pad
+        cols = self._per_query_fallback(req, lambda q, **kw: self.get_scores_for_router(q, P, retrieval_pool_size=req.pool, **kw), padded)
+        ids = np.empty((len(cols), P), dtype=object)
         for q, c in enumerate(cols):
             ids[q, :] = c[2]
-        return ids, np.array([c[0] for c in cols], np.float64).reshape(len(cols), num_passages), np.array([c[1] for c in cols], np.float64).reshape(len(cols), num_passages)
+        return ids, np.array([c[0] for c in cols], np.float64).reshape(len(cols), P), np.array([c[1] for c in cols], np.float64).reshape(len(cols), P)
 
-    def _route_batch(self, queries: Sequence[str], router, top_k: int, num_passages: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
-                     distinct_by: Optional[str] = None):
-        bm, dn = self.bm25_index, self.dense_index
-        r = min(int(top_k), int(num_passages))
-        usable = isinstance(bm, BM25Index) and isinstance(dn, DenseIndex)
-        if self._route_on_device(router, num_passages, retrieval_pool_size, usable):
-            ids, b, de, w, h, count = self._fuse_batch_device(list(queries), num_passages, retrieval_pool_size, complete_scores, each, route=(router, r),
-                                                              distinct_by=distinct_by)
+    # ---- the learned router over the fused pool (extension; include/rq.h "router gate", DESIGN.md 4.22) ------------------------------
+    def _route_batch(self, req: _BatchRequest, router, top_k: int, return_weights: bool):
+        P, r = req.n, min(int(top_k), req.n)
+
+        def refusal():
+            if not (isinstance(self.bm25_index, BM25Index) and isinstance(self.dense_index, DenseIndex)):
+                return "one of the two indexes is not this module's own index class"
+            reason = self._device_fusion_refusal(P, req.pool)
+            if reason is None:
+                try:
+                    router.native(self._fusion_device())
+                except _native.RqError as e:
+                    reason = f"the gate cannot be placed on the device: {e}"
+            return reason
+        if self._on_device("router_backend", refusal):
+            ids, b, de, w, h, count = self._fuse_batch_device(req, route=(router, r))
         else:
-            ids, cb, cd = self._router_columns(queries, num_passages, retrieval_pool_size, complete_scores, each, distinct_by)
-            keys = np.where(ids != "", np.arange(num_passages, dtype=np.int32)[None, :], -1)
-            _, b, de, w, h, pos, count = router.rerank(keys, cb, cd, np.full(len(queries), num_passages), r)
+            ids, cb, cd = self._router_columns(req)
+            keys = np.where(ids != "", np.arange(P, dtype=np.int32)[None, :], -1)
+            _, b, de, w, h, pos, count = router.rerank(keys, cb, cd, np.full(len(req.queries), P), r)
             ids = np.take_along_axis(ids, np.where(pos >= 0, pos, 0).astype(np.int64), 1)
-        idl, bl, dl, hl = ids.tolist(), b.tolist(), de.tolist(), h.tolist()
-        out = []
-        for q in range(len(queries)):
-            res = []
-            for i in range(int(count[q])):
-                doc = self.documents[idl[q][i]]
-                res.append(RetrievalResult(doc_id=doc.id, text=doc.text, bm25_score=bl[q][i], dense_score=dl[q][i], hybrid_score=hl[q][i],
-                                           title=doc.title, metadata=doc.metadata))
-            out.append(res)
-        return out, w
+        out = self._results(ids, b, de, h, count)
+        return (out, w) if return_weights else out
 
     def route_batch(self, queries: Sequence[str], router, top_k: int = 10, *, num_passages: int = 20, retrieval_pool_size: int = 50, complete_scores: bool = False,
                     allowed_ids=None, allowed_ids_each=None, return_weights: bool = False, distinct_by: Optional[str] = None, per_group: Optional[int] = None):
@@ -1962,18 +1931,15 @@ class HybridRetriever:
         `distinct_by`: the fused passages are `get_scores_for_router(q, ..., distinct_by=key)`'s, one per value of that field; the
         rerank is unchanged.  Where it runs is `router_backend`'s choice."""
         queries = list(queries)
-        self._check_distinct(distinct_by, per_group, complete_scores, allowed_ids_each, "route_batch")
-        if int(num_passages) < 1 or int(top_k) < 1:
-            raise ValueError(f"num_passages {num_passages} and top_k {top_k} must be at least 1")
-        if not queries:
-            return ([], np.zeros((0, min(int(top_k), int(num_passages))))) if return_weights else []
-        entries = self._filter_entries(len(queries), allowed_ids, allowed_ids_each)
-        if entries is None:
-            out, w = self._route_batch(queries, router, top_k, int(num_passages), retrieval_pool_size, complete_scores, None, distinct_by)
-        else:
-            out, w = self._with_filters(entries, lambda each: self._route_batch(queries, router, top_k, int(num_passages), retrieval_pool_size, complete_scores, each,
-                                                                                distinct_by))
-        return (out, w) if return_weights else out
+
+        def early():      # this call's own two checks, where they stand in the order of refusals: behind `distinct_by`'s, before the filters'
+            if int(num_passages) < 1 or int(top_k) < 1:
+                raise ValueError(f"num_passages {num_passages} and top_k {top_k} must be at least 1")
+            if not queries:
+                return ([], np.zeros((0, min(int(top_k), int(num_passages))))) if return_weights else []
+        return self._batch_call("route_batch", lambda req: self._route_batch(req, router, top_k, return_weights), queries, int(num_passages), retrieval_pool_size,
+                                complete_scores=complete_scores, allowed_ids=allowed_ids, allowed_ids_each=allowed_ids_each, distinct_by=distinct_by,
+                                per_group=per_group, early=early)
 
     def route(self, query: str, router, top_k: int = 10, **keywords):
         """`route_batch([query], ...)[0]` (with `return_weights=True`: the list and the weights of that one question)."""
@@ -2028,14 +1994,21 @@ class HybridRetriever:
             return "the dense index holds an id twice: dense rows do not map to distinct keys"
         return None
 
-    def _fuse_on_device(self, top_k: int, retrieval_pool_size: int) -> bool:
-        backend = getattr(self, "fusion_backend", "host")
+    def _on_device(self, which: str, refusal) -> bool:
+        """The placement rule of `fusion_backend` and `router_backend` (`which` names the attribute): "host" stays on the host; "auto"
+        takes the device unless `refusal()` gives a reason; "gpu" raises that reason."""
+        backend = getattr(self, which, "host")
         if backend == "host":
             return False
-        reason = self._device_fusion_refusal(top_k, retrieval_pool_size)
+        reason = refusal()
         if reason is not None and backend == "gpu":
-            raise _native.RqError(f"fusion_backend='gpu': {reason}")
+            raise _native.RqError(f"{which}='gpu': {reason}")
         return reason is None
+
+    def _fusion_device(self) -> int:
+        """The device both pools are drawn on: the dense index's, the sparse index's while the dense index holds nothing."""
+        dn = self.dense_index
+        return dn._index.device if dn._index is not None else self.bm25_index.__dict__.get("sparse_device", 0)
 
     def _hybrid_map(self, ks, device: int):
         """The device copy of the key space (`_native.HybridMap`): built by the first fusion that wants it, dropped with the key space."""
@@ -2054,127 +2027,150 @@ class HybridRetriever:
             tables[key] = np.fromiter((_native.GROUP_NONE if v is None else ids.setdefault(v, len(ids)) for v in values), np.int32, len(ks["ids"]))
         return tables[key]
 
-    def _fuse_batch_device(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool, each: Optional[list] = None,
-                           route: Optional[tuple] = None, distinct_by: Optional[str] = None):
-        """`_fuse_batch_rows` with both pools left where they are drawn: token ids and query vectors go down, rq_sparse_topk_device and
-        rq_search_device (with its fixup) fill the pools in HBM, `complete_scores` adds rq_hybrid_missing_device and the two row-scoring
-        calls, rq_hybrid_fuse_device ranks, and one copy brings [B][top_k] keys, scores and the counts back.  Same return value.
-        `each` (one HybridFilter or None per query): the mask table goes down once, rq_sparse_topk_masked_device and
-        rq_search_filtered_each_device (with its fixup; complete in stream order) fill the pools, the rest runs as it is -- pools that
-        are already filtered fuse as they are.
+    def _fuse_batch_device(self, req: _BatchRequest, route: Optional[tuple] = None):
+        """`_fused_rows` with both pools left where they are drawn, in steps on torch's current stream of the fusion device: token ids
+        and query vectors go down and fill the two pools in HBM (`_device_sparse_pool`, `_device_dense_pool`), `complete_scores` adds
+        the scores they miss (`_device_completions`), `_device_fuse` ranks, and one copy brings [B][top_k] keys, scores and the counts
+        back (`_device_block`).  Same return value.  Pools that are already filtered (`each`) or grouped (`distinct_by`, DESIGN.md 4.23:
+        never with `complete_scores`, `each` then holds one filter for the whole batch) fuse as they are.
         `route` = (router.RouterGate, top_r): the fused block stays on the device, rq_router_rerank_device runs on the same stream
-        over its keys, b, d and counts, and the one copy brings [B][top_r] up instead; the return value is then
-        (ids, b, d, w, h -- [B][top_r] -- and count [B]).
-        `distinct_by` (never with `complete_scores`, `each` then holds one filter for the whole batch): the sparse pool
-        comes from rq_sparse_topk_grouped_device, the dense pool from rq_search_grouped_device (with its fixup) under that one filter,
-        and rq_hybrid_fuse_grouped_device ranks all candidates and keeps the first of every group; the rest runs as it is.  Each stage
-        has a group table of its own: BM25 documents, dense rows (`_push_groups`), keys (`_key_groups`)."""
+        over its keys, b, d and counts, and the one copy brings [B][top_r] up instead: (ids, b, d, w, h -- [B][top_r] -- and count [B])."""
         import torch
-        bm, dn = self.bm25_index, self.dense_index
-        B, k, K1 = len(queries), int(top_k), max(int(retrieval_pool_size), 1)
+        queries = list(req.queries)
+        B, k, K1 = len(queries), int(req.n), max(int(req.pool), 1)
         ks = self._key_space()
-        device = dn._index.device if dn._index is not None else bm.__dict__.get("sparse_device", 0)
+        device = self._fusion_device()
         hm = self._hybrid_map(ks, device)
         dev = torch.device("cuda", device)
         with torch.cuda.device(dev):
             s = torch.cuda.current_stream(dev).cuda_stream
-            d_sp_rows = torch.empty((B, K1), device=dev, dtype=torch.int32)
-            d_sp_scores = torch.empty((B, K1), device=dev, dtype=torch.float64)
-            sp = None
-            if bm.bm25 is not None and bm.doc_ids and retrieval_pool_size > 0:
-                c = bm._csr()
-                sp = bm._sparse_index(c)
-                q_ptr, q_tok = bm._query_csr(c, queries)
-                d_ptr = torch.tensor(q_ptr, dtype=torch.int64).to(dev)
-                d_tok = torch.tensor(q_tok or [0], dtype=torch.int32).to(dev)
-                masked = {}
-                if each is not None:
-                    masks, mask_of = bm._mask_table([None if e is None else e.sparse for e in each])
-                    # (torch has no arithmetic on uint32 and needs none: the words travel as int32)
-                    masked = {"d_masks": None if masks is None else torch.from_numpy(masks.view(np.int32)).to(dev),
-                              "n_masks": 0 if masks is None else len(masks), "d_mask_of": torch.from_numpy(mask_of).to(dev)}
-                if distinct_by is not None:
-                    sp = bm._sparse_index_grouped(c, distinct_by)
-                    sp.topk_grouped_device(d_ptr, d_tok, B, len(q_tok), K1, d_sp_rows, d_sp_scores, torch.empty((B,), device=dev, dtype=torch.int32), stream=s, **masked)
-                else:
-                    sp.topk_device(d_ptr, d_tok, B, len(q_tok), K1, d_sp_rows, d_sp_scores, stream=s, **masked)
-            else:
-                d_sp_rows.fill_(-1)
-                d_sp_scores.zero_()
-            K2, d_q, d_de_rows, d_de_scores = 0, None, None, None
-            if not dn._nothing_to_search(retrieval_pool_size, B):
-                d_q = dn._embed_device(queries)
-                if d_q is None:
-                    d_q = torch.from_numpy(np.ascontiguousarray(dn._embed_matrix(list(queries)), dtype=np.float32)).to(dev)
-                d_q = d_q.to(torch.float32).contiguous()
-                dn._check_dim(int(d_q.shape[1]))
-                K2 = dn._k(retrieval_pool_size)
-                d_de_rows = torch.empty((B, K2), device=dev, dtype=torch.int64)
-                d_de_scores = torch.empty((B, K2), device=dev, dtype=torch.float32)
-                d_status = torch.empty((B,), device=dev, dtype=torch.int32)
-                if distinct_by is not None:
-                    dn._push_groups(distinct_by)
-                    flt = None if each is None or each[0] is None else each[0].dense
-                    d_groups = torch.empty((B, K2), device=dev, dtype=torch.int32)
-                    dn._index.search_grouped_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, d_groups, None, d_status, s, row_filter=flt)
-                    if bool(d_status.any()):                                   # fewer than K2 groups in the first rung, or no certificate
-                        dn._index.search_grouped_fixup_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, d_groups, None, d_status, s, row_filter=flt)
-                elif each is not None:
-                    filters = [None if e is None else e.dense for e in each]
-                    dn._index.search_filtered_each_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, filters, s)
-                    if bool(d_status.any()):
-                        dn._index.search_filtered_each_fixup_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, filters, s)
-                else:
-                    dn._index.search_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, s)
-                    dn._index.search_flush_device(s)
-                    if bool(d_status.any()):                                   # rare: a certificate failed -> exact repair on the device
-                        dn._index.search_fixup_device(d_q, B, K2, dn.metric, d_de_scores, d_de_rows, None, d_status, s)
-            extra = {}
-            if complete_scores:
-                d_miss_dense = torch.empty((B, K1), device=dev, dtype=torch.int64)
-                d_miss_sparse = torch.empty((B, max(K2, 1)), device=dev, dtype=torch.int32)
-                hm.missing_device(d_sp_rows, d_de_rows, B, K1, K2, d_miss_dense, d_miss_sparse, s)
-                if K2:
-                    d_extra_dense = torch.empty((B, K1), device=dev, dtype=torch.float32)
-                    dn._index.score_rows_device(d_q, B, d_miss_dense, K1, dn.metric, d_extra_dense, s)
-                    extra.update(d_miss_dense=d_miss_dense, d_extra_dense=d_extra_dense)
-                    if sp is not None:
-                        d_extra_sparse = torch.empty((B, K2), device=dev, dtype=torch.float64)
-                        sp.score_rows_device(d_ptr, d_tok, B, len(q_tok), d_miss_sparse, K2, d_extra_sparse, s)
-                        extra.update(d_miss_sparse=d_miss_sparse, d_extra_sparse=d_extra_sparse)
-            # one block, one copy back: b, d, h (float64) | keys (int32) | count (int32)
-            n = B * k
-            block = torch.empty((7 * n + B,), device=dev, dtype=torch.int32)
-            scores = block[: 6 * n].view(torch.float64)
-            if distinct_by is not None:
-                if ks.get("map_group_key") != distinct_by:
-                    hm.set_groups(self._key_groups(ks, distinct_by))
-                    ks["map_group_key"] = distinct_by
-                hm.fuse_grouped_device(d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B, K1, K2, k, block[6 * n: 7 * n], scores[:n], scores[n: 2 * n],
-                                       scores[2 * n:], None, block[7 * n:], s)
-            else:
-                hm.fuse_device(d_sp_rows, d_sp_scores, d_de_rows, d_de_scores, B, K1, K2, k, block[6 * n: 7 * n], scores[:n], scores[n: 2 * n], scores[2 * n:],
-                               None, block[7 * n:], s, **extra)
+            sparse = self._device_sparse_pool(req, queries, K1, dev, s)
+            dense = self._device_dense_pool(req, queries, dev, s)
+            extra = self._device_completions(hm, sparse, dense, B, K1, dev, s) if req.complete_scores else {}
+            (b, de, h), (keys,), count, read = self._device_block(dev, B, k, 3, 1)
+            self._device_fuse(req, ks, hm, (sparse[0], sparse[1], dense[2], dense[3], B, K1, dense[0], k), (keys, b, de, h, None, count, s), extra)
             if route is not None:
                 gate, r = route
-                m = B * r
-                out = torch.empty((10 * m + B,), device=dev, dtype=torch.int32)      # b, d, w, h (float64) | keys, pos (int32) | count (int32)
-                o64 = out[: 8 * m].view(torch.float64)
-                gate.native(device).rerank_device(block[6 * n: 7 * n], scores[:n], scores[n: 2 * n], block[7 * n:], B, k, r, out[8 * m: 9 * m], o64[:m],
-                                                  o64[m: 2 * m], o64[2 * m: 3 * m], o64[3 * m:], out[9 * m: 10 * m], out[10 * m:], mode=gate.mode,
-                                                  stats=gate.stats, stream=s)
-                host = out.cpu().numpy()
-                sc = host[: 8 * m].view(np.float64).reshape(4, B, r)
-                keys = host[8 * m: 9 * m].reshape(B, r)
-                return ks["ids"][np.where(keys >= 0, keys, 0)], sc[0], sc[1], sc[2], sc[3], host[10 * m:].astype(np.int64)
+                (ob, od, ow, oh), (okeys, opos), ocount, read = self._device_block(dev, B, r, 4, 2)
+                gate.native(device).rerank_device(keys, b, de, count, B, k, r, okeys, ob, od, ow, oh, opos, ocount, mode=gate.mode, stats=gate.stats, stream=s)
+            scores, (keys, *_), count = read()
+        return (ks["ids"][np.where(keys >= 0, keys, 0)], *scores, count)
+
+    def _device_sparse_pool(self, req: _BatchRequest, queries: List[str], K1: int, dev, s):
+        """The sparse pool in HBM: (rows int32 [B][K1], scores float64 [B][K1], what rescoring needs -- the index, the queries' token
+        pointers, tokens and their count -- or None where BM25 has nothing to search: a pool of padding)."""
+        import torch
+        bm, B = self.bm25_index, len(queries)
+        d_rows = torch.empty((B, K1), device=dev, dtype=torch.int32)
+        d_scores = torch.empty((B, K1), device=dev, dtype=torch.float64)
+        if not (bm.bm25 is not None and bm.doc_ids and req.pool > 0):
+            d_rows.fill_(-1)
+            d_scores.zero_()
+            return d_rows, d_scores, None
+        c = bm._csr()
+        sp = bm._sparse_index(c)
+        q_ptr, q_tok = bm._query_csr(c, queries)
+        d_ptr = torch.tensor(q_ptr, dtype=torch.int64).to(dev)
+        d_tok = torch.tensor(q_tok or [0], dtype=torch.int32).to(dev)
+        masked = {}
+        if req.each is not None:
+            masks, mask_of = bm._mask_table([None if e is None else e.sparse for e in req.each])
+            # (torch has no arithmetic on uint32 and needs none: the words travel as int32)
+            masked = {"d_masks": None if masks is None else torch.from_numpy(masks.view(np.int32)).to(dev),
+                      "n_masks": 0 if masks is None else len(masks), "d_mask_of": torch.from_numpy(mask_of).to(dev)}
+        if req.distinct_by is not None:
+            sp = bm._sparse_index_grouped(c, req.distinct_by)
+            sp.topk_grouped_device(d_ptr, d_tok, B, len(q_tok), K1, d_rows, d_scores, torch.empty((B,), device=dev, dtype=torch.int32), stream=s, **masked)
+        else:
+            sp.topk_device(d_ptr, d_tok, B, len(q_tok), K1, d_rows, d_scores, stream=s, **masked)
+        return d_rows, d_scores, (sp, d_ptr, d_tok, len(q_tok))
+
+    def _device_dense_pool(self, req: _BatchRequest, queries: List[str], dev, s):
+        """The dense pool in HBM: (K2, query vectors fp32 [B][dim], rows int64 [B][K2], scores float32 [B][K2]), or (0, None, None, None)
+        where the dense index has nothing to search.  One of three routes -- grouped under the batch's one filter, one filter per
+        query, plain -- as (search, fixup, their arguments); the status is read once, and the fixup runs where it says so."""
+        import torch
+        dn, B = self.dense_index, len(queries)
+        if dn._nothing_to_search(req.pool, B):
+            return 0, None, None, None
+        d_q = dn._embed_device(queries)
+        if d_q is None:
+            d_q = torch.from_numpy(np.ascontiguousarray(dn._embed_matrix(list(queries)), dtype=np.float32)).to(dev)
+        d_q = d_q.to(torch.float32).contiguous()
+        dn._check_dim(int(d_q.shape[1]))
+        K2, index = dn._k(req.pool), dn._index
+        d_rows = torch.empty((B, K2), device=dev, dtype=torch.int64)
+        d_scores = torch.empty((B, K2), device=dev, dtype=torch.float32)
+        d_status = torch.empty((B,), device=dev, dtype=torch.int32)
+        keywords = {}
+        if req.distinct_by is not None:      # (its fixup: fewer than K2 groups in the first rung, or no certificate)
+            dn._push_groups(req.distinct_by)
+            keywords = {"row_filter": None if req.each is None or req.each[0] is None else req.each[0].dense}
+            d_groups = torch.empty((B, K2), device=dev, dtype=torch.int32)
+            search, fixup, args = index.search_grouped_device, index.search_grouped_fixup_device, (d_scores, d_rows, d_groups, None, d_status, s)
+        elif req.each is not None:
+            filters = [None if e is None else e.dense for e in req.each]
+            search, fixup, args = index.search_filtered_each_device, index.search_filtered_each_fixup_device, (d_scores, d_rows, None, d_status, filters, s)
+        else:                                # (its fixup is rare: a certificate failed -> exact repair on the device)
+            search, fixup, args = index.search_device, index.search_fixup_device, (d_scores, d_rows, None, d_status, s)
+        search(d_q, B, K2, dn.metric, *args, **keywords)
+        if req.distinct_by is None and req.each is None:
+            index.search_flush_device(s)
+        if bool(d_status.any()):
+            fixup(d_q, B, K2, dn.metric, *args, **keywords)
+        return K2, d_q, d_rows, d_scores
+
+    def _device_completions(self, hm, sparse, dense, B: int, K1: int, dev, s) -> dict:
+        """`complete_scores` in HBM: which candidates miss a score (rq_hybrid_missing_device), then the dense scores of the sparse pool
+        and the BM25 scores of the dense pool; returns the miss / extra keywords of `fuse_device`."""
+        import torch
+        d_sp_rows, _, rescore = sparse
+        K2, d_q, d_de_rows, _ = dense
+        dn, extra = self.dense_index, {}
+        d_miss_dense = torch.empty((B, K1), device=dev, dtype=torch.int64)
+        d_miss_sparse = torch.empty((B, max(K2, 1)), device=dev, dtype=torch.int32)
+        hm.missing_device(d_sp_rows, d_de_rows, B, K1, K2, d_miss_dense, d_miss_sparse, s)
+        if K2:
+            d_extra_dense = torch.empty((B, K1), device=dev, dtype=torch.float32)
+            dn._index.score_rows_device(d_q, B, d_miss_dense, K1, dn.metric, d_extra_dense, s)
+            extra.update(d_miss_dense=d_miss_dense, d_extra_dense=d_extra_dense)
+            if rescore is not None:
+                sp, d_ptr, d_tok, n_tok = rescore
+                d_extra_sparse = torch.empty((B, K2), device=dev, dtype=torch.float64)
+                sp.score_rows_device(d_ptr, d_tok, B, n_tok, d_miss_sparse, K2, d_extra_sparse, s)
+                extra.update(d_miss_sparse=d_miss_sparse, d_extra_sparse=d_extra_sparse)
+        return extra
+
+    def _device_fuse(self, req: _BatchRequest, ks, hm, pools: tuple, out: tuple, extra: dict) -> None:
+        """Rank `pools` (rows and scores of both, B, K1, K2, top_k) into `out` (keys, b, d, h, positions, count, stream):
+        rq_hybrid_fuse_device, or under `distinct_by` the grouped form over the key groups of that field (pushed when it changes)."""
+        if req.distinct_by is None:
+            return hm.fuse_device(*pools, *out, **extra)
+        if ks.get("map_group_key") != req.distinct_by:
+            hm.set_groups(self._key_groups(ks, req.distinct_by))
+            ks["map_group_key"] = req.distinct_by
+        hm.fuse_grouped_device(*pools, *out)
+
+    @staticmethod
+    def _device_block(dev, B: int, width: int, n_scores: int, n_keys: int):
+        """One int32 block in HBM: n_scores float64 planes [B][width] | n_keys int32 planes [B][width] | count int32 [B].  Returns the planes and
+        the count as flat device views, and `read()`: the one copy up, as (float64 [n_scores][B][width], int32 [n_keys][B][width], count int64 [B])."""
+        import torch
+        m, a, z = B * width, 2 * n_scores * B * width, (2 * n_scores + n_keys) * B * width
+        block = torch.empty((z + B,), device=dev, dtype=torch.int32)
+        scores = block[:a].view(torch.float64)
+
+        def read():
             host = block.cpu().numpy()
-        sc = host[: 6 * n].view(np.float64)
-        keys = host[6 * n: 7 * n].reshape(B, k)
-        return (ks["ids"][np.where(keys >= 0, keys, 0)], sc[:n].reshape(B, k), sc[n: 2 * n].reshape(B, k), sc[2 * n:].reshape(B, k),
-                host[7 * n:].astype(np.int64))
+            return host[:a].view(np.float64).reshape(n_scores, B, width), host[a:z].reshape(n_keys, B, width), host[z:].astype(np.int64)
+        return [scores[i * m: (i + 1) * m] for i in range(n_scores)], [block[a + i * m: a + (i + 1) * m] for i in range(n_keys)], block[z:], read
 
     def _fuse_batch_rows(self, queries: Sequence[str], top_k: int, retrieval_pool_size: int, complete_scores: bool = False, each: Optional[list] = None,
                          distinct_by: Optional[str] = None):
+        """`_fused_rows` of these arguments (the name tools, tests and include/rq.h know the batched fusion by)."""
+        return self._fused_rows(_BatchRequest(queries, top_k, retrieval_pool_size, complete_scores, each, distinct_by))
+
+    def _fused_rows(self, req: _BatchRequest):
         """`_fuse_columns` for every query of the batch at once, on integer keys: same candidates (union of both pools in first-seen
         order -- BM25 pool, then dense pool -- ids unknown to `self.documents` dropped), same float64 arithmetic (`max(...) or 1` over all
         candidates, hybrid = (b/max_b + d/max_d)/2), same stable descending sort, first top_k.  Returns (ids [B][top_k] object,
@@ -2191,16 +2187,16 @@ class HybridRetriever:
         pools come from `search_batch(distinct_by=)`, the dense pools from the grouped `search_batch(distinct_by=)`, and `_fuse(...,
         distinct_by=)` runs per query -- the per-query call's own steps; the device route is `_fuse_batch_device`'s."""
         bm, dn = self.bm25_index, self.dense_index
+        queries, top_k, retrieval_pool_size, complete_scores, each, distinct_by = req.queries, req.n, req.pool, req.complete_scores, req.each, req.distinct_by
         if not (isinstance(bm, BM25Index) and isinstance(dn, DenseIndex)) or len(queries) == 0 or top_k <= 0:
             return None
-        if self._fuse_on_device(top_k, retrieval_pool_size):
-            return self._fuse_batch_device(list(queries), top_k, retrieval_pool_size, complete_scores, each, distinct_by=distinct_by)
+        if self._on_device("fusion_backend", lambda: self._device_fusion_refusal(top_k, retrieval_pool_size)):
+            return self._fuse_batch_device(req)
         B = len(queries)
         if distinct_by is not None:
             e = None if each is None else each[0]
             sparse = bm.search_batch(list(queries), retrieval_pool_size, **self._sparse_kw(), distinct_by=distinct_by, **_given(allowed_ids=None if e is None else e.sparse))
-            dense_allowed = None if e is None else (list(e.ids) if e.dense is None else e.dense)
-            dense = [[(d, sc) for d, sc, _ in r] for r in dn.search_batch(list(queries), retrieval_pool_size, distinct_by=distinct_by, **_given(allowed_ids=dense_allowed))]
+            dense = [[(d, sc) for d, sc, _ in r] for r in dn.search_batch(list(queries), retrieval_pool_size, distinct_by=distinct_by, **_given(allowed_ids=self._dense_half(e)))]
             ids = np.full((B, top_k), "", dtype=object)
             b, de, hy, count = np.zeros((B, top_k)), np.zeros((B, top_k)), np.zeros((B, top_k)), np.zeros(B, np.int64)
             for q in range(B):
