@@ -20,6 +20,24 @@
  * single-threaded, streaming_index.py has no locks).  There is no CPU fallback: without a gfx950
  * device every call that touches data fails with RQ_ENODEVICE.
  *
+ * Caller buffers (every pointer argument of every *_device call: queries, thresholds, candidate lists, pools, masks, CSR query
+ * arrays, and all outputs; pinned by tests/test_gpu_memory_contract.py):
+ *   alignment: the natural alignment of the element type -- 4 bytes for float / int32_t / uint32_t, 8 bytes for double / int64_t /
+ *            uint64_t, 2 bytes for fp16 rows -- and no more.  A view into a larger array is as good as an allocation of its own.
+ *            Every load and store of a caller's array is one element wide; the wider accesses of the kernels touch only the
+ *            library's own padded buffers.
+ *   extents: a call reads and writes exactly the extents its arguments state -- [B][dim], [B][k], [B][k][s], [B][cap], [B],
+ *            [B + 1], [n_q_tokens], [n_masks][W] -- whatever the number of query slots of the passes that serve it: no byte in
+ *            front of an array, none behind it, no row of a pad slot.  Every slot of every output array is written: a result, or
+ *            the padding the call defines (-1, 0.0, key 0, RQ_GROUP_NONE, count 0), d_status included.  An optional output
+ *            that is NULL is skipped.  A fixup form writes the rows of the flagged queries only.
+ *   inputs:  are never written.
+ *   refusal: a call that returns RQ_EINVAL has written none of its outputs.
+ *   deferred outputs: under "pipeline" 1 and 2, with announced batches and in bundles (see the flush call below) the outputs of a
+ *            call belong to the library from the call until the call that completes them, or the stream's flush, or the release
+ *            of the stream: they are written by later launches, each call's own [B][k] and d_status and nothing else, and must
+ *            stay valid and untouched until then.
+ *
  * Score definition (pinned by oracle/dense_oracle.py, "parity unpinned" upstream -- Chroma's own
  * arithmetic is not in the reference tree):
  *   cosine:  s = fp32( dot64(q, x) / (||q||_64 * ||x||_64 + 1e-30) )   on the STORED fp16 row x

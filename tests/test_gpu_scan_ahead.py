@@ -2,12 +2,21 @@
 batch (rq_search_hint_next_device) scans both batches in ONE 128-query pass; the next call, if it brings exactly the announced
 batch and metric, enqueues no scan and only runs the two tails.  Every query of every call is compared with the oracle (rows
 identical, |score difference| <= 1e-6, status 0) with the candidate lists poisoned before every tail (poison_cand), and the
-counters say which calls were paired: one scan launch per matched pair, hints_used = calls whose announcement was acted on."""
+counters say which calls were paired: one scan launch per matched pair, hints_used = calls whose announcement was acted on.
+
+Every output buffer, d_status included, lies between guard words (tests/guarded.py): a call's outputs are written by a LATER launch
+here, and that launch must write every slot of them and nothing in front of or behind them."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from oracle import dense_oracle as orc
 from rag_uq_amd import _native as nat
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from guarded import guarded  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SCORE_TOL = 1e-6
@@ -52,14 +61,28 @@ class Shard:
             self.exact[(qi, metric)] = orc.exact_scores(self.qs[qi], self.x16, metric)
         return orc.topk_from_scores(self.exact[(qi, metric)][:B], k)
 
+    def bufs(self, B, k):
+        """(scores, rows, status) of one call, each between guard words"""
+        import torch
+        return guarded((B, k), torch.float32, self.dev), guarded((B, k), torch.int64, self.dev), guarded((B,), torch.int32, self.dev)
+
+    def check(self, qi, B, k, metric, sc, rw, st):
+        es, er = self.oracle(qi, B, k, metric)
+        where = f"q{qi} B={B} k={k} metric={metric}"
+        for name, g in (("scores", sc), ("rows", rw), ("status", st)):
+            g.check(f"{where}: {name}")
+        assert int(st.view.abs().sum()) == 0, f"{where}: status {st.cpu().tolist()}"
+        got_r, got_s = rw.numpy(), sc.numpy()
+        assert np.array_equal(got_r, er), f"{where}: rows differ at {np.argwhere(got_r != er)[:4].tolist()}"
+        assert float(np.abs(got_s - es).max()) <= SCORE_TOL, where
+
     def run(self, ops):
         """ops: ("hint", qi or None, B, stream) | ("search", qi, B, k, metric, stream) | ("flush", stream) | ("release", stream).
         Returns (scan launches, hints used) of the sequence; every search is checked against the oracle."""
         import torch
         idx = self.idx
-        # output buffers, filled with markers on torch's stream BEFORE any search is enqueued on the callers' streams
-        bufs = [(torch.full((op[2], op[3]), -7.0, device=self.dev), torch.full((op[2], op[3]), -7, device=self.dev, dtype=torch.int64),
-                 torch.full((op[2],), 9, device=self.dev, dtype=torch.int32)) for op in ops if op[0] == "search"]
+        # output buffers between guard words, filled with the sentinel on torch's stream BEFORE any search is enqueued on the callers' streams
+        bufs = [self.bufs(op[2], op[3]) for op in ops if op[0] == "search"]
         torch.cuda.synchronize()
         idx.reset_timing()
         used0 = int(idx.get_option("hints_used"))
@@ -78,12 +101,7 @@ class Shard:
                 idx.stream_release(op[1])
         torch.cuda.synchronize()
         for (_, qi, B, k, metric, s), sc, rw, st in outs:
-            es, er = self.oracle(qi, B, k, metric)
-            where = f"q{qi} B={B} k={k} metric={metric}"
-            assert int(st.abs().sum()) == 0, f"{where}: status {st.cpu().tolist()}"
-            got_r, got_s = rw.cpu().numpy(), sc.cpu().numpy()
-            assert np.array_equal(got_r, er), f"{where}: rows differ at {np.argwhere(got_r != er)[:4].tolist()}"
-            assert float(np.abs(got_s - es).max()) <= SCORE_TOL, where
+            self.check(qi, B, k, metric, sc, rw, st)
         return int(idx.timing()["scan_launches"]), int(idx.get_option("hints_used")) - used0
 
     def close(self):
@@ -173,8 +191,7 @@ def test_search_train_pairs_per_stream(shard, stream):
     import torch
     idx = shard.idx
     n, k = 6, 10
-    outs = [(torch.empty((64, k), device=shard.dev), torch.empty((64, k), device=shard.dev, dtype=torch.int64),
-             torch.full((64,), 9, device=shard.dev, dtype=torch.int32)) for _ in range(n)]
+    outs = [shard.bufs(64, k) for _ in range(n)]
     train = idx.make_train(shard.dqs[:n], [o[0] for o in outs], [o[1] for o in outs], None, [o[2] for o in outs], [stream])
     torch.cuda.synchronize()          # (the status markers are written on torch's stream)
     idx.reset_timing()
@@ -185,10 +202,7 @@ def test_search_train_pairs_per_stream(shard, stream):
     assert int(idx.timing()["scan_launches"]) == 3
     assert int(idx.get_option("hints_used")) - used0 == 5
     for qi, (sc, rw, st) in enumerate(outs):
-        es, er = shard.oracle(qi, 64, k, 0)
-        assert int(st.abs().sum()) == 0
-        assert np.array_equal(rw.cpu().numpy(), er)
-        assert float(np.abs(sc.cpu().numpy() - es).max()) <= SCORE_TOL
+        shard.check(qi, 64, k, 0, sc, rw, st)
 
 
 def test_stream_release_with_a_half_pending_pair(shard):

@@ -7,7 +7,10 @@ corpus pass), "hints_used", "bundles4" (256-query passes of bundles).
 
 ONE module-scoped shard of 150 017 rows (just beyond the 208 MiB rule, a ragged last quad, about 2.3 quads per workgroup) and 14
 cached query batches serve every scenario; the append scenario, which grows the shard by 128 rows, runs last.  No scenario of
-the list in the issue is left out or skipped."""
+the list in the issue is left out or skipped.
+
+Every output buffer, d_status included, lies between guard words (tests/guarded.py): a member's outputs are written by the tail launch
+of a LATER call, "each with its own k and outputs", and that launch must write every slot of them and nothing around them."""
 import os
 import sys
 
@@ -19,6 +22,7 @@ from rag_uq_amd import _native as nat
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_gpu_bin_records as gbr  # noqa: E402  (the record checks and their bound are imported, not copied)
+from guarded import guarded  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SCORE_TOL = 1e-6
@@ -76,14 +80,18 @@ class Shard:
         idx = self.idx
         return (int(idx.timing()["scan_launches"]), int(idx.get_option("hints_used")), int(idx.get_option("bundles4")))
 
+    def bufs(self, B, k):
+        """(scores, rows, status) of one call, each between guard words"""
+        import torch
+        return guarded((B, k), torch.float32, self.dev), guarded((B, k), torch.int64, self.dev), guarded((B,), torch.int32, self.dev)
+
     def run(self, ops):
         """ops: ("hint", qi or None, B, stream) | ("search", qi, B, k, metric, stream) | ("flush", stream) | ("release", stream) |
         ("call", f): f() runs there (another route, an append).  Returns (scan launches, hints used, 256-query bundle passes) of the
         sequence; every search is checked against the oracle over the rows the index held when it was made."""
         import torch
         idx = self.idx
-        bufs = [(torch.full((op[2], op[3]), -7.0, device=self.dev), torch.full((op[2], op[3]), -7, device=self.dev, dtype=torch.int64),
-                 torch.full((op[2],), 9, device=self.dev, dtype=torch.int32)) for op in ops if op[0] == "search"]
+        bufs = [self.bufs(op[2], op[3]) for op in ops if op[0] == "search"]
         torch.cuda.synchronize()
         idx.reset_timing()
         _, used0, b40 = self.counters()
@@ -111,8 +119,10 @@ class Shard:
         for (_, qi, B, k, metric, s), n, sc, rw, st in outs:
             es, er = self.oracle(qi, B, k, metric, n)
             where = f"q{qi} B={B} k={k} metric={metric} rows={n}"
-            assert int(st.abs().sum()) == 0, f"{where}: status {st.cpu().tolist()}"
-            got_r, got_s = rw.cpu().numpy(), sc.cpu().numpy()
+            for name, g in (("scores", sc), ("rows", rw), ("status", st)):
+                g.check(f"{where}: {name}")
+            assert int(st.view.abs().sum()) == 0, f"{where}: status {st.cpu().tolist()}"
+            got_r, got_s = rw.numpy(), sc.numpy()
             assert np.array_equal(got_r, er), f"{where}: rows differ at {np.argwhere(got_r != er)[:4].tolist()}"
             assert float(np.abs(got_s - es).max()) <= SCORE_TOL, where
 
@@ -194,6 +204,14 @@ def test_mismatch_at_each_position(shard, stream, pos, kind):
 
 def test_members_with_their_own_k(shard, stream):
     assert shard.run(_loop(list(range(10)), stream, ks={6: 1, 7: 10, 8: 50, 9: 100})) == (4, 9, 1)
+
+
+def test_members_with_their_own_B_and_k(shard, stream):
+    """B = (64, 1, 64, 17) with k = (1, 128, 10, 3) behind the three warm pairs: only the LAST member of a bundle may be ragged, so the
+    one-query call in the second place keeps the loop with pairs -- (6, 7 [1]) and (8, 9 [17]): a 128-query pass whose second half holds
+    one real query, then one with 17 --, as test_ragged_middle_member_keeps_pairs has it for B = 40.  Each tail writes [B][k] of its own
+    call and nothing else: the guards of every buffer hold."""
+    assert shard.run(_loop(list(range(10)), stream, Bs={7: 1, 9: 17}, ks={6: 1, 7: 128, 8: 10, 9: 3})) == (5, 9, 0)
 
 
 def test_ragged_last_member(shard, stream):
@@ -291,8 +309,7 @@ def test_two_streams_alternating(shard):
 def test_train_of_14_batches(shard, stream):
     import torch
     idx, k = shard.idx, 10
-    outs = [(torch.empty((64, k), device=shard.dev), torch.empty((64, k), device=shard.dev, dtype=torch.int64),
-             torch.full((64,), 9, device=shard.dev, dtype=torch.int32)) for _ in range(NQ)]
+    outs = [shard.bufs(64, k) for _ in range(NQ)]
     train = idx.make_train(shard.dqs, [o[0] for o in outs], [o[1] for o in outs], None, [o[2] for o in outs], [stream])
     torch.cuda.synchronize()
     idx.reset_timing()
