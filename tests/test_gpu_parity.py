@@ -12,6 +12,7 @@ from oracle import dense_oracle as orc
 from rag_uq_amd import _native as nat
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ingest_oracle as ino  # noqa: E402
 import nonfinite_oracle as nfo  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -1766,14 +1767,7 @@ def test_int8_bin_errors_bound_each_bin_and_lift_the_threshold():
     _check(idx, x16, q, 10)
     be = idx.debug_bin_err((n + 63) // 64)
     assert be.shape[0] == (n + 63) // 64
-    xf = x16.astype(np.float64)
-    am = np.abs(xf).max(1)
-    sr = (am.astype(np.float32) / np.float32(127.0)).astype(np.float64)
-    inv = (np.float32(127.0) / am.astype(np.float32)).astype(np.float32)
-    q8 = np.clip(np.rint(x16.astype(np.float32) * inv[:, None]), -127, 127).astype(np.float64)
-    err = np.sqrt(((xf - sr[:, None] * q8) ** 2).sum(1)) / np.sqrt((xf * xf).sum(1))
-    pad = np.zeros(((n + 63) // 64) * 64); pad[:n] = err
-    want = pad.reshape(-1, 64).max(1)
+    want = ino.int8_image(x16).bin_err.astype(np.float64)      # (the recomputation: tests/ingest_oracle.py)
     assert np.all(be >= want * (1 - 1e-6)) and np.all(be <= want * (1 + 1e-5) + 1e-9), float(np.abs(be - want).max())
     assert abs(float(be.max()) - idx.get_option("scan8_row_err")) <= 1e-6 * float(be.max())
     assert be[1000 // 64] > 1.2 * np.median(be)
