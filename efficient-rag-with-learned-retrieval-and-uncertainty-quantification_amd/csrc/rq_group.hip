@@ -203,7 +203,7 @@ static int group_fetch_rows(rq_index* idx, const rq_filter* f, const float* d_q,
     if (f) return search_filtered_device(idx, f, d_q, B, m, metric, cand, s);
     idx->t.searches++;
     idx->t.queries += B;
-    return run_pipeline(idx, d_q, B, m, metric, nb_default(idx, m), cand, s, CALL_ALLOW8);
+    return run_pipeline(idx, d_q, B, m, metric, nb_default(idx, m), cand, s, CALL_ALLOW8 | CALL_FETCH);
 }
 
 static int group_fill_empty(int B, int k, const GroupOut& out, hipStream_t s) {

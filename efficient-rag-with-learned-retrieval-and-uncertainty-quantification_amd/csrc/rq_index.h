@@ -315,6 +315,7 @@ enum CallFlags : unsigned {
     CALL_MAY_DEFER = 1,       // the caller accepts results that are complete only after rq_search_flush_device ("pipeline" option)
     CALL_FORCE_GENERIC = 2,   // the generic sorted tail, whatever "fast_tail" says
     CALL_ALLOW8 = 4,          // the int8 image may be the scan operand
+    CALL_FETCH = 8,           // the fetch of a route built on the search (MMR, grouped): like the caller's own search, what it scanned is what the ladder repairs (last_use8)
 };
 // A call that ends after its scan passes (rq_range.hip: the range tail reads the bin records itself).  In: the candidate keys the
 // workspace must hold.  Out: where the call's records, prepared queries and candidate keys are.

@@ -192,7 +192,7 @@ extern "C" int rq_search_mmr(rq_index* idx, const rq_filter* f, const float* que
     } else {
         idx->t.searches++;
         idx->t.queries += B;
-        if (int r = run_pipeline(idx, d_q, B, m, metric, nb_default(idx, m), {d_cs, d_cr, nullptr, d_status}, s, CALL_ALLOW8)) return r;
+        if (int r = run_pipeline(idx, d_q, B, m, metric, nb_default(idx, m), {d_cs, d_cr, nullptr, d_status}, s, CALL_ALLOW8 | CALL_FETCH)) return r;
     }
     if (int r = fixup_ladder(idx, f, d_q, B, m, metric, d_cs, d_cr, nullptr, d_status, s); r < 0) return r;
     if (int r = mmr_select(idx, d_cr, d_cs, B, m, k, lambda, metric, d_scores, d_rows, d_mmr, s)) return r;

@@ -56,6 +56,18 @@ static inline int scan8_kclass(int k) { return k <= RQ_SCAN8_SMALL_K ? 0 : 1; }
 // Shards that cannot stay in the 256 MiB Infinity Cache between two scans
 static inline bool beyond_cache(int64_t rows, int64_t row_bytes) { return rows * row_bytes > ((int64_t)208 << 20); }
 
+// Workgroups of a scan pass that runs wg_cu workgroups per CU (the grids: below, at CallPlan).
+static inline int scan_grid(const rq_index* idx, int nquads, int wg_cu) {
+    return (int)std::min<int64_t>(std::min<int64_t>(nquads, RQ_WGMAX_STRIDE), (int64_t)idx->cu_count * wg_cu);
+}
+// The fast tail's threshold is the m-th largest PARTITION maximum (rq_tail_body.h phase A; m = the rows wanted), and a scan pass leaves
+// one maximum per workgroup.  A pass of fewer workgroups than that has no such maximum: the threshold is -inf, every bin becomes a
+// candidate, the lists overflow, and the ladder searches every query of the pass again.  The 64-query passes run two workgroups per
+// CU, which covers RQ_FAST_MAX_K on any device of 160 CUs and more; the wide passes run ONE per CU -- 256 on an MI355X -- so a call
+// with a wide pass over the fp16 rows that wants more rows than that takes the generic tail at once (plan_call).  This is the bound
+// that can be proven; how loose the threshold already is just below it is a matter of the corpus, and stays with the ladder.
+static inline bool fast_tail_fits(const rq_index* idx, int k, int nwg) { return std::min<int64_t>(k, idx->n) <= (int64_t)nwg; }
+
 // Calls of more than 64 queries: passes of 128 queries over the image (two 16-query groups per wave, rq_scan.hip I8 = 3) while
 // the class runs with one image per query and "wide8" is on; otherwise the fp16 passes of rq_scan_wide.hip.
 // ... or while it runs with two images for its 64-query calls and one image is known to be good enough for the wide ones (wide1, rq_index.h)
@@ -115,9 +127,6 @@ struct CallPlan {
 // pass's grid served the whole call, and the remainder pass of e.g. 384 int8 queries ran at half its occupancy (232 us instead of 150).
 // (rows of 384 elements: both forms are 256-thread workgroups)
 static inline bool pass_wide(const CallPlan& p, int qb) { return qb > 64 && !p.narrow && (!p.use8 || qb == 256); }
-static inline int scan_grid(const rq_index* idx, int nquads, int wg_cu) {
-    return (int)std::min<int64_t>(std::min<int64_t>(nquads, RQ_WGMAX_STRIDE), (int64_t)idx->cu_count * wg_cu);
-}
 
 // Everything about a call of B queries on a shard that holds rows which does not depend on its stream.  nb < 0: exact scan.
 static inline int plan_call(const rq_index* idx, int B, int k, int metric, int nb, bool use8, unsigned flags, CallPlan* plan) {
@@ -173,5 +182,11 @@ static inline int plan_call(const rq_index* idx, int B, int k, int metric, int n
     p.grid_wide = scan_grid(idx, p.nquads, 1);
     p.nwg_split = p.bpad;
     for (int blk = p.npass - 1, q0 = p.bpad; blk >= 0 && !pass_wide(p, p.pass_q[blk]); --blk) p.nwg_split = (q0 -= p.pass_q[blk]);
+    // a call with a pass on the wide grid whose workgroups are fewer than the rows wanted: the generic tail (fast_tail_fits)
+    // (not over the int8 image, which only the fast tail reads: there the ladder's own count of repairs takes the class off the image)
+    if (p.fast && !use8 && p.nwg_split > 0 && !fast_tail_fits(idx, k, p.grid_wide)) {
+        p.fast = false;
+        p.ncand = (int64_t)nb * RQ_BIN_ROWS;
+    }
     return RQ_OK;
 }

@@ -706,7 +706,8 @@ int run_pipeline(rq_index* idx, const float* d_q, int B, int k, int metric, int 
         w.counters_zero = true;
     }
     if (use8) idx->scan8_used++;
-    if (may_defer) { idx->last_use8 = use8; idx->last_wide1 = use8 && B > 64 && idx->scan8_level[p.kclass] == 1; }   // (may_defer: the caller's own search, not a repair pass of rq_search_fixup_device)
+    // (may_defer: the caller's own search; CALL_FETCH: the fetch of a route -- not a repair pass of rq_search_fixup_device)
+    if (may_defer || (flags & CALL_FETCH)) { idx->last_use8 = use8; idx->last_wide1 = use8 && B > 64 && idx->scan8_level[p.kclass] == 1; }
     // unit-norm fp16 query fragments for the scan (+ padded fp32 queries / fp64 norms for the generic tail)
     // ... unless the previous launch of this stream has already prepared exactly these queries (rq_search_hint_next_device)
     const QuerySet qs = fused ? ring_slot(cx, c.slot) : w.qs;

@@ -44,7 +44,33 @@ static void check_passes(const rq_index& idx, int B, bool use8, const char* want
     if (want_split >= 0) CHECK(p.nwg_split == want_split, "B=%d use8=%d dpad=%d [%s]: nwg_split %d, expected %d", B, (int)use8, idx.dpad, want, p.nwg_split, want_split);
 }
 
-int main() {
+// `plan_check plan ROWS:DPAD:B:M:USE8 ...`: one line per shape with what plan_call decides for a search of B queries for M rows at
+// the default nb on a default index of ROWS rows of DPAD elements -- "ROWS DPAD B M USE8 exact fast nb npass pass,pass,... wanted8".
+// tests/test_route_shapes.py compares the lines with tests/route_shapes.py, the Python restatement the GPU tests rely on.
+static int print_plans(int argc, char** argv) {
+    for (int i = 2; i < argc; ++i) {
+        long long rows = 0;
+        int dpad = 0, B = 0, m = 0, use8 = 0;
+        if (std::sscanf(argv[i], "%lld:%d:%d:%d:%d", &rows, &dpad, &B, &m, &use8) != 5 || (dpad != 768 && dpad != 384)) {
+            std::printf("bad shape %s\n", argv[i]);
+            return 2;
+        }
+        rq_index idx;
+        if (dpad == 384) narrow_index(idx, rows); else fp16_index(idx, rows);
+        CallPlan p;
+        if (plan_call(&idx, B, m, RQ_METRIC_COSINE, nb_default(&idx, m), use8 != 0, CALL_ALLOW8, &p) != RQ_OK) {
+            std::printf("plan_call(%s) failed: %s\n", argv[i], rq_err_text());
+            return 2;
+        }
+        idx.scan8 = 2;                                             // ... and whether "scan8" = 2 would make the image the operand
+        const int wanted8 = (int)scan8_wanted(&idx, B, m, nb_default(&idx, m), CALL_ALLOW8);
+        std::printf("%lld %d %d %d %d %d %d %d %d %s %d\n", rows, dpad, B, m, use8, (int)p.exact, (int)p.fast, p.nb, p.npass, passes_text(p).c_str(), wanted8);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "plan") return print_plans(argc, argv);
     {   // ---- pass cutting and nwg_split --------------------------------------------------------------------------
         rq_index idx;
         fp16_index(idx, BIG);
@@ -107,6 +133,25 @@ int main() {
         CHECK(!p.fast && p.ncand == 18 * 64, "force_generic: fast %d ncand %lld", (int)p.fast, (long long)p.ncand);
         idx.fast_tail = 0;
         CHECK(!plan(idx, 64, false).fast, "fast_tail = 0");
+        // a wide pass leaves one partition maximum per workgroup, 256 of them: beyond 256 wanted rows the m-th largest does not exist
+        idx.fast_tail = 1;
+        CHECK(idx.cu_count == 256 && plan(idx, 130, false, 256).fast && plan(idx, 65, false, 256).fast && plan(idx, 300, false, 256).fast, "k = 256 on the wide grid");
+        p = plan(idx, 130, false, 257);                            // nb = 257 + 257 / 8
+        CHECK(!p.fast && !p.exact && p.nb == 289 && p.ncand == 289 * 64 && p.nwg_split == 256, "B=130 k=257: fast %d nb %d ncand %lld", (int)p.fast, p.nb, (long long)p.ncand);
+        CHECK(!plan(idx, 65, false, 320).fast && !plan(idx, 300, false, 320).fast && plan(idx, 64, false, 320).fast, "k = 320: the 64-query grid alone holds 320 maxima");
+        idx.wide_batch = 0;
+        CHECK(plan(idx, 300, false, 320).fast, "passes of 64 only");
+        idx.wide_batch = 1;
+        idx.cu_count = 304;                                        // grid_wide 304
+        CHECK(plan(idx, 130, false, 304).fast && !plan(idx, 130, false, 305).fast, "304 CUs");
+        idx.cu_count = 256;
+        CHECK(plan(idx, 130, true, 320).fast && plan(idx, 300, true, 257).fast, "the int8 image is read by the fast tail only: left to its ladder");
+        rq_index nar;
+        narrow_index(nar, BIG);
+        CHECK(plan(nar, 200, false, 320).fast, "rows of 384 elements: no wide grid");
+        rq_index small;
+        fp16_index(small, 49157);                                  // 769 bins
+        CHECK(plan(small, 130, false, 256).fast && !plan(small, 130, false, 257).fast && !plan(small, 130, false, 257).exact, "769 bins");
     }
     {   // ---- non-temporal loads: rows x scanned bytes per row beyond 208 MiB ----------------------------------------------
         rq_index idx;
